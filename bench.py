@@ -7,18 +7,27 @@ client updates per GPU, bit-exact reference-order kernel.  One "step" = one
 aggregation of the resident client rows (plus, for N > 1 GPUs, the RCCL
 all-reduce of the partial sums; clients are sharded, K per rank: weak scaling).
 
-The same JSON line carries:
-  * ``roofline``     dominant kernel (dls_fedavg_f32): algorithmic bytes per
-                     launch / its average duration from HIP events recorded on
-                     the launch stream around every launch of the timed region;
+A plain run (``--gpus 1 --steps K --warmup W``) does only what the headline needs:
+set up, W warm-up steps, K timed steps, the result line.  Its ``roofline`` is the
+dominant kernel (dls_fedavg_f32): algorithmic bytes per launch / its average
+duration from HIP events recorded on the launch stream around every launch of the
+timed region (no run of its own).  ``--dump-outputs DIR`` also writes what the
+last timed step computed, DIR/fedavg_aggregate.npy (the aggregated fp32 parameter
+row, all P padded elements): the inputs are seeded, so two builds of the library
+can be compared output for output.
+
+``--full`` adds, on the same JSON line:
   * ``cpu_baseline`` the reference's own torch op sequence (oracle restatement,
                      servers/fed_server.py:52-65) on this host's cores, bounded
                      sample, rank 0 at N = 1 only;
   * ``components``   the other BASELINE configs (sign vote 1000 x ResNet-18,
                      fed_quant 100 x VGG-16, Shapley subset GEMM 50 x ResNet-18),
                      each with its own roofline (skip with --quick).
+``--only``, ``--quick`` and ``--no-cpu-baseline`` select among the parts of a
+``--full`` run.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--quick]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+                       [--full [--quick] [--only a,b] [--no-cpu-baseline]]
 """
 import argparse
 import json
@@ -29,6 +38,7 @@ import subprocess
 import sys
 import time
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -209,7 +219,7 @@ def bench_fedavg(args, dev, rank, world, scaling="weak"):
         rf["note"] = "launch window includes chunked all-reduce overlap"
     del U
     return value, ms, rf, {"clients_per_gpu": K, "clients_total": total_clients,
-                           "params": layout.numel, "padded_row": P}
+                           "params": layout.numel, "padded_row": P}, out
 
 
 def bench_fedavg_bitexact_sharded(args, dev, world, rank):
@@ -958,7 +968,12 @@ def main():
     ap.add_argument("--subsets", type=int, default=50)
     ap.add_argument("--evals", type=int, default=8, help="timed Shapley utility evaluations per GPU")
     ap.add_argument("--eval-images", type=int, default=10000)
-    ap.add_argument("--quick", action="store_true", help="headline only (no components)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the components (other configs, sizes, sharded servers) and the "
+                         "CPU baseline; a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's aggregate as DIR/fedavg_aggregate.npy")
+    ap.add_argument("--quick", action="store_true", help="with --full: no components")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N>1")
     ap.add_argument("--only", default="", help="comma list: headline,fedavg_other_scaling,"
@@ -969,6 +984,8 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--cpu-eval-images", type=int, default=500)
     args = ap.parse_args()
+    if not args.full and args.only and set(args.only.split(",")) != {"headline"}:
+        ap.error("--only names parts of a --full run (a plain run times the headline only)")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -988,9 +1005,14 @@ def main():
     value = ms = rf = None
     extra = {}
     if want("headline"):
-        value, ms, rf, extra = bench_fedavg(args, dev, rank, world, args.scaling)
+        value, ms, rf, extra, out = bench_fedavg(args, dev, rank, world, args.scaling)
+        if args.dump_outputs and rank == 0:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "fedavg_aggregate.npy"), out.cpu().numpy())
+        del out
     components = {}
-    if world > 1 and not args.quick:  # collectives: every rank takes part, no per-rank skipping
+    # collectives: every rank takes part, no per-rank skipping
+    if args.full and world > 1 and not args.quick:
         other = "strong" if args.scaling == "weak" else "weak"
         coll = [("fedavg_other_scaling",
                  lambda *a: dict(zip(("value", "ms_per_step", "roofline", "config"),
@@ -1008,7 +1030,7 @@ def main():
             if rank == 0:
                 log(name, json.dumps(components[name]))
             torch.cuda.empty_cache()
-    if not args.quick and rank == 0:
+    if args.full and not args.quick and rank == 0:
         local_parts = [("fedavg_k1000", bench_fedavg_k1000), ("sign_vote", bench_sign),
                        ("fed_quant", bench_quant), ("fed_quant_k1000", bench_quant_k1000),
                        ("shapley_exact", bench_shapley_exact), ("shapley_gemm", bench_shapley_gemm),
@@ -1025,7 +1047,8 @@ def main():
                 components[name] = {"error": repr(e)}
             torch.cuda.empty_cache()
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and only is None:
+    if (args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
+            and only is None):
         cpu = cpu_baseline(args)
     if world > 1:
         dist.barrier()

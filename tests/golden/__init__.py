@@ -7,8 +7,66 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
+PART_BYTES = 900 * 1024  # raw array bytes per part file (every committed file stays under 1 MiB)
+
+
+class Fixture(dict):
+    """The arrays of one fixture by name, with NpzFile's ``files``."""
+
+    @property
+    def files(self):
+        return list(self)
+
+
+def save(name, arrays):
+    """Write a fixture.  One compressed ``name`` where its arrays fit PART_BYTES,
+    else ``<stem>.partNN.npz`` files: each holds whole arrays, and blocks of rows
+    ``<key>@rows<i>`` of an array that is too large for one part."""
+    stem = os.path.join(HERE, name[:-len(".npz")])
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    if sum(a.nbytes for a in arrays.values()) <= PART_BYTES:
+        np.savez_compressed(stem + ".npz", **arrays)
+        return
+    pieces = []
+    for k, a in arrays.items():
+        if a.nbytes <= PART_BYTES:
+            pieces.append((k, a))
+            continue
+        rows = max(1, PART_BYTES // (a.nbytes // a.shape[0]))
+        pieces += [(f"{k}@rows{i:04d}", a[r:r + rows])
+                   for i, r in enumerate(range(0, a.shape[0], rows))]
+    parts, size = [{}], 0
+    for k, a in pieces:
+        if parts[-1] and size + a.nbytes > PART_BYTES:
+            parts.append({})
+            size = 0
+        parts[-1][k] = a
+        size += a.nbytes
+    for i, p in enumerate(parts):
+        np.savez_compressed(f"{stem}.part{i:02d}.npz", **p)
+
+
 def load(name):
-    return np.load(os.path.join(HERE, name), allow_pickle=False)
+    """A fixture written by save(): the npz file, or its parts put together again."""
+    path = os.path.join(HERE, name)
+    if os.path.exists(path):
+        return np.load(path, allow_pickle=False)
+    stem = name[:-len(".npz")]
+    names = sorted(f for f in os.listdir(HERE)
+                   if f.startswith(stem + ".part") and f.endswith(".npz"))
+    if not names:
+        raise FileNotFoundError(path)
+    out, blocks = Fixture(), {}
+    for f in names:
+        with np.load(os.path.join(HERE, f), allow_pickle=False) as z:
+            for k in z.files:
+                if "@rows" in k:
+                    blocks.setdefault(k.split("@rows")[0], []).append((k, z[k]))
+                else:
+                    out[k] = z[k]
+    for k, bl in blocks.items():
+        out[k] = np.concatenate([a for _, a in sorted(bl, key=lambda t: t[0])])
+    return out
 
 
 def meta(npz):

@@ -11,7 +11,7 @@ mkdir -p "$OUT"
 D="$(mktemp -d /tmp/evtrace.XXXXXX)"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d "$D" -o run -- \
-    python3 -u "$ROOT/bench.py" --only shapley_evals --no-cpu-baseline > "$OUT/evals.json" 2> "$OUT/evals.log" || exit $?
+    python3 -u "$ROOT/bench.py" --full --only shapley_evals --no-cpu-baseline > "$OUT/evals.json" 2> "$OUT/evals.log" || exit $?
 for f in "$D"/run_memory_copy_stats.csv "$D"/run_kernel_stats.csv; do
     [ -f "$f" ] && cp "$f" "$OUT/evals_$(basename "$f")"
 done

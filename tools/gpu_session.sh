@@ -10,7 +10,7 @@
 #   ab:<workloads>[:<rounds>]    tools/ab_bench.py over every tools/_variants lib
 #   abv:<variants>:<workloads>[:<rounds>]   the same, only the named variants
 #   check:<variants>:<workloads> bit-identity of the named variants' outputs
-#   bench[:<bench.py args>]      python bench.py (default --steps 20 --warmup 5)
+#   bench[:<bench.py args>]      python bench.py (default --full --steps 20 --warmup 5)
 #   trace:<workloads>[:<launches>]  rocprofv3 --kernel-trace --stats of ab_bench --only-run
 #   pmc:<counters>:<workloads>   one rocprofv3 --pmc pass (counters comma-separated)
 #   pmcv:<variant>:<counters>:<workload>:<name>  one --pmc pass of one variant -> <name>.csv
@@ -61,7 +61,7 @@ for step in "$@"; do
         grep -E "^[a-z_0-9]+ (\{|skip|check)" "$log"
         ;;
     bench)
-        args="${rest:---steps 20 --warmup 5}"
+        args="${rest:---full --steps 20 --warmup 5}"
         # shellcheck disable=SC2086
         timeout -k 10 900 python -u bench.py $args > "$log" 2>&1
         rc=$?

@@ -17,7 +17,7 @@ rm -rf "$D"
 echo "conv trace: $OUT/conv_kernel_stats.csv"
 D2="$(mktemp -d /tmp/benchtrace.XXXXXX)"
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$D2" -o run -- \
-    python3 -u "$ROOT/bench.py" > "$OUT/trace_bench.json" 2> "$OUT/trace_bench.err" || exit $?
+    python3 -u "$ROOT/bench.py" --full > "$OUT/trace_bench.json" 2> "$OUT/trace_bench.err" || exit $?
 cd "$ROOT"
 cp "$D2/run_kernel_stats.csv" "$OUT/kernel_stats_all.csv"
 { head -1 "$D2/run_kernel_trace.csv"; grep "dls::" "$D2/run_kernel_trace.csv" || true; } > "$D2/kernel_trace_dls.csv"
