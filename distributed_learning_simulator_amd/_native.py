@@ -94,6 +94,7 @@ SIGNATURES = {
     "dls_conv_stem_bn_act_f32": ([_p, _i64, _i32, _i32, _i32, _p, _i32, _i32, _i32, _i32, _i32, _p,
                                   _i32, _p, _p], _i32),
     "dls_pool_linear_split": ([_p, _i64, _i32, _i32, _p, _p, _i32, _p, _p], _i32),
+    "dls_lenet5_eval_f32": ([_p, _i64, _i32, _p, _p, _i64, _p, _i32, _p, _p, _p], _i32),
 }
 
 _lib = None
@@ -143,7 +144,7 @@ def _stream(stream=None, like=None):
 
 
 CSRC_HASHED = ["dls_runtime.hip", "fedavg.hip", "sign.hip", "quant.hip", "quant_fma.hip", "shapley.hip",
-               "infer.hip", "conv.hip", "dls_common.h", "quant_common.h", os.path.join("..", "..", "include", "dls_hip.h")]
+               "infer.hip", "conv.hip", "lenet.hip", "dls_common.h", "quant_common.h", os.path.join("..", "..", "include", "dls_hip.h")]
 
 
 def source_hash():
@@ -536,6 +537,69 @@ def pool_linear(x, weight, bias=None, stream=None):
                                        _ptr(None if bias is None else bias.detach()), O, _ptr(out),
                                        _stream(stream, x)), "dls_pool_linear_split")
     return out
+
+
+# ------------------------------------------------- batched LeNet-5 evaluation
+LENET5_MAX_OUT = 32  # fc3 outputs dls_lenet5_eval_f32 takes
+LENET5_NAMES = ("conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias", "fc1.weight",
+                "fc1.bias", "fc2.weight", "fc2.bias", "fc3.weight", "fc3.bias")
+
+
+def lenet5_shapes(num_out):
+    """The ten parameter shapes of a LeNet-5 with num_out outputs, in LENET5_NAMES order."""
+    return ((6, 1, 5, 5), (6,), (16, 6, 5, 5), (16,), (120, 400), (120,), (84, 120), (84,),
+            (num_out, 84), (num_out,))
+
+
+def lenet5_eval(models, offsets, x, labels=None, logits=None, correct=None, stream=None,
+                num_out=None):
+    """S LeNet-5 models x B images in one launch (dls_lenet5_eval_f32).
+
+    models: fp32 [S, ld] (or one row [ld]), a LeNet-5 per row in the flat layout;
+    offsets: the ten element offsets of LENET5_NAMES within a row
+    (ParameterLayout.offsets); x: fp32 [B, 1, 32, 32] contiguous; labels: int64
+    [B] (needed for correct).  Outputs, at least one: logits fp32 [S, B, O] and /
+    or correct int64 [S], which is accumulated into (zero it first).  O is
+    logits' last dimension, else num_out.  Returns (logits, correct)."""
+    fn = "lenet5_eval"
+    if models.dim() == 1:
+        models = models.unsqueeze(0)
+    if (models.dtype != torch.float32 or models.dim() != 2 or models.stride(1) != 1
+            or (models.shape[0] > 1 and models.stride(0) < models.shape[1])):
+        raise RuntimeError(f"{fn}: models must be fp32 [S, ld] rows with unit element stride")
+    if (x.dtype != torch.float32 or x.dim() != 4 or tuple(x.shape[1:]) != (1, 32, 32)
+            or not x.is_contiguous()):
+        raise RuntimeError(f"{fn}: x must be a contiguous fp32 [B, 1, 32, 32] tensor")
+    offsets = [int(o) for o in offsets]
+    if len(offsets) != 10:
+        raise RuntimeError(f"{fn}: ten offsets expected ({', '.join(LENET5_NAMES)})")
+    S, B = models.shape[0], x.shape[0]
+    if logits is None and correct is None:
+        raise RuntimeError(f"{fn}: give logits [S, B, O] and / or correct [S]")
+    _check_same_device(fn, x, models=models, labels=labels, logits=logits, correct=correct)
+    if labels is not None and (labels.dtype != torch.int64 or tuple(labels.shape) != (B,)
+                               or not labels.is_contiguous()):
+        raise RuntimeError(f"{fn}: labels must be a contiguous int64 [B] tensor")
+    if correct is not None:
+        if labels is None:
+            raise RuntimeError(f"{fn}: correct needs labels")
+        if (correct.dtype != torch.int64 or tuple(correct.shape) != (S,)
+                or not correct.is_contiguous()):
+            raise RuntimeError(f"{fn}: correct must be a contiguous int64 [S] tensor")
+    if logits is not None:
+        if (logits.dtype != torch.float32 or logits.dim() != 3
+                or tuple(logits.shape[:2]) != (S, B) or not logits.is_contiguous()):
+            raise RuntimeError(f"{fn}: logits must be a contiguous fp32 [S, B, O] tensor")
+        if num_out is not None and int(num_out) != logits.shape[2]:
+            raise RuntimeError(f"{fn}: num_out={num_out} but logits has {logits.shape[2]} outputs")
+        num_out = logits.shape[2]
+    elif num_out is None:
+        raise RuntimeError(f"{fn}: num_out is needed without logits")
+    ldm = models.stride(0) if S > 1 else models.shape[1]
+    _check(lib().dls_lenet5_eval_f32(_ptr(models), ldm, S, (ctypes.c_int64 * 10)(*offsets),
+                                     _ptr(x), B, _ptr(labels), int(num_out), _ptr(logits),
+                                     _ptr(correct), _stream(stream, x)), "dls_lenet5_eval_f32")
+    return logits, correct
 
 
 def split_to_f32(x):

@@ -24,6 +24,71 @@ class LeNet5(nn.Module):
         x = x.flatten(1)
         return self.fc3(F.relu(self.fc2(F.relu(self.fc1(x)))))
 
+    # ---- the library's deterministic eval forward (csrc/lenet.hip): the whole
+    # network one launch in fp32, every sum in an order fixed by the layer shapes,
+    # for one model (forward_split) or a matrix of flat-layout rows (count_rows)
+    def split_layout(self):
+        """The flat ParameterLayout of this module's named_parameters."""
+        from .layout import ParameterLayout
+        return ParameterLayout((n, tuple(p.shape)) for n, p in self.named_parameters())
+
+    def split_supports(self, shape):
+        """Whether forward_split takes inputs of `shape`: [*, 1, 32, 32] images into
+        this architecture with 1..32 outputs."""
+        from . import _native
+        o = self.fc3.out_features
+        lay = self.split_layout()
+        return (len(shape) == 4 and tuple(shape[1:]) == (1, 32, 32)
+                and 1 <= o <= _native.LENET5_MAX_OUT
+                and tuple(lay.names) == _native.LENET5_NAMES
+                and tuple(lay.shapes) == _native.lenet5_shapes(o))
+
+    def split_rows_match(self, layout):
+        """Whether rows of `layout` are this module's parameters (names and shapes)."""
+        return layout == self.split_layout()
+
+    @torch.no_grad()
+    def pack_split(self):
+        """The operand of forward_split: {"row": one ParameterLayout.flatten of the
+        parameters into a fresh row}.  A copy: the module may be overwritten once
+        this returns while the forward is still queued."""
+        lay = self.split_layout()
+        return {"row": lay.flatten(dict(self.named_parameters()))}
+
+    def split_activation_bytes(self, H, W):
+        """Device bytes one image holds in forward_split: the fp32 input and the
+        logits (every activation stays on chip)."""
+        return 4 * self.conv1.in_channels * H * W + 4 * self.fc3.out_features
+
+    @staticmethod
+    def _split_offsets(layout):
+        from . import _native
+        return [layout.offset_of(n) for n in _native.LENET5_NAMES]
+
+    def forward_split(self, x, pk):
+        """forward() in eval mode through dls_lenet5_eval_f32 (S = 1): logits [B, O],
+        the same bits for the same model and image in any batch, process or stream.
+        x: NCHW fp32 [B, 1, 32, 32]; pk = pack_split()."""
+        from . import _native
+        if not self.split_supports(x.shape):
+            raise RuntimeError(f"LeNet5.forward_split: unsupported input {tuple(x.shape)} or "
+                               f"{self.fc3.out_features} outputs")
+        logits = torch.empty((1, x.shape[0], self.fc3.out_features), dtype=torch.float32,
+                             device=x.device)
+        _native.lenet5_eval(pk["row"], self._split_offsets(self.split_layout()), x.contiguous(),
+                            logits=logits)
+        return logits[0]
+
+    def count_rows(self, rows, layout, x, labels, correct, stream=None):
+        """correct[s] += the top-1 hits of model rows[s] on (x, labels): S models of
+        `layout` (this module's names and shapes, split_rows_match) read in place
+        from the device matrix rows [S, ld], one launch; the module's own
+        parameters are not read."""
+        from . import _native
+        _native.lenet5_eval(rows, self._split_offsets(layout), x, labels=labels, correct=correct,
+                            num_out=self.fc3.out_features, stream=stream)
+        return correct
+
 
 class _Block(nn.Module):
     def __init__(self, cin, cout, stride):

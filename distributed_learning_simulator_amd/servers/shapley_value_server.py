@@ -57,7 +57,15 @@ class ShapleyValueServer(FedServer):
         return self._streams
 
     def evaluate_subsets(self, subsets):
-        """Utilities of coalitions (tuples of worker ids) -> list of floats, in order."""
+        """Utilities of coalitions (tuples of worker ids) -> list of floats, in order.
+
+        With a tester that scores a matrix of flat rows in one launch
+        (``Inferencer.correct_many``: models.LeNet5) a batch's subset models are
+        evaluated in place, ``int(count) / n`` each, and the tester module's
+        parameters are NOT overwritten per coalition.  Nothing depends on them:
+        ``FedServer.get_metric`` loads its model before every evaluation, and the
+        only other reader in the package is ``FedServer.__init__`` (the initial
+        ``prev_model`` copy)."""
         subsets = [tuple(s) for s in subsets]
         world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         rank = dist.get_rank() if world > 1 else 0
@@ -71,7 +79,19 @@ class ShapleyValueServer(FedServer):
         # (not when a subclass or the instance replaces get_metric)
         queued = (getattr(self.get_metric, "__func__", None) is FedServer.get_metric
                   and self.tester is not None and hasattr(self.tester, "correct_async"))
-        streams = self._eval_stream_list() if queued else None
+        # a tester that scores a whole matrix of flat rows in one launch
+        # (Inferencer.correct_many: models.LeNet5): the batch's subset models are
+        # read in place from the matrix subset_models returned, the empty coalition
+        # (prev_model) from one more flattened row.  The tester module's parameters
+        # are not overwritten on this path: get_metric always loads a model before
+        # it evaluates (fed_server.get_metric) and nothing else in the package reads
+        # the tester's parameters after construction (FedServer.__init__ copies them
+        # into prev_model once), so no caller sees the difference.
+        many = (queued and hasattr(self.tester, "correct_many")
+                and getattr(self.tester, "supports_correct_many", None) is not None
+                and self.tester.supports_correct_many(store.layout)
+                and (not self.prev_model or store.layout.matches(self.prev_model)))
+        streams = self._eval_stream_list() if queued and not many else None
         for b0 in range(0, len(mine), bs):
             idx = mine[b0:b0 + bs]
             nonempty = [i for i in idx if subsets[i]]
@@ -80,6 +100,22 @@ class ShapleyValueServer(FedServer):
                 rows = [[self.parameters.row_of(w) for w in subsets[i]] for i in nonempty]
                 out = store.subset_models(rows, self.parameters.n_of_row(), method=self.subset_method)
             pos = {i: k for k, i in enumerate(nonempty)}
+            if many:
+                n = self.tester.dataset[0].shape[0]
+                counts = []
+                if nonempty:
+                    counts.append(self.tester.correct_many(out[:len(nonempty)], store.layout))
+                empty = [i for i in idx if not subsets[i]]
+                if empty:
+                    row = store.layout.flatten(self.prev_model, device=store.device)
+                    counts.append(self.tester.correct_many(row.unsqueeze(0), store.layout))
+                counts = torch.cat(counts).tolist()  # one synchronisation
+                for i in idx:
+                    c = counts[pos[i]] if subsets[i] else counts[-1]
+                    values[i] = int(c) / n
+                    self.evaluated_subsets.append(subsets[i])
+                self.tester.accuracy_metric.value = values[idx[-1]]
+                continue
             pending = []
             for i in idx:
                 model = store.layout.views(out[pos[i]]) if subsets[i] else self.prev_model

@@ -89,6 +89,12 @@ class Inferencer:
     differ from the module's fp32 forward in the low bits, top-1 only at near-ties
     (tests/test_gpu_conv.py).
 
+    models.LeNet5's split path is one fp32 kernel for the whole network
+    (csrc/lenet.hip; [*, 1, 32, 32] inputs, at most 32 outputs: the model's
+    ``split_supports`` decides, other inputs run the module's forward), and
+    ``correct_many`` scores a matrix of flat-layout models with it in one launch
+    (tests/test_gpu_lenet.py).
+
     ``conv="miopen"`` runs torch / MIOpen convolutions instead.  MIOpen's default
     algorithms are not run-to-run reproducible on this stack (the 512-channel
     layers of ResNet-18 gave different bits for the same input), so that path
@@ -175,7 +181,44 @@ class Inferencer:
         if not (self.fused_eval and self.conv == "dls" and self.dataset[0].dim() == 4
                 and torch.device(self.device).type == "cuda"):
             return None
+        # the model decides which inputs its split forward takes (models.LeNet5:
+        # [*, 1, 32, 32] only); without the hook every 4-d input is taken
+        supports = getattr(self.model, "split_supports", None)
+        if supports is not None and not supports(tuple(self.dataset[0].shape)):
+            return None
         return getattr(self.model, "forward_split", None)
+
+    def supports_correct_many(self, layout):
+        """Whether correct_many scores rows of `layout`: the split path is active, the
+        model has the batched entry (models.LeNet5.count_rows) and the layout's
+        names and shapes are the module's named_parameters."""
+        if self._split_forward() is None:
+            return False
+        if not (hasattr(self.model, "count_rows") and hasattr(self.model, "split_rows_match")):
+            return False
+        return bool(self.model.split_rows_match(layout))
+
+    @torch.no_grad()
+    def correct_many(self, rows, layout):
+        """Top-1 correct counts over the dataset of S models at once: ``rows`` is a
+        device fp32 [S, ld] matrix of flat rows of ``layout`` (the Shapley store's
+        subset models), read in place.  Returns a device int64 [S] tensor, with no
+        host synchronisation; ``int(count) / n`` is ``inference()``'s accuracy of
+        that model (the same logits bits, the same argmax rule).  The module's own
+        parameters are neither read nor written."""
+        if not self.supports_correct_many(layout):
+            raise RuntimeError("Inferencer.correct_many: not available for this model / layout "
+                               "(see supports_correct_many)")
+        X, y = self._resident_dataset()
+        n = X.shape[0]
+        correct = torch.zeros(rows.shape[0] if rows.dim() == 2 else 1, dtype=torch.int64,
+                              device=self.device)
+        bs = self.split_batch(n)
+        for i in range(0, n, bs):
+            xb = X[i:i + bs].to(self.device, torch.float32, non_blocking=True).contiguous()
+            yb = y[i:i + bs].to(self.device, torch.int64, non_blocking=True).contiguous()
+            self.model.count_rows(rows, layout, xb, yb, correct)
+        return correct
 
     def _flags(self):
         if (not self.deterministic or torch.device(self.device).type != "cuda"

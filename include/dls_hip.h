@@ -323,6 +323,36 @@ int dls_conv_stem_bn_act_f32(const float *x, int64_t B, int32_t C, int32_t H, in
 int dls_pool_linear_split(const uint16_t *x, int64_t B, int32_t HW, int32_t C, const float *weight,
                           const float *bias, int32_t O, float *out, dls_stream_t stream);
 
+/* Batched deterministic LeNet-5 utility evaluation (the tester's model forward
+ * and top-1 count behind servers/fed_server.py:26-32 for the reference's MNIST /
+ * LeNet-5 example; csrc/lenet.hip): S models x B images in one launch.
+ *   models  fp32 [S, ldm]     one LeNet-5 per row, read in place (a row of the
+ *                             Shapley store's subset models, or one flat row)
+ *   offsets int64 [10], HOST  element offset within a row of conv1.weight
+ *                             [6,1,5,5], conv1.bias, conv2.weight [16,6,5,5],
+ *                             conv2.bias, fc1.weight [120,400], fc1.bias,
+ *                             fc2.weight [84,120], fc2.bias, fc3.weight [O,84],
+ *                             fc3.bias (the flat layout's offsets); multiples of
+ *                             4, every tensor inside ldm
+ *   x       fp32 [B,1,32,32]  contiguous
+ *   labels  int64 [B]         may be null when correct is null
+ *   O       1..32             fc3's outputs
+ *   logits  fp32 [S,B,O] or null
+ *   correct int64 [S] or null correct[s] += #{b : argmax_o logits[s,b,:] ==
+ *                             labels[b]} (accumulated; the caller zeroes it);
+ *                             argmax as torch.argmax: the lowest index among
+ *                             equal maxima, a NaN logit is a maximum
+ * At least one output is non-null.  The function is the eval forward conv 5x5 ->
+ * ReLU -> 2x2 max-pool (twice), flatten [c][y][x], fc1-ReLU-fc2-ReLU-fc3 with
+ * biases, in fp32 (values, products, accumulation); every output's reduction
+ * order is fixed by the layer shapes alone (not by B, S, ldm, the image's or
+ * the model's position, the grid or the stream) and the count is an integer
+ * atomic: the same bits in any process.  B == 0 returns 0 without a launch.
+ * models, x and logits 16-byte aligned; ldm a multiple of 4. */
+int dls_lenet5_eval_f32(const float *models, int64_t ldm, int32_t S, const int64_t *offsets,
+                        const float *x, int64_t B, const int64_t *labels, int32_t O,
+                        float *logits, int64_t *correct, dls_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

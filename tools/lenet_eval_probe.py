@@ -1,0 +1,119 @@
+"""LeNet-5 utility evaluation rates on the GPU.
+
+  workload  a multiround-style Shapley round: N clients (default 10: 1,024
+            coalitions) scored on a 10,000-image synthetic MNIST-shaped test set
+            through ShapleyValueServer.evaluate_subsets, in utility evaluations
+            per second (wall clock around the synchronised call, after a warm-up
+            round; the best and the median of --repeats).  --conv miopen runs the
+            tester's module / MIOpen path.  Uses only the server interface, so
+            the same file measures an older tree (PYTHONPATH=<that tree>).
+  kernel    dls_lenet5_eval_f32 alone, S = 64 models x B = 10,000 images, HIP
+            event timing over --repeats launches after 3 warm-up launches, as a
+            fraction of the 157.3 TFLOP/s fp32 MFMA peak at 2 x 416,520 FLOP per
+            image and model.
+
+Prints one JSON line per measurement.
+"""
+import argparse
+import itertools
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+# the tree this file lies in, unless PYTHONPATH names another one first
+sys.path.append(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+MACS = 416_520  # conv1 117,600 + conv2 240,000 + fc1 48,000 + fc2 10,080 + fc3 840
+PEAK = 157.3e12
+
+
+def workload(args, dev):
+    from distributed_learning_simulator_amd.models import LeNet5, synthetic_classification
+    from distributed_learning_simulator_amd.servers.multiround_shapley_value_server import \
+        MultiRoundShapleyValueServer
+    from distributed_learning_simulator_amd.trainer import Inferencer
+    torch.manual_seed(0)
+    base = LeNet5()
+    X, y = synthetic_classification(args.images, (1, 32, 32), seed=1)
+    kw = {} if args.conv is None else {"conv": args.conv}
+    tester = Inferencer(LeNet5().to(dev), (X, y), device=dev, **kw)
+    N = args.clients
+    server = MultiRoundShapleyValueServer(tester=tester, worker_number=N, synchronous=True,
+                                          metric_dir=None)
+    g = torch.Generator().manual_seed(2)
+    for i in range(N):
+        server.parameters[i] = (100 + i, {k: v.detach() + 0.01 * torch.randn(v.shape, generator=g)
+                                          for k, v in base.named_parameters()})
+    subsets = [s for r in range(N + 1) for s in itertools.combinations(range(N), r)]
+    times = []
+    for rep in range(args.repeats + 1):  # the first round is the warm-up
+        server.evaluated_subsets = []
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        values = server.evaluate_subsets(subsets)
+        torch.cuda.synchronize(dev)
+        if rep:
+            times.append(time.perf_counter() - t0)
+    batched = bool(getattr(tester, "supports_correct_many", lambda _l: False)(
+        server.parameters.store.layout))
+    print(json.dumps({"probe": "workload", "clients": N, "coalitions": len(subsets),
+                      "images": args.images, "conv": getattr(tester, "conv", None),
+                      "batched": batched, "split": tester._split_forward() is not None,
+                      "evals_per_s_best": len(subsets) / min(times),
+                      "evals_per_s_median": len(subsets) / statistics.median(times),
+                      "round_s": sorted(times), "distinct_utilities": len(set(values))}))
+
+
+def kernel(args, dev):
+    from distributed_learning_simulator_amd import _native
+    from distributed_learning_simulator_amd.models import LeNet5, synthetic_classification
+    S, B = args.models, args.images
+    torch.manual_seed(0)
+    m = LeNet5()
+    lay = m.split_layout()
+    row = lay.flatten(dict(m.named_parameters()), device=dev)
+    M = row.repeat(S, 1) * (1 + 0.01 * torch.arange(S, device=dev)[:, None])
+    X, y = synthetic_classification(B, (1, 32, 32), seed=1)
+    X, y = X.to(dev), y.to(dev)
+    off = [lay.offset_of(n) for n in _native.LENET5_NAMES]
+    correct = torch.zeros(S, dtype=torch.int64, device=dev)
+    for _ in range(3):
+        _native.lenet5_eval(M, off, X, labels=y, correct=correct, num_out=10)
+    torch.cuda.synchronize(dev)
+    ms = []
+    for _ in range(args.repeats):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        _native.lenet5_eval(M, off, X, labels=y, correct=correct, num_out=10)
+        e1.record()
+        e1.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    flop = 2.0 * MACS * S * B
+    best, med = min(ms), statistics.median(ms)
+    print(json.dumps({"probe": "kernel", "S": S, "B": B, "ms_best": best, "ms_median": med,
+                      "tflops_median": flop / (med * 1e-3) / 1e12,
+                      "fraction_of_fp32_mfma_peak_median": flop / (med * 1e-3) / PEAK,
+                      "model_evals_per_s_median": S / (med * 1e-3), "ms": sorted(ms)}))
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__,
+                                 formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("what", choices=["workload", "kernel"])
+    ap.add_argument("--clients", type=int, default=10)
+    ap.add_argument("--images", type=int, default=10000)
+    ap.add_argument("--models", type=int, default=64)
+    ap.add_argument("--conv", choices=["dls", "miopen"], default=None)
+    ap.add_argument("--repeats", type=int, default=5)
+    args = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    (workload if args.what == "workload" else kernel)(args, dev)
+
+
+if __name__ == "__main__":
+    main()
