@@ -95,6 +95,10 @@ SIGNATURES = {
                                   _i32, _p, _p], _i32),
     "dls_pool_linear_split": ([_p, _i64, _i32, _i32, _p, _p, _i32, _p, _p], _i32),
     "dls_lenet5_eval_f32": ([_p, _i64, _i32, _p, _p, _i64, _p, _i32, _p, _p, _p], _i32),
+    "dls_lenet5_eval_loss_f32": ([_p, _i64, _i32, _p, _p, _i64, _p, _i32, _p, _p, _p, _i64, _p],
+                                 _i32),
+    "dls_softmax_ce_f32": ([_p, _i32, _i64, _i32, _p, _p, _i64, _p], _i32),
+    "dls_sum_rows_f64": ([_p, _i64, _i32, _i64, _p, _p], _i32),
 }
 
 _lib = None
@@ -144,7 +148,8 @@ def _stream(stream=None, like=None):
 
 
 CSRC_HASHED = ["dls_runtime.hip", "fedavg.hip", "sign.hip", "quant.hip", "quant_fma.hip", "shapley.hip",
-               "infer.hip", "conv.hip", "lenet.hip", "dls_common.h", "quant_common.h", os.path.join("..", "..", "include", "dls_hip.h")]
+               "infer.hip", "conv.hip", "lenet.hip", "loss.hip", "dls_common.h", "quant_common.h",
+               "loss_common.h", os.path.join("..", "..", "include", "dls_hip.h")]
 
 
 def source_hash():
@@ -551,16 +556,73 @@ def lenet5_shapes(num_out):
             (num_out, 84), (num_out,))
 
 
+def _loss_rows(fn, loss, S, B):
+    """The row pitch of a per-image loss output: fp32 [S, B] with unit element
+    stride, rows at any pitch >= B (a column window of a wider [S, n] buffer)."""
+    if (loss.dtype != torch.float32 or tuple(loss.shape) != (S, B)
+            or (B > 1 and loss.stride(1) != 1) or (S > 1 and loss.stride(0) < B)):
+        raise RuntimeError(f"{fn}: loss must be fp32 [S, B] with unit element stride and a row "
+                           "pitch of at least B")
+    return loss.stride(0) if S > 1 else B
+
+
+def softmax_ce(logits, labels, loss=None, stream=None):
+    """Per-image cross-entropy of fp32 logits [S, B, O] (or [B, O]) against int64
+    labels [B] (dls_softmax_ce_f32): fp32 [S, B], written into ``loss`` when given
+    (see _loss_rows).  Any O >= 1; a label outside [0, O) gives NaN."""
+    fn = "softmax_ce"
+    if logits.dim() == 2:
+        logits = logits.unsqueeze(0)
+    if logits.dtype != torch.float32 or logits.dim() != 3 or not logits.is_contiguous():
+        raise RuntimeError(f"{fn}: logits must be a contiguous fp32 [S, B, O] tensor")
+    S, B, O = logits.shape
+    if labels.dtype != torch.int64 or tuple(labels.shape) != (B,) or not labels.is_contiguous():
+        raise RuntimeError(f"{fn}: labels must be a contiguous int64 [B] tensor")
+    if loss is None:
+        loss = torch.empty((S, B), dtype=torch.float32, device=logits.device)
+    _check_same_device(fn, logits, labels=labels, loss=loss)
+    ldn = _loss_rows(fn, loss, S, B)
+    _check(lib().dls_softmax_ce_f32(_ptr(logits), S, B, O, _ptr(labels), _ptr(loss), ldn,
+                                    _stream(stream, logits)), "dls_softmax_ce_f32")
+    return loss
+
+
+def sum_rows_f64(v, out=None, stream=None):
+    """out[s] = the fp64 sum of row s of the fp32 matrix v [S, n] (unit element
+    stride, any row pitch >= n), in an order fixed by n alone (dls_sum_rows_f64).
+    Returns fp64 [S]."""
+    fn = "sum_rows_f64"
+    if (v.dtype != torch.float32 or v.dim() != 2 or v.shape[0] < 1
+            or (v.shape[1] > 1 and v.stride(1) != 1)
+            or (v.shape[0] > 1 and v.stride(0) < v.shape[1])):
+        raise RuntimeError(f"{fn}: v must be fp32 [S >= 1, n] with unit element stride")
+    S, n = v.shape
+    if out is None:
+        out = torch.empty((S,), dtype=torch.float64, device=v.device)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (S,) or not out.is_contiguous():
+        raise RuntimeError(f"{fn}: out must be a contiguous fp64 [S] tensor")
+    _check_same_device(fn, v, out=out)
+    ldn = v.stride(0) if S > 1 else n
+    # an empty tensor may have no storage: nothing of v is read when n == 0, so any
+    # valid device address serves
+    vp = _ptr(v) if n > 0 or v.data_ptr() else _ptr(out)
+    _check(lib().dls_sum_rows_f64(vp, ldn, S, n, _ptr(out), _stream(stream, v)),
+           "dls_sum_rows_f64")
+    return out
+
+
 def lenet5_eval(models, offsets, x, labels=None, logits=None, correct=None, stream=None,
-                num_out=None):
+                num_out=None, loss=None):
     """S LeNet-5 models x B images in one launch (dls_lenet5_eval_f32).
 
     models: fp32 [S, ld] (or one row [ld]), a LeNet-5 per row in the flat layout;
     offsets: the ten element offsets of LENET5_NAMES within a row
     (ParameterLayout.offsets); x: fp32 [B, 1, 32, 32] contiguous; labels: int64
-    [B] (needed for correct).  Outputs, at least one: logits fp32 [S, B, O] and /
-    or correct int64 [S], which is accumulated into (zero it first).  O is
-    logits' last dimension, else num_out.  Returns (logits, correct)."""
+    [B] (needed for correct and loss).  Outputs, at least one: logits fp32 [S, B, O],
+    correct int64 [S], which is accumulated into (zero it first), and loss fp32
+    [S, B] (see _loss_rows), the per-image cross-entropy; with loss the launch is
+    dls_lenet5_eval_loss_f32.  O is logits' last dimension, else num_out.  Returns
+    (logits, correct)."""
     fn = "lenet5_eval"
     if models.dim() == 1:
         models = models.unsqueeze(0)
@@ -574,9 +636,11 @@ def lenet5_eval(models, offsets, x, labels=None, logits=None, correct=None, stre
     if len(offsets) != 10:
         raise RuntimeError(f"{fn}: ten offsets expected ({', '.join(LENET5_NAMES)})")
     S, B = models.shape[0], x.shape[0]
-    if logits is None and correct is None:
-        raise RuntimeError(f"{fn}: give logits [S, B, O] and / or correct [S]")
-    _check_same_device(fn, x, models=models, labels=labels, logits=logits, correct=correct)
+    if logits is None and correct is None and loss is None:
+        raise RuntimeError(f"{fn}: give logits [S, B, O] and / or correct [S]"
+                           " and / or loss [S, B]")
+    _check_same_device(fn, x, models=models, labels=labels, logits=logits, correct=correct,
+                       loss=loss)
     if labels is not None and (labels.dtype != torch.int64 or tuple(labels.shape) != (B,)
                                or not labels.is_contiguous()):
         raise RuntimeError(f"{fn}: labels must be a contiguous int64 [B] tensor")
@@ -596,6 +660,15 @@ def lenet5_eval(models, offsets, x, labels=None, logits=None, correct=None, stre
     elif num_out is None:
         raise RuntimeError(f"{fn}: num_out is needed without logits")
     ldm = models.stride(0) if S > 1 else models.shape[1]
+    if loss is not None:
+        if labels is None:
+            raise RuntimeError(f"{fn}: loss needs labels")
+        ldn = _loss_rows(fn, loss, S, B)
+        _check(lib().dls_lenet5_eval_loss_f32(_ptr(models), ldm, S, (ctypes.c_int64 * 10)(*offsets),
+                                              _ptr(x), B, _ptr(labels), int(num_out), _ptr(logits),
+                                              _ptr(correct), _ptr(loss), ldn, _stream(stream, x)),
+               "dls_lenet5_eval_loss_f32")
+        return logits, correct
     _check(lib().dls_lenet5_eval_f32(_ptr(models), ldm, S, (ctypes.c_int64 * 10)(*offsets),
                                      _ptr(x), B, _ptr(labels), int(num_out), _ptr(logits),
                                      _ptr(correct), _stream(stream, x)), "dls_lenet5_eval_f32")

@@ -28,12 +28,15 @@
 // is fixed by the layer shapes: an MFMA column (one image, or one image's pooled
 // position) never sees another column's data, invalid images of a ragged tile
 // are zero inputs whose results are dropped, and nothing is combined in arrival
-// order.  The correct count is an integer atomic, one per block.
+// order.  The correct count is an integer atomic, one per block.  The loss
+// instantiation (dls_lenet5_eval_loss_f32) adds one epilogue: a lane per image
+// runs ce_row (loss_common.h) on the image's logits in LDS and stores the loss.
 //
 // LDS: pooled conv1 activations 16 x 1176 fp32 (73.5 KB; the fc activations
 // alias them once conv2 is done), features 16 x 402, conv weights 10.5 KB:
 // ~110 KB, one block of 4 waves per CU.
 #include "dls_common.h"
+#include "loss_common.h"
 
 namespace dls {
 namespace {
@@ -104,10 +107,12 @@ __device__ __forceinline__ void fc_layer(const float *__restrict__ W, const floa
     }
 }
 
+// kLoss = false is the kernel dls_lenet5_eval_f32 launches: loss / ldn are unused
+template <bool kLoss>
 __global__ __launch_bounds__(kThreads) void k_lenet5_eval(
     const float *__restrict__ models, int64_t ldm, LenetOffsets off, const float *__restrict__ x,
     int64_t B, const int64_t *__restrict__ labels, int O, int tiles, float *__restrict__ logits,
-    unsigned long long *__restrict__ correct) {
+    unsigned long long *__restrict__ correct, float *__restrict__ loss, int64_t ldn) {
     __shared__ __attribute__((aligned(16))) float p1[kT * kP1];
     __shared__ __attribute__((aligned(16))) float feat[kT * kFeatLd];
     __shared__ __attribute__((aligned(16))) float w2t[kK2p * 16];  // [k][co]
@@ -239,6 +244,10 @@ __global__ __launch_bounds__(kThreads) void k_lenet5_eval(
             if (b < B) logits[((int64_t)s * B + b) * O + o] = lg[img * kLgLd + o];
         }
     }
+    if constexpr (kLoss) {
+        const int64_t b = b0 + tid;
+        if (tid < kT && b < B) loss[(int64_t)s * ldn + b] = ce_row(lg + tid * kLgLd, 1, O, labels[b]);
+    }
     if (correct && tid < 64) {
         bool hit = false;
         const int64_t b = b0 + tid;
@@ -265,51 +274,81 @@ __global__ __launch_bounds__(kThreads) void k_lenet5_eval(
 
 using namespace dls;
 
-extern "C" int dls_lenet5_eval_f32(const float *models, int64_t ldm, int32_t S,
-                                   const int64_t *offsets, const float *x, int64_t B,
-                                   const int64_t *labels, int32_t O, float *logits,
-                                   int64_t *correct, dls_stream_t stream) {
+// Both entry points: fn names the caller in the messages; with_loss is the newer
+// one, whose third output (loss, row pitch ldn) is optional like the other two.
+static int lenet5_eval(const char *fn, bool with_loss, const float *models, int64_t ldm, int32_t S,
+                       const int64_t *offsets, const float *x, int64_t B, const int64_t *labels,
+                       int32_t O, float *logits, int64_t *correct, float *loss, int64_t ldn,
+                       dls_stream_t stream) {
     static const char *const kNames[10] = {"conv1.weight", "conv1.bias", "conv2.weight",
                                            "conv2.bias",   "fc1.weight", "fc1.bias",
                                            "fc2.weight",   "fc2.bias",   "fc3.weight",
                                            "fc3.bias"};
-    DLS_REQUIRE(models, DLS_EINVAL, "dls_lenet5_eval_f32: null pointer: models");
-    DLS_REQUIRE(offsets, DLS_EINVAL, "dls_lenet5_eval_f32: null pointer: offsets");
-    DLS_REQUIRE(x, DLS_EINVAL, "dls_lenet5_eval_f32: null pointer: x");
-    DLS_REQUIRE(logits || correct, DLS_EINVAL,
-                "dls_lenet5_eval_f32: logits and correct are both null");
-    DLS_REQUIRE(labels || !correct, DLS_EINVAL,
-                "dls_lenet5_eval_f32: null pointer: labels (needed for correct)");
-    DLS_REQUIRE(S >= 1, DLS_EINVAL, "dls_lenet5_eval_f32: S=%d (at least 1)", S);
-    DLS_REQUIRE(B >= 0, DLS_EINVAL, "dls_lenet5_eval_f32: B=%lld (negative)", (long long)B);
-    DLS_REQUIRE(O >= 1 && O <= kOMax, DLS_EINVAL, "dls_lenet5_eval_f32: O=%d (1..%d)", O, kOMax);
+    DLS_REQUIRE(models, DLS_EINVAL, "%s: null pointer: models", fn);
+    DLS_REQUIRE(offsets, DLS_EINVAL, "%s: null pointer: offsets", fn);
+    DLS_REQUIRE(x, DLS_EINVAL, "%s: null pointer: x", fn);
+    if (with_loss) {
+        DLS_REQUIRE(logits || correct || loss, DLS_EINVAL,
+                    "%s: logits, correct and loss are all null", fn);
+        DLS_REQUIRE(labels || !(correct || loss), DLS_EINVAL,
+                    "%s: null pointer: labels (needed for correct and loss)", fn);
+    } else {
+        DLS_REQUIRE(logits || correct, DLS_EINVAL, "%s: logits and correct are both null", fn);
+        DLS_REQUIRE(labels || !correct, DLS_EINVAL,
+                    "%s: null pointer: labels (needed for correct)", fn);
+    }
+    DLS_REQUIRE(S >= 1, DLS_EINVAL, "%s: S=%d (at least 1)", fn, S);
+    DLS_REQUIRE(B >= 0, DLS_EINVAL, "%s: B=%lld (negative)", fn, (long long)B);
+    DLS_REQUIRE(O >= 1 && O <= kOMax, DLS_EINVAL, "%s: O=%d (1..%d)", fn, O, kOMax);
+    DLS_REQUIRE(!loss || ldn >= B, DLS_EINVAL, "%s: ldn=%lld is less than B=%lld", fn,
+                (long long)ldn, (long long)B);
     const int64_t tiles = (B + kT - 1) / kT;
-    DLS_REQUIRE(tiles * S < (int64_t)1 << 31, DLS_EINVAL,
-                "dls_lenet5_eval_f32: S=%d x B=%lld exceeds one grid", S, (long long)B);
-    DLS_REQUIRE(aligned16(models), DLS_ELAYOUT, "dls_lenet5_eval_f32: models: 16-byte alignment");
-    DLS_REQUIRE(aligned16(x), DLS_ELAYOUT, "dls_lenet5_eval_f32: x: 16-byte alignment");
-    DLS_REQUIRE(!logits || aligned16(logits), DLS_ELAYOUT,
-                "dls_lenet5_eval_f32: logits: 16-byte alignment");
+    DLS_REQUIRE(tiles * S < (int64_t)1 << 31, DLS_EINVAL, "%s: S=%d x B=%lld exceeds one grid", fn,
+                S, (long long)B);
+    DLS_REQUIRE(aligned16(models), DLS_ELAYOUT, "%s: models: 16-byte alignment", fn);
+    DLS_REQUIRE(aligned16(x), DLS_ELAYOUT, "%s: x: 16-byte alignment", fn);
+    DLS_REQUIRE(!logits || aligned16(logits), DLS_ELAYOUT, "%s: logits: 16-byte alignment", fn);
     DLS_REQUIRE((reinterpret_cast<uintptr_t>(labels) & 7u) == 0, DLS_ELAYOUT,
-                "dls_lenet5_eval_f32: labels: 8-byte alignment");
+                "%s: labels: 8-byte alignment", fn);
     DLS_REQUIRE((reinterpret_cast<uintptr_t>(correct) & 7u) == 0, DLS_ELAYOUT,
-                "dls_lenet5_eval_f32: correct: 8-byte alignment");
-    DLS_REQUIRE(ldm > 0 && ldm % 4 == 0, DLS_ELAYOUT,
-                "dls_lenet5_eval_f32: ldm=%lld (a positive multiple of 4)", (long long)ldm);
+                "%s: correct: 8-byte alignment", fn);
+    DLS_REQUIRE((reinterpret_cast<uintptr_t>(loss) & 3u) == 0, DLS_ELAYOUT,
+                "%s: loss: 4-byte alignment", fn);
+    DLS_REQUIRE(ldm > 0 && ldm % 4 == 0, DLS_ELAYOUT, "%s: ldm=%lld (a positive multiple of 4)", fn,
+                (long long)ldm);
     const int64_t numel[10] = {150, 6, 2400, 16, 48000, 120, 10080, 84, (int64_t)O * 84, O};
     LenetOffsets off;
     for (int i = 0; i < 10; ++i) {
         DLS_REQUIRE(offsets[i] >= 0 && offsets[i] % 4 == 0, DLS_ELAYOUT,
-                    "dls_lenet5_eval_f32: offsets[%d] (%s) = %lld (a non-negative multiple of 4)", i,
-                    kNames[i], (long long)offsets[i]);
+                    "%s: offsets[%d] (%s) = %lld (a non-negative multiple of 4)", fn, i, kNames[i],
+                    (long long)offsets[i]);
         DLS_REQUIRE(offsets[i] <= ldm - numel[i], DLS_EINVAL,
-                    "dls_lenet5_eval_f32: offsets[%d] (%s) = %lld: the tensor ends past ldm=%lld", i,
-                    kNames[i], (long long)offsets[i], (long long)ldm);
+                    "%s: offsets[%d] (%s) = %lld: the tensor ends past ldm=%lld", fn, i, kNames[i],
+                    (long long)offsets[i], (long long)ldm);
         off.o[i] = offsets[i];
     }
     if (B == 0) return DLS_OK;
-    hipLaunchKernelGGL(k_lenet5_eval, dim3((unsigned)(tiles * S)), dim3(kThreads), 0,
-                       as_stream(stream), models, ldm, off, x, B, labels, (int)O, (int)tiles, logits,
-                       reinterpret_cast<unsigned long long *>(correct));
-    return check_launch("dls_lenet5_eval_f32");
+    // without loss: the instantiation with no loss code, whichever entry was called
+    auto *kernel = loss ? k_lenet5_eval<true> : k_lenet5_eval<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(tiles * S)), dim3(kThreads), 0, as_stream(stream),
+                       models, ldm, off, x, B, labels, (int)O, (int)tiles, logits,
+                       reinterpret_cast<unsigned long long *>(correct), loss, ldn);
+    return check_launch(fn);
+}
+
+extern "C" int dls_lenet5_eval_f32(const float *models, int64_t ldm, int32_t S,
+                                   const int64_t *offsets, const float *x, int64_t B,
+                                   const int64_t *labels, int32_t O, float *logits,
+                                   int64_t *correct, dls_stream_t stream) {
+    return lenet5_eval("dls_lenet5_eval_f32", false, models, ldm, S, offsets, x, B, labels, O, logits,
+                       correct, nullptr, 0, stream);
+}
+
+extern "C" int dls_lenet5_eval_loss_f32(const float *models, int64_t ldm, int32_t S,
+                                        const int64_t *offsets, const float *x, int64_t B,
+                                        const int64_t *labels, int32_t O, float *logits,
+                                        int64_t *correct, float *loss, int64_t ldn,
+                                        dls_stream_t stream) {
+    return lenet5_eval("dls_lenet5_eval_loss_f32", true, models, ldm, S, offsets, x, B, labels, O,
+                       logits, correct, loss, ldn, stream);
 }

@@ -89,6 +89,21 @@ class LeNet5(nn.Module):
                             num_out=self.fc3.out_features, stream=stream)
         return correct
 
+    def score_rows(self, rows, layout, x, labels, correct, loss, col0=0, stream=None):
+        """count_rows plus the per-image cross-entropy, one launch
+        (dls_lenet5_eval_loss_f32): correct[s] += the top-1 hits of model rows[s] on
+        the B images (x, labels), and loss[s, col0 + b] = image b's loss under that
+        model (loss: fp32 [S, n >= col0 + B], the whole test set's buffer)."""
+        from . import _native
+        B = x.shape[0]
+        if loss.dim() != 2 or col0 < 0 or col0 + B > loss.shape[1]:
+            raise RuntimeError(f"LeNet5.score_rows: columns [{col0}, {col0 + B}) are not inside "
+                               f"loss {tuple(loss.shape)}")
+        _native.lenet5_eval(rows, self._split_offsets(layout), x, labels=labels, correct=correct,
+                            loss=loss[:, col0:col0 + B], num_out=self.fc3.out_features,
+                            stream=stream)
+        return correct, loss
+
 
 class _Block(nn.Module):
     def __init__(self, cin, cout, stride):

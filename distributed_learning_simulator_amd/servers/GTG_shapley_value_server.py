@@ -41,8 +41,8 @@ class GTGShapleyValueServer(ShapleyValueServer):
     def _process_aggregated_parameter(self, aggregated_parameter: dict):
         N = self.worker_number
         self.evaluated_subsets = []
-        last_round_metric = self.get_metric(self.prev_model)
-        this_round_metric = self.get_metric(aggregated_parameter)
+        last_round_metric = self.utility(self.prev_model)
+        this_round_metric = self.utility(aggregated_parameter)
         log.info("last_round_metric %s ,this_round_metric %s, round_trunc_threshold %s",
                  last_round_metric, this_round_metric, self.round_trunc_threshold)
         if abs(last_round_metric - this_round_metric) <= self.round_trunc_threshold:

@@ -36,8 +36,8 @@ class MultiRoundShapleyValueServer(ShapleyValueServer):
         self.evaluated_subsets = []
         metrics = dict()
         if self.round_trunc_threshold is not None:
-            last_round_metric = self.get_metric(self.prev_model)
-            this_round_metric = self.get_metric(aggregated_parameter)
+            last_round_metric = self.utility(self.prev_model)
+            this_round_metric = self.utility(aggregated_parameter)
             metrics[()] = last_round_metric
             metrics[tuple(sorted(range(N)))] = this_round_metric
             log.info("this_round_metric %s last_round_metric %s round_trunc_threshold %s",

@@ -9,6 +9,13 @@ model is scored with ``get_metric`` (servers/fed_server.py:26-32).  Under
 ``torch.distributed`` with several ranks the coalitions are dealt round-robin
 over the ranks and the utilities are summed with one all-reduce (each rank
 fills only its own entries), so every rank ends with the full table.
+
+``utility_metric="loss"`` makes the utility the tester's mean cross-entropy
+(``get_metric(model, "loss")``, unnegated: the sign convention is the caller's)
+instead of the top-1 accuracy, on the same fast paths: every image's loss is
+computed in fp32 by one lane and the mean is one fixed-order fp64 sum
+(``Inferencer.metrics_many`` / ``metrics_async``), so a coalition's loss is a
+function of the coalition, the same bits in any batch, chunking or process.
 """
 import inspect
 from itertools import chain, combinations
@@ -21,8 +28,12 @@ from .fed_server import FedServer
 
 
 class ShapleyValueServer(FedServer):
-    def __init__(self, subset_method="exact", subset_batch=None, eval_streams=1, **kwargs):
+    def __init__(self, subset_method="exact", subset_batch=None, eval_streams=1,
+                 utility_metric="acc", **kwargs):
+        if utility_metric not in ("acc", "loss"):
+            raise ValueError(f"utility_metric must be 'acc' or 'loss', not {utility_metric!r}")
         super().__init__(**kwargs)
+        self.utility_metric = utility_metric
         self.subset_method = subset_method
         self.subset_batch = subset_batch
         # queued utility forwards in flight at once, one HIP stream each (1: all
@@ -56,6 +67,36 @@ class ShapleyValueServer(FedServer):
             self._streams = [torch.cuda.Stream(dev) for _ in range(self.eval_streams)]
         return self._streams
 
+    def _metrics_tester(self):
+        """Whether the loss utility runs on the tester's deterministic entries: a GPU
+        tester with metrics_async, and get_metric not replaced by a subclass or on
+        the instance (a replaced get_metric is the user's own utility)."""
+        t = self.tester
+        return (getattr(self.get_metric, "__func__", None) is FedServer.get_metric
+                and t is not None and hasattr(t, "metrics_async")
+                and torch.device(getattr(t, "device", None) or "cpu").type == "cuda")
+
+    def _set_tester_metrics(self, acc, loss):
+        """The tester's state as get_metric leaves it: the last evaluated model's."""
+        self.tester.accuracy_metric.value = acc
+        self.tester.loss_metric.value = torch.tensor(loss, dtype=torch.float64)
+
+    def utility(self, model):
+        """The utility of one model (the round metrics of the GTG and multiround
+        servers): get_metric(model) for "acc"; for "loss" the mean loss, from the
+        tester's metrics_async when it has one (the same float evaluate_subsets
+        returns for that model), else get_metric(model, "loss")."""
+        if self.utility_metric == "acc":
+            return self.get_metric(model)
+        if not self._metrics_tester():
+            return self.get_metric(model, "loss")
+        ModelUtil(self.tester.model).load_parameter_dict(model)
+        correct, loss_sum = self.tester.metrics_async()
+        n = self.tester.dataset[0].shape[0]
+        c, l = torch.stack([correct.double(), loss_sum]).tolist()  # one synchronisation
+        self._set_tester_metrics(int(c) / n, l / n)
+        return l / n
+
     def evaluate_subsets(self, subsets):
         """Utilities of coalitions (tuples of worker ids) -> list of floats, in order.
 
@@ -77,8 +118,14 @@ class ShapleyValueServer(FedServer):
         # synchronisation: the batch's evaluations are queued back to back and
         # their counts read once (int(count) / n: the same floats as get_metric)
         # (not when a subclass or the instance replaces get_metric)
+        # utility_metric="loss": the same two paths through the tester's metrics_many /
+        # metrics_async, which return (count, fp64 loss sum); the utility is
+        # float(sum) / n
+        loss = self.utility_metric == "loss"
         queued = (getattr(self.get_metric, "__func__", None) is FedServer.get_metric
                   and self.tester is not None and hasattr(self.tester, "correct_async"))
+        if loss:
+            queued = self._metrics_tester()
         # a tester that scores a whole matrix of flat rows in one launch
         # (Inferencer.correct_many: models.LeNet5): the batch's subset models are
         # read in place from the matrix subset_models returned, the empty coalition
@@ -91,7 +138,9 @@ class ShapleyValueServer(FedServer):
                 and getattr(self.tester, "supports_correct_many", None) is not None
                 and self.tester.supports_correct_many(store.layout)
                 and (not self.prev_model or store.layout.matches(self.prev_model)))
-        streams = self._eval_stream_list() if queued and not many else None
+        if loss:
+            many = many and hasattr(self.tester, "metrics_many")
+        streams = self._eval_stream_list() if queued and not many and not loss else None
         for b0 in range(0, len(mine), bs):
             idx = mine[b0:b0 + bs]
             nonempty = [i for i in idx if subsets[i]]
@@ -103,12 +152,23 @@ class ShapleyValueServer(FedServer):
             if many:
                 n = self.tester.dataset[0].shape[0]
                 counts = []
+                score = self.tester.metrics_many if loss else self.tester.correct_many
                 if nonempty:
-                    counts.append(self.tester.correct_many(out[:len(nonempty)], store.layout))
+                    counts.append(score(out[:len(nonempty)], store.layout))
                 empty = [i for i in idx if not subsets[i]]
                 if empty:
                     row = store.layout.flatten(self.prev_model, device=store.device)
-                    counts.append(self.tester.correct_many(row.unsqueeze(0), store.layout))
+                    counts.append(score(row.unsqueeze(0), store.layout))
+                if loss:
+                    both = torch.stack([torch.cat([c for c, _ in counts]).double(),
+                                        torch.cat([l for _, l in counts])]).tolist()  # one sync
+                    for i in idx:
+                        k = pos[i] if subsets[i] else -1
+                        values[i] = both[1][k] / n
+                        self.evaluated_subsets.append(subsets[i])
+                    k = pos[idx[-1]] if subsets[idx[-1]] else -1
+                    self._set_tester_metrics(int(both[0][k]) / n, both[1][k] / n)
+                    continue
                 counts = torch.cat(counts).tolist()  # one synchronisation
                 for i in idx:
                     c = counts[pos[i]] if subsets[i] else counts[-1]
@@ -121,13 +181,15 @@ class ShapleyValueServer(FedServer):
                 model = store.layout.views(out[pos[i]]) if subsets[i] else self.prev_model
                 if queued:
                     ModelUtil(self.tester.model).load_parameter_dict(model)
-                    if streams:
+                    if loss:
+                        c = torch.stack([t.double() for t in self.tester.metrics_async()])
+                    elif streams:
                         c = self.tester.correct_async(stream=streams[len(pending) % len(streams)])
                     else:
                         c = self.tester.correct_async()
                     pending.append((i, c))
                 else:
-                    values[i] = float(self.get_metric(model))
+                    values[i] = float(self.utility(model))
                 self.evaluated_subsets.append(subsets[i])
             if pending:
                 if streams:
@@ -136,6 +198,11 @@ class ShapleyValueServer(FedServer):
                         cur.wait_stream(st)
                 n = self.tester.dataset[0].shape[0]
                 counts = torch.stack([c for _, c in pending]).tolist()  # one synchronisation
+                if loss:
+                    for (i, _), (c, l) in zip(pending, counts):
+                        values[i] = l / n
+                    self._set_tester_metrics(int(counts[-1][0]) / n, counts[-1][1] / n)
+                    continue
                 for (i, _), c in zip(pending, counts):
                     values[i] = int(c) / n
                 # the tester's state as get_metric leaves it: its accuracy metric holds

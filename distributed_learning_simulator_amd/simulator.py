@@ -54,16 +54,24 @@ def get_config(argv=None):
     # process), or "miopen", torch's fp32 forward with MIOpen's deterministic
     # algorithms (the reference tester's arithmetic, ~4x slower)
     ap.add_argument("--tester_conv", type=str, default="dls", choices=("dls", "miopen"))
+    # the utility the two Shapley servers score coalitions with: the tester's top-1
+    # accuracy ("acc", the reference's) or its mean cross-entropy ("loss",
+    # get_metric(model, "loss"), unnegated), both on the deterministic evaluation path
+    ap.add_argument("--utility_metric", type=str, default="acc", choices=("acc", "loss"))
     return ap.parse_args(argv)
 
 
 def server_kwargs(config):
     """The keyword arguments run() passes to factory.get_server beside tester /
     worker_number / multi_process: the aggregation mode for the FedAvg-based
-    servers (sign_SGD votes; it has no FedAvg)."""
+    servers (sign_SGD votes; it has no FedAvg), and the utility metric for the two
+    Shapley servers."""
     if config.distributed_algorithm == "sign_SGD":
         return {}
-    return {"aggregation_mode": config.aggregation_mode}
+    kwargs = {"aggregation_mode": config.aggregation_mode}
+    if config.distributed_algorithm in ("GTG_shapley_value", "multiround_shapley_value"):
+        kwargs["utility_metric"] = getattr(config, "utility_metric", "acc")
+    return kwargs
 
 
 def get_cuda_devices():

@@ -95,6 +95,12 @@ class Inferencer:
     ``correct_many`` scores a matrix of flat-layout models with it in one launch
     (tests/test_gpu_lenet.py).
 
+    ``metrics_many`` / ``metrics_async`` add the loss as a utility that is a
+    function of the coalition too: one fp32 cross-entropy per image, computed by
+    one lane, and one fixed-order fp64 sum over the test set (csrc/loss.hip;
+    tests/test_gpu_loss.py).  ``inference()``'s loss stays torch's reduction per
+    forward batch, whose bits move with ``split_batch``.
+
     ``conv="miopen"`` runs torch / MIOpen convolutions instead.  MIOpen's default
     algorithms are not run-to-run reproducible on this stack (the 512-channel
     layers of ResNet-18 gave different bits for the same input), so that path
@@ -349,6 +355,65 @@ class Inferencer:
             for out, yb in self._batches():
                 correct += (out.argmax(1) == yb).sum()
         return correct
+
+    @torch.no_grad()
+    def metrics_many(self, rows, layout):
+        """correct_many plus the loss: (top-1 correct counts int64 [S], per-model sums
+        of the per-image cross-entropy fp64 [S]) of S flat rows of ``layout`` over
+        the dataset, device tensors, no host synchronisation.  ``float(sum) / n`` is
+        the mean loss.  One pass in split_batch chunks, each one launch that stores
+        every image's fp32 loss in an [S, n] buffer (models.LeNet5.score_rows), then
+        one fixed-order fp64 sum per row (dls_sum_rows_f64): the bits depend on the
+        model and the dataset alone, not on the chunking, S, the row or the stream.
+        The precondition is supports_correct_many."""
+        from . import _native
+        if not (self.supports_correct_many(layout) and hasattr(self.model, "score_rows")):
+            raise RuntimeError("Inferencer.metrics_many: not available for this model / layout "
+                               "(see supports_correct_many)")
+        if rows.dim() == 1:
+            rows = rows.unsqueeze(0)
+        X, y = self._resident_dataset()
+        n, S = X.shape[0], rows.shape[0]
+        correct = torch.zeros(S, dtype=torch.int64, device=self.device)
+        loss = torch.empty((S, n), dtype=torch.float32, device=self.device)
+        bs = self.split_batch(n)
+        for i in range(0, n, bs):
+            xb = X[i:i + bs].to(self.device, torch.float32, non_blocking=True).contiguous()
+            yb = y[i:i + bs].to(self.device, torch.int64, non_blocking=True).contiguous()
+            self.model.score_rows(rows, layout, xb, yb, correct, loss, i)
+        return correct, _native.sum_rows_f64(loss)
+
+    @torch.no_grad()
+    def metrics_async(self):
+        """(top-1 correct count int64, sum of the per-image cross-entropy fp64) of the
+        module's current parameters over the dataset, 0-d device tensors, no host
+        synchronisation: ``float(sum) / n`` is the mean loss, a function of the
+        model and the dataset alone.  Any model on a GPU tester.  A model with the
+        batched entry (models.LeNet5 on the split path) is scored as its own flat
+        row: the same bits as that row of metrics_many.  Any other model: the
+        logits of ``inference()``'s batches, their per-image losses
+        (dls_softmax_ce_f32) into one [1, n] buffer and one dls_sum_rows_f64."""
+        from . import _native
+        if torch.device(self.device).type != "cuda":
+            raise RuntimeError("Inferencer.metrics_async needs a GPU tester (no CPU fallback)")
+        if self._split_forward() is not None and hasattr(self.model, "score_rows"):
+            lay = self.model.split_layout()
+            if self.supports_correct_many(lay):
+                self.model.eval()
+                correct, loss_sum = self.metrics_many(self.model.pack_split()["row"], lay)
+                return correct[0], loss_sum[0]
+        with self._flags():
+            n = self.dataset[0].shape[0]
+            correct = torch.zeros((), dtype=torch.int64, device=self.device)
+            loss = torch.empty((1, n), dtype=torch.float32, device=self.device)
+            i = 0
+            for out, yb in self._batches():
+                b = out.shape[0]
+                correct += (out.argmax(1) == yb).sum()
+                _native.softmax_ce(out.float().contiguous(), yb.to(torch.int64).contiguous(),
+                                   loss=loss[:, i:i + b])
+                i += b
+            return correct, _native.sum_rows_f64(loss)[0]
 
     @torch.no_grad()
     def inference(self):

@@ -353,6 +353,36 @@ int dls_lenet5_eval_f32(const float *models, int64_t ldm, int32_t S, const int64
                         const float *x, int64_t B, const int64_t *labels, int32_t O,
                         float *logits, int64_t *correct, dls_stream_t stream);
 
+/* Deterministic loss utilities (the tester's mean cross-entropy, get_metric(model,
+ * "loss"), servers/fed_server.py:26-32; csrc/loss.hip, csrc/loss_common.h).
+ * The per-image loss of both kernels is one function, in fp32 and index order:
+ *   m = max_o z[o] (a NaN is a maximum), s = sum_o expf(z[o] - m) for o ascending,
+ *   loss = (m - z[label]) + logf(s)
+ * with the device library's expf / logf, computed by one lane per image; a label
+ * outside [0, O) gives NaN and reads nothing.
+ * dls_softmax_ce_f32: loss[s*ldn + b] of logits fp32 [S, B, O] (contiguous, 16-byte
+ * aligned), labels int64 [B]; S >= 1, B >= 0 (0: no launch), O >= 1, ldn >= B. */
+int dls_softmax_ce_f32(const float *logits, int32_t S, int64_t B, int32_t O, const int64_t *labels,
+                       float *loss, int64_t ldn, dls_stream_t stream);
+/* dls_lenet5_eval_f32 with a third optional output (servers/fed_server.py:26-32, the
+ * loss metric): loss fp32, loss[s*ldn + b] = the cross-entropy above of
+ * logits[s,b,:] and labels[b], ldn >= B, stored by the launch that computes the
+ * logits (the same bits as dls_softmax_ce_f32 of them).  At least one of logits,
+ * correct, loss is non-null; labels is needed for correct and for loss.  logits
+ * and correct are the bits dls_lenet5_eval_f32 gives. */
+int dls_lenet5_eval_loss_f32(const float *models, int64_t ldm, int32_t S, const int64_t *offsets,
+                             const float *x, int64_t B, const int64_t *labels, int32_t O,
+                             float *logits, int64_t *correct, float *loss, int64_t ldn,
+                             dls_stream_t stream);
+/* The sum the mean loss of servers/fed_server.py:26-32 divides by n:
+ * out[s] = sum_{i<n} (double) v[s*ldn + i], S >= 1 rows, n >= 0 (0: out[s] = 0.0),
+ * ldn >= n, out fp64 [S].  One block of 256 threads per row: thread t adds
+ * elements t, t + 256, ... in ascending order in fp64, then the 256 partials are
+ * combined by a fixed pairwise tree: the order is a function of n alone (not of
+ * S, ldn, the row or the stream), so the same values give the same bits. */
+int dls_sum_rows_f64(const float *v, int64_t ldn, int32_t S, int64_t n, double *out,
+                     dls_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,10 +7,15 @@
             round; the best and the median of --repeats).  --conv miopen runs the
             tester's module / MIOpen path.  Uses only the server interface, so
             the same file measures an older tree (PYTHONPATH=<that tree>).
+            --metric loss scores the mean cross-entropy instead
+            (utility_metric="loss"); with --replaced-get-metric it runs the only
+            route a tree without that keyword has: a server whose get_metric is
+            replaced by one returning get_metric(model, "loss").
   kernel    dls_lenet5_eval_f32 alone, S = 64 models x B = 10,000 images, HIP
             event timing over --repeats launches after 3 warm-up launches, as a
             fraction of the 157.3 TFLOP/s fp32 MFMA peak at 2 x 416,520 FLOP per
-            image and model.
+            image and model.  --metric loss times dls_lenet5_eval_loss_f32
+            (count + per-image loss) and the one dls_sum_rows_f64 launch after it.
 
 Prints one JSON line per measurement.
 """
@@ -42,8 +47,15 @@ def workload(args, dev):
     kw = {} if args.conv is None else {"conv": args.conv}
     tester = Inferencer(LeNet5().to(dev), (X, y), device=dev, **kw)
     N = args.clients
+    skw = {}
+    if args.metric == "loss" and not args.replaced_get_metric:
+        skw["utility_metric"] = "loss"
     server = MultiRoundShapleyValueServer(tester=tester, worker_number=N, synchronous=True,
-                                          metric_dir=None)
+                                          metric_dir=None, **skw)
+    if args.metric == "loss" and args.replaced_get_metric:
+        from distributed_learning_simulator_amd.servers.fed_server import FedServer
+        server.get_metric = lambda model, metric_type="acc": FedServer.get_metric(
+            server, model, "loss")
     g = torch.Generator().manual_seed(2)
     for i in range(N):
         server.parameters[i] = (100 + i, {k: v.detach() + 0.01 * torch.randn(v.shape, generator=g)
@@ -60,7 +72,8 @@ def workload(args, dev):
             times.append(time.perf_counter() - t0)
     batched = bool(getattr(tester, "supports_correct_many", lambda _l: False)(
         server.parameters.store.layout))
-    print(json.dumps({"probe": "workload", "clients": N, "coalitions": len(subsets),
+    print(json.dumps({"probe": "workload", "metric": args.metric,
+                      "replaced_get_metric": bool(args.replaced_get_metric), "clients": N, "coalitions": len(subsets),
                       "images": args.images, "conv": getattr(tester, "conv", None),
                       "batched": batched, "split": tester._split_forward() is not None,
                       "evals_per_s_best": len(subsets) / min(times),
@@ -81,20 +94,34 @@ def kernel(args, dev):
     X, y = X.to(dev), y.to(dev)
     off = [lay.offset_of(n) for n in _native.LENET5_NAMES]
     correct = torch.zeros(S, dtype=torch.int64, device=dev)
+    kw, sum_ms = {}, []
+    if args.metric == "loss":
+        kw["loss"] = torch.empty((S, B), dtype=torch.float32, device=dev)
+        sums = torch.empty(S, dtype=torch.float64, device=dev)
     for _ in range(3):
-        _native.lenet5_eval(M, off, X, labels=y, correct=correct, num_out=10)
+        _native.lenet5_eval(M, off, X, labels=y, correct=correct, num_out=10, **kw)
+        if kw:
+            _native.sum_rows_f64(kw["loss"], out=sums)
     torch.cuda.synchronize(dev)
     ms = []
     for _ in range(args.repeats):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
         e0.record()
-        _native.lenet5_eval(M, off, X, labels=y, correct=correct, num_out=10)
+        _native.lenet5_eval(M, off, X, labels=y, correct=correct, num_out=10, **kw)
         e1.record()
-        e1.synchronize()
+        if kw:
+            _native.sum_rows_f64(kw["loss"], out=sums)
+        e2.record()
+        e2.synchronize()
         ms.append(e0.elapsed_time(e1))
+        if kw:
+            sum_ms.append(e1.elapsed_time(e2))
     flop = 2.0 * MACS * S * B
     best, med = min(ms), statistics.median(ms)
-    print(json.dumps({"probe": "kernel", "S": S, "B": B, "ms_best": best, "ms_median": med,
+    extra = {"sum_rows_ms_median": statistics.median(sum_ms), "sum_rows_ms": sorted(sum_ms)} \
+        if sum_ms else {}
+    print(json.dumps({"probe": "kernel", "metric": args.metric, **extra, "S": S, "B": B,
+                      "ms_best": best, "ms_median": med,
                       "tflops_median": flop / (med * 1e-3) / 1e12,
                       "fraction_of_fp32_mfma_peak_median": flop / (med * 1e-3) / PEAK,
                       "model_evals_per_s_median": S / (med * 1e-3), "ms": sorted(ms)}))
@@ -109,6 +136,9 @@ def main():
     ap.add_argument("--models", type=int, default=64)
     ap.add_argument("--conv", choices=["dls", "miopen"], default=None)
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--metric", choices=["acc", "loss"], default="acc")
+    ap.add_argument("--replaced-get-metric", action="store_true",
+                    help="workload --metric loss through a replaced get_metric (any tree)")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
