@@ -94,6 +94,8 @@ SIGNATURES = {
     "dls_conv_stem_bn_act_f32": ([_p, _i64, _i32, _i32, _i32, _p, _i32, _i32, _i32, _i32, _i32, _p,
                                   _i32, _p, _p], _i32),
     "dls_pool_linear_split": ([_p, _i64, _i32, _i32, _p, _p, _i32, _p, _p], _i32),
+    "dls_conv_kernel_choice": ([_i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32], _i32),
+    "dls_conv_stem_kernel_choice": ([_i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32], _i32),
     "dls_lenet5_eval_f32": ([_p, _i64, _i32, _p, _p, _i64, _p, _i32, _p, _p, _p], _i32),
     "dls_lenet5_eval_loss_f32": ([_p, _i64, _i32, _p, _p, _i64, _p, _i32, _p, _p, _p, _i64, _p],
                                  _i32),
@@ -410,6 +412,29 @@ def _overlaps(a, b):
 def split_channels(c):
     """The padded channel count of a split tensor: a multiple of 32."""
     return (int(c) + 31) // 32 * 32
+
+
+# DLS_CONV_KERNEL_* / DLS_STEM_KERNEL_* (include/dls_hip.h): id -> kernel instantiation
+CONV_KERNELS = {
+    0: "none", 1: "generic<1,4>", 2: "generic<2,2>", 3: "pipe<1,4,10,1,2>", 4: "pipe<1,4,12,1,2>",
+    5: "pipe<2,2,5,1,2>", 6: "pipe<2,4,5>", 7: "pipe<2,4,6>", 8: "halo<2,2,9,false>",
+    9: "halo<2,2,9,true>", 10: "halo<1,4,11,false>", 11: "halo<1,4,11,true>", 12: "phase<2,4,5>",
+}
+STEM_KERNELS = {0: "none", 1: "window", 2: "3x3", 3: "generic"}
+
+
+def conv_kernel_choice(B, H, W, C, Cout, ksize, stride, pad):
+    """The kernel id (CONV_KERNELS) conv_bn_act launches for a shape, or the negative
+    status it would fail with (dls_conv_kernel_choice: host only, needs no GPU)."""
+    kh, kw = ksize
+    return int(lib().dls_conv_kernel_choice(B, H, W, C, Cout, kh, kw, stride, pad))
+
+
+def conv_stem_kernel_choice(B, C, H, W, Cout, ksize, stride, pad):
+    """The kernel id (STEM_KERNELS) conv_stem_bn_act launches for a shape, or the
+    negative status it would fail with (dls_conv_stem_kernel_choice: host only)."""
+    kh, kw = ksize
+    return int(lib().dls_conv_stem_kernel_choice(B, C, H, W, Cout, kh, kw, stride, pad))
 
 
 def conv_pack_input(x, stream=None):

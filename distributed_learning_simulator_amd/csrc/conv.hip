@@ -106,11 +106,16 @@ __device__ __forceinline__ uint32_t bf16_rne(float x) {
     return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
 }
 
-// x = hi + lo + O(2^-17 |x|); lo = 0 for non-finite x (hi carries the inf / NaN)
+// x = hi + lo + O(2^-17 |x|); lo = 0 whenever hi is not finite (hi carries the
+// inf / NaN): an inf or NaN x, and a finite |x| >= 0x7f7f8000, which rounds to
+// bf16 infinity as a plain bf16 conversion does (x - hi would be the opposite
+// infinity and hi + lo a NaN).  The test is taken on r = x - hi, which is
+// non-finite exactly when hi is (a finite hi has a finite x; inf - inf and
+// NaN - hi are NaN, finite - inf is inf): one v_cmp_class, as the test on x was.
 __device__ __forceinline__ void split2(float x, uint32_t &hi, uint32_t &lo) {
     hi = bf16_rne(x);
     const float r = x - __uint_as_float(hi << 16);
-    lo = (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u ? 0u : bf16_rne(r);
+    lo = (__float_as_uint(r) & 0x7f800000u) == 0x7f800000u ? 0u : bf16_rne(r);
 }
 
 __device__ __forceinline__ float bf16_to_f32(uint32_t h) { return __uint_as_float(h << 16); }
@@ -127,8 +132,8 @@ __device__ __forceinline__ void split2x2(float a, float b, uint32_t &hi2, uint32
     hi2 = __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{a, b}, bf16x2));
     float ra = a - __uint_as_float(hi2 << 16);
     float rb = b - __uint_as_float(hi2 & 0xffff0000u);
-    ra = (__float_as_uint(a) & 0x7f800000u) == 0x7f800000u ? 0.f : ra;
-    rb = (__float_as_uint(b) & 0x7f800000u) == 0x7f800000u ? 0.f : rb;
+    ra = (__float_as_uint(ra) & 0x7f800000u) == 0x7f800000u ? 0.f : ra;  // split2's rule: lo = 0 under a
+    rb = (__float_as_uint(rb) & 0x7f800000u) == 0x7f800000u ? 0.f : rb;  // non-finite hi (r non-finite)
     lo2 = __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{ra, rb}, bf16x2));
 }
 
@@ -1487,6 +1492,163 @@ __global__ __launch_bounds__(kPoolBlock) void k_pool_linear(const uint16_t *__re
     }
 }
 
+// ---- the kernel choice: pure host functions of the shape (no device call, no
+// stream, no process state), shared by the launch (dls_conv_bn_act_split) and
+// the query (dls_conv_kernel_choice).  Each fit_* fills the ConvArgs tile fields
+// (TI / TR / NH / pix_tiles / co_tiles) and returns whether its kernel takes
+// the shape.
+template <int WCO, int WPIX>
+bool fit_generic(ConvArgs &a) {
+    a.pix_tiles = (a.M + kWaveTile * WPIX - 1) / (kWaveTile * WPIX);
+    a.co_tiles = a.Cout / (kWaveTile * WCO);
+    return (int64_t)a.pix_tiles * a.co_tiles <= INT32_MAX;
+}
+
+// The halo kernel when the pixel tile can be whole output rows
+template <int WCO, int WPIX, int NHMAX>
+bool fit_halo(ConvArgs &a) {
+    constexpr int BNP = kWaveTile * WPIX;
+    constexpr int RPP = 64 * WCO * WPIX / (kBK / 4);
+    const int H = a.H, W = a.W;
+    if (W > BNP || BNP % W) return false;
+    const int TR = H < BNP / W ? H : BNP / W;
+    int TI = 1;
+    if (TR == H) {
+        if (BNP % (H * W)) return false;
+        TI = BNP / (H * W);
+    } else if (H % TR) {
+        return false;
+    }
+    const int NH = TI * (TR + 2) * (W + 2);
+    if (NH > RPP * NHMAX) return false;
+    a.TI = TI;
+    a.TR = TR;
+    a.NH = NH;
+    a.pix_tiles = (a.M + BNP - 1) / BNP;
+    a.co_tiles = a.Cout / (kWaveTile * WCO);
+    return (int64_t)a.pix_tiles * a.co_tiles <= INT32_MAX;
+}
+
+// The stride-2 phase pipeline (k_conv3x3s2_phase) when its phase halos fit NHI
+// DMAs per wave
+template <int WCO, int WPIX, int NHI>
+bool fit_phase(ConvArgs &a) {
+    constexpr int BNP = kWaveTile * WPIX;
+    const int H = a.H, W = a.W, Ho = a.Ho, Wo = a.Wo;
+    if ((H | W) & 1 || 2 * Ho != H || 2 * Wo != W || 32 % Wo || a.Cout % (kWaveTile * WCO)) return false;
+    if ((int64_t)a.B * H * W >= (1ll << 30)) return false;  // input pixel indices in 32 bits
+    const int TR = Ho < BNP / Wo ? Ho : BNP / Wo;
+    int TI = 1;
+    if (TR == Ho) {
+        if (BNP % (Ho * Wo)) return false;
+        TI = BNP / (Ho * Wo);
+    } else if (Ho % TR) {
+        return false;
+    }
+    if (TR * Wo >= 32 ? (TR * Wo) % 64 : 32 % (TR * Wo)) return false;
+    const int NH = TI * (TR + 1) * Wo;
+    if (NH > 8 * WCO * WPIX * NHI) return false;
+    a.TI = TI;
+    a.TR = TR;
+    a.NH = NH;
+    a.pix_tiles = (a.M + BNP - 1) / BNP;
+    a.co_tiles = a.Cout / (kWaveTile * WCO);
+    return (int64_t)a.pix_tiles * a.co_tiles <= INT32_MAX;
+}
+
+// The LDS-DMA pipeline (k_conv3x3_pipe, or k_conv3x3_pipe16 with DLS_CONV_MF16)
+// when the halo tile fits NHI DMAs per wave
+template <int WCO, int WPIX, int NHI>
+bool fit_pipe(ConvArgs &a) {
+    constexpr int BNP = kWaveTile * WPIX;
+    const int H = a.H, W = a.W;
+    if (32 % W) return false;  // a wave's two 32-pixel tiles share their columns
+    if ((int64_t)a.B * H * W >= (1ll << 28)) return false;  // halo sources: input pixel * 8 + piece in 32 bits
+    const int TR = H < BNP / W ? H : BNP / W;
+    int TI = 1;
+    if (TR == H) {
+        if (BNP % (H * W)) return false;
+        TI = BNP / (H * W);
+    } else if (H % TR) {
+        return false;
+    }
+    // pixel tile 1 = tile 0 + 32 pixels in the same image tile, or whole images on
+    if (TR * W >= 32 ? (TR * W) % 64 : 32 % (TR * W)) return false;
+    const int NH = TI * (TR + 2) * W;  // halo rows without the padding columns
+    if (NH > 8 * WCO * WPIX * NHI || a.Cout % (kWaveTile * WCO)) return false;
+    a.TI = TI;
+    a.TR = TR;
+    a.NH = NH;
+    a.pix_tiles = (a.M + BNP - 1) / BNP;
+    a.co_tiles = a.Cout / (kWaveTile * WCO);
+    return (int64_t)a.pix_tiles * a.co_tiles <= INT32_MAX;
+}
+
+// The shape checks of dls_conv_bn_act_split and its query: the output pixels in
+// M, or a negative status with the error text set.
+int conv_check_shape(int64_t B, int32_t H, int32_t W, int32_t C, int32_t Cout, int32_t KH, int32_t KW,
+                     int32_t stride, int32_t pad, int64_t &M) {
+    DLS_REQUIRE(B >= 0 && H > 0 && W > 0 && C >= 32 && C % 32 == 0 && Cout >= 64 && Cout % 64 == 0 &&
+                    KH > 0 && KW > 0 && stride > 0 && pad >= 0 && H + 2 * pad >= KH &&
+                    W + 2 * pad >= KW && (int64_t)KH * KW * C <= (1 << 24),
+                DLS_EINVAL,
+                "dls_conv_bn_act_split: B=%lld H=%d W=%d C=%d Cout=%d KH=%d KW=%d stride=%d pad=%d "
+                "(C a multiple of 32, Cout of 64)",
+                (long long)B, H, W, C, Cout, KH, KW, stride, pad);
+    const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
+    M = B * Ho * Wo;
+    // pixel indices are 32-bit inside the kernel; element offsets 64-bit
+    DLS_REQUIRE(M <= INT32_MAX / 2 && B * H * W <= INT32_MAX / 2, DLS_EINVAL,
+                "dls_conv_bn_act_split: %lld output pixels", (long long)M);
+    return DLS_OK;
+}
+
+// The kernel (DLS_CONV_KERNEL_*, include/dls_hip.h) of a checked shape with
+// M > 0, its tile fields filled in; DLS_EINVAL if no grid holds its blocks.
+// The choice is a function of the shape alone (never of the process's
+// environment): a coalition's utility must be the same bits on every rank.
+// DLS_CONV_GENERIC_ONLY=1 (compile-time probe knob, tools/build_variants.py):
+// the generic kernel for every shape.
+int conv_choose(ConvArgs &a, int KH) {
+    const int W = a.W, KW = a.KW;
+    const bool wide = a.Cout % 128 == 0;
+    if (!DLS_CONV_GENERIC_ONLY && KH == 3 && KW == 3 && a.stride == 1 && a.pad == 1) {
+        // the LDS-DMA pipelines (profiles/r06_conv_pipe_ab.txt): 128-channel
+        // multiples 16 wide in 64-channel 4-wave blocks of one whole 16x16 image
+        // (no halo rows re-read, half the weight bytes per MFMA), else in
+        // 128-channel 4-wave one-halo-buffer blocks two per CU on images at least
+        // 16 wide, else in 8-wave double-buffered ones (8x8, 4x4); 64 channels in
+        // 4-wave one-halo-buffer blocks (32x32)
+        const bool narrow = (W == 16 && (DLS_PIPE_NARROW & 1)) || (W == 8 && (DLS_PIPE_NARROW & 2)) ||
+                            (W == 4 && (DLS_PIPE_NARROW & 4));
+        if (DLS_CONV_PIPE && narrow) {
+            if (fit_pipe<1, 4, 10>(a)) return DLS_CONV_KERNEL_PIPE64_H10;
+            if (fit_pipe<1, 4, 12>(a)) return DLS_CONV_KERNEL_PIPE64_H12;
+        }
+        if (DLS_CONV_PIPE && wide) {
+            if (W >= 16 && fit_pipe<2, 2, 5>(a)) return DLS_CONV_KERNEL_PIPE128_W4;
+            if (fit_pipe<2, 4, 5>(a)) return DLS_CONV_KERNEL_PIPE128_W8_H5;
+            if (fit_pipe<2, 4, 6>(a)) return DLS_CONV_KERNEL_PIPE128_W8_H6;
+        }
+        if (DLS_CONV_PIPE && !wide && fit_pipe<1, 4, 10>(a)) return DLS_CONV_KERNEL_PIPE64_H10;
+        const bool skew = W <= 16;
+        if (wide ? fit_halo<2, 2, 9>(a) : fit_halo<1, 4, 11>(a))
+            return wide ? (skew ? DLS_CONV_KERNEL_HALO128_SKEW : DLS_CONV_KERNEL_HALO128)
+                        : (skew ? DLS_CONV_KERNEL_HALO64_SKEW : DLS_CONV_KERNEL_HALO64);
+    }
+    if (DLS_CONV_PHASE && !DLS_CONV_GENERIC_ONLY && KH == 3 && KW == 3 && a.stride == 2 && a.pad == 1 && wide &&
+        fit_phase<2, 4, 5>(a))
+        return DLS_CONV_KERNEL_PHASE;
+    a.TI = a.TR = a.NH = 0;
+    if (!(wide ? fit_generic<2, 2>(a) : fit_generic<1, 4>(a))) {
+        set_error("dls_conv_bn_act_split: %lld blocks", (long long)a.pix_tiles * a.co_tiles);
+        return DLS_EINVAL;
+    }
+    return wide ? DLS_CONV_KERNEL_GENERIC128 : DLS_CONV_KERNEL_GENERIC64;
+}
+
+inline unsigned conv_blocks(const ConvArgs &a) { return (unsigned)((int64_t)a.pix_tiles * a.co_tiles); }
+
 // The generic kernel's LDS form: 64-channel tiles (WCO = 1: 64 x 256 blocks)
 // stage through one buffer (two barriers per chunk) and transpose their epilogue
 // in two 32-channel passes, 46 instead of 92 KB per block (3 blocks per CU
@@ -1496,117 +1658,59 @@ __global__ __launch_bounds__(kPoolBlock) void k_pool_linear(const uint16_t *__re
 // 37 KB and 4 blocks per CU, made the stride-2 3x3 convolutions 2-3.5 % slower
 // (profiles/r05_conv_probe.txt r05g)
 template <int WCO, int WPIX>
-int launch_conv(ConvArgs a, hipStream_t st) {
+void launch_conv(const ConvArgs &a, hipStream_t st) {
     constexpr int NBUF = WCO == 1 ? 1 : 2, NPASS = WCO == 1 ? 2 : 1;
-    a.pix_tiles = (a.M + kWaveTile * WPIX - 1) / (kWaveTile * WPIX);
-    a.co_tiles = a.Cout / (kWaveTile * WCO);
-    const int64_t blocks = (int64_t)a.pix_tiles * a.co_tiles;
-    if (blocks > INT32_MAX) {
-        set_error("dls_conv_bn_act_split: %lld blocks", (long long)blocks);
-        return DLS_EINVAL;
-    }
-    hipLaunchKernelGGL((k_conv_bf16x3<WCO, WPIX, NBUF, NPASS>), dim3((unsigned)blocks), dim3(64 * WCO * WPIX), 0,
+    hipLaunchKernelGGL((k_conv_bf16x3<WCO, WPIX, NBUF, NPASS>), dim3(conv_blocks(a)), dim3(64 * WCO * WPIX), 0,
                        st, a);
-    return check_launch("dls_conv_bn_act_split");
 }
 
-// The halo kernel when the pixel tile can be whole output rows: returns 1 if
-// launched (or the launch failed: rc set), 0 if the shape does not fit it.
 template <int WCO, int WPIX, int NHMAX, bool SKEW>
-int try_launch_halo(ConvArgs a, hipStream_t st, int &rc) {
-    constexpr int BNP = kWaveTile * WPIX;
-    constexpr int RPP = 64 * WCO * WPIX / (kBK / 4);
-    const int H = a.H, W = a.W;
-    if (W > BNP || BNP % W) return 0;
-    const int TR = H < BNP / W ? H : BNP / W;
-    int TI = 1;
-    if (TR == H) {
-        if (BNP % (H * W)) return 0;
-        TI = BNP / (H * W);
-    } else if (H % TR) {
-        return 0;
-    }
-    const int NH = TI * (TR + 2) * (W + 2);
-    if (NH > RPP * NHMAX) return 0;
-    a.TI = TI;
-    a.TR = TR;
-    a.NH = NH;
-    a.pix_tiles = (a.M + BNP - 1) / BNP;
-    a.co_tiles = a.Cout / (kWaveTile * WCO);
-    const int64_t blocks = (int64_t)a.pix_tiles * a.co_tiles;
-    if (blocks > INT32_MAX) return 0;
-    hipLaunchKernelGGL((k_conv3x3_halo<WCO, WPIX, NHMAX, SKEW>), dim3((unsigned)blocks), dim3(64 * WCO * WPIX), 0,
+void launch_halo(const ConvArgs &a, hipStream_t st) {
+    hipLaunchKernelGGL((k_conv3x3_halo<WCO, WPIX, NHMAX, SKEW>), dim3(conv_blocks(a)), dim3(64 * WCO * WPIX), 0,
                        st, a);
-    rc = check_launch("dls_conv_bn_act_split");
-    return 1;
 }
 
-// The stride-2 phase pipeline (k_conv3x3s2_phase) when its phase halos fit NHI
-// DMAs per wave
 template <int WCO, int WPIX, int NHI>
-int try_launch_phase(ConvArgs a, hipStream_t st, int &rc) {
-    constexpr int BNP = kWaveTile * WPIX;
-    const int H = a.H, W = a.W, Ho = a.Ho, Wo = a.Wo;
-    if ((H | W) & 1 || 2 * Ho != H || 2 * Wo != W || 32 % Wo || a.Cout % (kWaveTile * WCO)) return 0;
-    if ((int64_t)a.B * H * W >= (1ll << 30)) return 0;  // input pixel indices in 32 bits
-    const int TR = Ho < BNP / Wo ? Ho : BNP / Wo;
-    int TI = 1;
-    if (TR == Ho) {
-        if (BNP % (Ho * Wo)) return 0;
-        TI = BNP / (Ho * Wo);
-    } else if (Ho % TR) {
-        return 0;
-    }
-    if (TR * Wo >= 32 ? (TR * Wo) % 64 : 32 % (TR * Wo)) return 0;
-    const int NH = TI * (TR + 1) * Wo;
-    if (NH > 8 * WCO * WPIX * NHI) return 0;
-    a.TI = TI;
-    a.TR = TR;
-    a.NH = NH;
-    a.pix_tiles = (a.M + BNP - 1) / BNP;
-    a.co_tiles = a.Cout / (kWaveTile * WCO);
-    const int64_t blocks = (int64_t)a.pix_tiles * a.co_tiles;
-    if (blocks > INT32_MAX) return 0;
-    hipLaunchKernelGGL((k_conv3x3s2_phase<WCO, WPIX, NHI>), dim3((unsigned)blocks), dim3(64 * WCO * WPIX), 0, st, a);
-    rc = check_launch("dls_conv_bn_act_split");
-    return 1;
+void launch_phase(const ConvArgs &a, hipStream_t st) {
+    hipLaunchKernelGGL((k_conv3x3s2_phase<WCO, WPIX, NHI>), dim3(conv_blocks(a)), dim3(64 * WCO * WPIX), 0, st, a);
 }
 
-// The LDS-DMA pipeline (k_conv3x3_pipe, or k_conv3x3_pipe16 with DLS_CONV_MF16)
-// when the halo tile fits NHI DMAs per wave
 template <int WCO, int WPIX, int NHI, int NHB = 2, int OCC = 1>
-int try_launch_pipe(ConvArgs a, hipStream_t st, int &rc) {
-    constexpr int BNP = kWaveTile * WPIX;
-    const int H = a.H, W = a.W;
-    if (32 % W) return 0;  // a wave's two 32-pixel tiles share their columns
-    if ((int64_t)a.B * H * W >= (1ll << 28)) return 0;  // halo sources: input pixel * 8 + piece in 32 bits
-    const int TR = H < BNP / W ? H : BNP / W;
-    int TI = 1;
-    if (TR == H) {
-        if (BNP % (H * W)) return 0;
-        TI = BNP / (H * W);
-    } else if (H % TR) {
-        return 0;
-    }
-    // pixel tile 1 = tile 0 + 32 pixels in the same image tile, or whole images on
-    if (TR * W >= 32 ? (TR * W) % 64 : 32 % (TR * W)) return 0;
-    const int NH = TI * (TR + 2) * W;  // halo rows without the padding columns
-    if (NH > 8 * WCO * WPIX * NHI || a.Cout % (kWaveTile * WCO)) return 0;
-    a.TI = TI;
-    a.TR = TR;
-    a.NH = NH;
-    a.pix_tiles = (a.M + BNP - 1) / BNP;
-    a.co_tiles = a.Cout / (kWaveTile * WCO);
-    const int64_t blocks = (int64_t)a.pix_tiles * a.co_tiles;
-    if (blocks > INT32_MAX) return 0;
+void launch_pipe(const ConvArgs &a, hipStream_t st) {
     if (DLS_CONV_MF16)
-        hipLaunchKernelGGL((k_conv3x3_pipe16<WCO, WPIX, NHI, NHB, OCC>), dim3((unsigned)blocks),
+        hipLaunchKernelGGL((k_conv3x3_pipe16<WCO, WPIX, NHI, NHB, OCC>), dim3(conv_blocks(a)),
                            dim3(64 * WCO * WPIX), 0, st, a);
     else
-        hipLaunchKernelGGL((k_conv3x3_pipe<WCO, WPIX, NHI, NHB, OCC>), dim3((unsigned)blocks),
+        hipLaunchKernelGGL((k_conv3x3_pipe<WCO, WPIX, NHI, NHB, OCC>), dim3(conv_blocks(a)),
                            dim3(64 * WCO * WPIX), 0, st, a);
-    rc = check_launch("dls_conv_bn_act_split");
-    return 1;
+}
+
+// The stem's kernel (DLS_STEM_KERNEL_*) of a checked shape
+int stem_choose(int C, int H, int W, int KH, int KW, int stride, int pad) {
+    if (DLS_STEM_WINDOW && C == 3 && KH == 3 && KW == 3 && stride == 1 && pad == 1 && W == 32 && H % 8 == 0)
+        return DLS_STEM_KERNEL_WINDOW;
+    return C == 3 && KH == 3 && KW == 3 ? DLS_STEM_KERNEL_3X3 : DLS_STEM_KERNEL_GENERIC;
+}
+
+int stem_check_shape(int64_t B, int32_t C, int32_t H, int32_t W, int32_t Cout, int32_t KH, int32_t KW,
+                     int32_t stride, int32_t pad, int64_t &M, int &pix_tiles, int &co_tiles) {
+    DLS_REQUIRE(B >= 0 && C > 0 && H > 0 && W > 0 && KH > 0 && KW > 0 && KH * KW * C <= kBK &&
+                    Cout >= 64 && Cout % 64 == 0 && stride > 0 && pad >= 0 && H + 2 * pad >= KH &&
+                    W + 2 * pad >= KW,
+                DLS_EINVAL,
+                "dls_conv_stem_bn_act_f32: B=%lld C=%d H=%d W=%d Cout=%d KH=%d KW=%d (KH*KW*C <= %d, "
+                "Cout a multiple of 64)",
+                (long long)B, C, H, W, Cout, KH, KW, kBK);
+    const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
+    M = B * Ho * Wo;
+    if (M == 0) return DLS_OK;
+    DLS_REQUIRE(M <= INT32_MAX / 2, DLS_EINVAL, "dls_conv_stem_bn_act_f32: %lld output pixels",
+                (long long)M);
+    pix_tiles = (int)((M + kWaveTile * 4 - 1) / (kWaveTile * 4));
+    co_tiles = Cout / kWaveTile;
+    const int64_t blocks = (int64_t)pix_tiles * co_tiles;
+    DLS_REQUIRE(blocks <= INT32_MAX, DLS_EINVAL, "dls_conv_stem_bn_act_f32: %lld blocks", (long long)blocks);
+    return DLS_OK;
 }
 
 // The walk direction of a launch: the opposite of the one its input was
@@ -1711,104 +1815,95 @@ int dls_conv_bn_act_split(const uint16_t *x, int64_t B, int32_t H, int32_t W, in
                           int32_t pad, const float *consts, const uint16_t *residual, int32_t relu,
                           uint16_t *y, dls_stream_t stream) {
     DLS_REQUIRE(x && w && y, DLS_EINVAL, "dls_conv_bn_act_split: null pointer");
-    DLS_REQUIRE(B >= 0 && H > 0 && W > 0 && C >= 32 && C % 32 == 0 && Cout >= 64 && Cout % 64 == 0 &&
-                    KH > 0 && KW > 0 && stride > 0 && pad >= 0 && H + 2 * pad >= KH &&
-                    W + 2 * pad >= KW && (int64_t)KH * KW * C <= (1 << 24),
-                DLS_EINVAL,
-                "dls_conv_bn_act_split: B=%lld H=%d W=%d C=%d Cout=%d KH=%d KW=%d stride=%d pad=%d "
-                "(C a multiple of 32, Cout of 64)",
-                (long long)B, H, W, C, Cout, KH, KW, stride, pad);
+    int64_t M = 0;
+    if (const int rc = conv_check_shape(B, H, W, C, Cout, KH, KW, stride, pad, M)) return rc;
     DLS_REQUIRE(aligned16(x) && aligned16(w) && aligned16(y) && (!consts || aligned16(consts)) &&
                     (!residual || aligned16(residual)),
                 DLS_ELAYOUT, "dls_conv_bn_act_split: 16-byte alignment");
-    const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
-    const int64_t M = B * Ho * Wo;
     if (M == 0) return DLS_OK;
-    // pixel indices are 32-bit inside the kernel; element offsets 64-bit
-    DLS_REQUIRE(M <= INT32_MAX / 2 && B * H * W <= INT32_MAX / 2, DLS_EINVAL,
-                "dls_conv_bn_act_split: %lld output pixels", (long long)M);
+    const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
     ConvArgs a{x, w, consts, residual, y, (int)H, (int)W, (int)C, Ho, Wo, (int)Cout, (int)KW,
                (int)(KH * KW), (int)stride, (int)pad, (int)(KH * KW * C), (int)M, relu ? 1 : 0, 0, 0,
                (int)B, 0, 0, 0};
+    const int id = conv_choose(a, KH);
+    if (id < 0) return id;
     a.rev = conv_walk_direction(x);
     conv_record_walk(y, a.rev);
     hipStream_t st = as_stream(stream);
-    const bool wide = Cout % 128 == 0;
-    // The kernel choice is a function of the shape alone (never of the process's
-    // environment): a coalition's utility must be the same bits on every rank.
-    // DLS_CONV_GENERIC_ONLY=1 (compile-time probe knob, tools/build_variants.py):
-    // the generic kernel for every shape.
-    if (!DLS_CONV_GENERIC_ONLY && KH == 3 && KW == 3 && stride == 1 && pad == 1) {
-        int rc = DLS_OK;
-        // the LDS-DMA pipelines (profiles/r06_conv_pipe_ab.txt): 128-channel
-        // multiples 16 wide in 64-channel 4-wave blocks of one whole 16x16 image
-        // (no halo rows re-read, half the weight bytes per MFMA), else in
-        // 128-channel 4-wave one-halo-buffer blocks two per CU on images at least
-        // 16 wide, else in 8-wave double-buffered ones (8x8, 4x4); 64 channels in
-        // 4-wave one-halo-buffer blocks (32x32)
-        const bool narrow = (W == 16 && (DLS_PIPE_NARROW & 1)) || (W == 8 && (DLS_PIPE_NARROW & 2)) ||
-                            (W == 4 && (DLS_PIPE_NARROW & 4));
-        if (DLS_CONV_PIPE && narrow &&
-            (try_launch_pipe<1, 4, 10, 1, 2>(a, st, rc) || try_launch_pipe<1, 4, 12, 1, 2>(a, st, rc)))
-            return rc;
-        if (DLS_CONV_PIPE && wide &&
-            ((W >= 16 && try_launch_pipe<2, 2, 5, 1, 2>(a, st, rc)) || try_launch_pipe<2, 4, 5>(a, st, rc) ||
-             try_launch_pipe<2, 4, 6>(a, st, rc)))
-            return rc;
-        if (DLS_CONV_PIPE && !wide && try_launch_pipe<1, 4, 10, 1, 2>(a, st, rc)) return rc;
-        const bool skew = W <= 16;
-        const int hit = wide ? (skew ? try_launch_halo<2, 2, 9, true>(a, st, rc)
-                                     : try_launch_halo<2, 2, 9, false>(a, st, rc))
-                             : (skew ? try_launch_halo<1, 4, 11, true>(a, st, rc)
-                                     : try_launch_halo<1, 4, 11, false>(a, st, rc));
-        if (hit) return rc;
+    switch (id) {
+    case DLS_CONV_KERNEL_PIPE64_H10: launch_pipe<1, 4, 10, 1, 2>(a, st); break;
+    case DLS_CONV_KERNEL_PIPE64_H12: launch_pipe<1, 4, 12, 1, 2>(a, st); break;
+    case DLS_CONV_KERNEL_PIPE128_W4: launch_pipe<2, 2, 5, 1, 2>(a, st); break;
+    case DLS_CONV_KERNEL_PIPE128_W8_H5: launch_pipe<2, 4, 5>(a, st); break;
+    case DLS_CONV_KERNEL_PIPE128_W8_H6: launch_pipe<2, 4, 6>(a, st); break;
+    case DLS_CONV_KERNEL_HALO128: launch_halo<2, 2, 9, false>(a, st); break;
+    case DLS_CONV_KERNEL_HALO128_SKEW: launch_halo<2, 2, 9, true>(a, st); break;
+    case DLS_CONV_KERNEL_HALO64: launch_halo<1, 4, 11, false>(a, st); break;
+    case DLS_CONV_KERNEL_HALO64_SKEW: launch_halo<1, 4, 11, true>(a, st); break;
+    case DLS_CONV_KERNEL_PHASE: launch_phase<2, 4, 5>(a, st); break;
+    case DLS_CONV_KERNEL_GENERIC128: launch_conv<2, 2>(a, st); break;
+    default: launch_conv<1, 4>(a, st); break;
     }
-    if (DLS_CONV_PHASE && !DLS_CONV_GENERIC_ONLY && KH == 3 && KW == 3 && stride == 2 && pad == 1 && wide) {
-        int rc = DLS_OK;
-        if (try_launch_phase<2, 4, 5>(a, st, rc)) return rc;
-    }
-    return wide ? launch_conv<2, 2>(a, st) : launch_conv<1, 4>(a, st);
+    return check_launch("dls_conv_bn_act_split");
+}
+
+int dls_conv_kernel_choice(int64_t B, int32_t H, int32_t W, int32_t C, int32_t Cout, int32_t KH,
+                           int32_t KW, int32_t stride, int32_t pad) {
+    int64_t M = 0;
+    if (const int rc = conv_check_shape(B, H, W, C, Cout, KH, KW, stride, pad, M)) return rc;
+    if (M == 0) return DLS_CONV_KERNEL_NONE;
+    const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
+    ConvArgs a{nullptr, nullptr, nullptr, nullptr, nullptr, (int)H, (int)W, (int)C, Ho, Wo, (int)Cout,
+               (int)KW, (int)(KH * KW), (int)stride, (int)pad, (int)(KH * KW * C), (int)M, 0, 0, 0,
+               (int)B, 0, 0, 0};
+    return conv_choose(a, KH);
 }
 
 int dls_conv_stem_bn_act_f32(const float *x, int64_t B, int32_t C, int32_t H, int32_t W, const uint16_t *w,
                              int32_t Cout, int32_t KH, int32_t KW, int32_t stride, int32_t pad,
                              const float *consts, int32_t relu, uint16_t *y, dls_stream_t stream) {
     DLS_REQUIRE(x && w && y, DLS_EINVAL, "dls_conv_stem_bn_act_f32: null pointer");
-    DLS_REQUIRE(B >= 0 && C > 0 && H > 0 && W > 0 && KH > 0 && KW > 0 && KH * KW * C <= kBK &&
-                    Cout >= 64 && Cout % 64 == 0 && stride > 0 && pad >= 0 && H + 2 * pad >= KH &&
-                    W + 2 * pad >= KW,
-                DLS_EINVAL,
-                "dls_conv_stem_bn_act_f32: B=%lld C=%d H=%d W=%d Cout=%d KH=%d KW=%d (KH*KW*C <= %d, "
-                "Cout a multiple of 64)",
-                (long long)B, C, H, W, Cout, KH, KW, kBK);
+    int64_t M = 0;
+    int pix_tiles = 0, co_tiles = 0;
+    if (const int rc = stem_check_shape(B, C, H, W, Cout, KH, KW, stride, pad, M, pix_tiles, co_tiles)) return rc;
     DLS_REQUIRE(aligned16(w) && aligned16(y) && (!consts || aligned16(consts)), DLS_ELAYOUT,
                 "dls_conv_stem_bn_act_f32: 16-byte alignment");
-    const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
-    const int64_t M = B * Ho * Wo;
     if (M == 0) return DLS_OK;
-    DLS_REQUIRE(M <= INT32_MAX / 2, DLS_EINVAL, "dls_conv_stem_bn_act_f32: %lld output pixels",
-                (long long)M);
-    constexpr int WPIX = 4;
+    const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
+    constexpr int WPIX = 4;  // stem_check_shape's pixel tiles: 64 * WPIX pixels
     ConvArgs a{nullptr, w, consts, nullptr, y, (int)H, (int)W, (int)C, Ho, Wo, (int)Cout, (int)KW,
                (int)(KH * KW), (int)stride, (int)pad, kBK, (int)M, relu ? 1 : 0, 0, 0, (int)B, 0, 0, 0};
     conv_record_walk(y, 0);  // the stem walks forwards; the next layer backwards
-    a.pix_tiles = (int)((M + kWaveTile * WPIX - 1) / (kWaveTile * WPIX));
-    a.co_tiles = Cout / kWaveTile;
+    a.pix_tiles = pix_tiles;
+    a.co_tiles = co_tiles;
     const int64_t blocks = (int64_t)a.pix_tiles * a.co_tiles;
-    DLS_REQUIRE(blocks <= INT32_MAX, DLS_EINVAL, "dls_conv_stem_bn_act_f32: %lld blocks", (long long)blocks);
-    if (DLS_STEM_WINDOW && C == 3 && KH == 3 && KW == 3 && stride == 1 && pad == 1 && W == 32 && H % 8 == 0) {
+    switch (stem_choose(C, H, W, KH, KW, stride, pad)) {
+    case DLS_STEM_KERNEL_WINDOW: {
         // the CIFAR ResNet stem, window staged in LDS, DLS_STEM_TILES pixel tiles per block
         constexpr int NTL = DLS_STEM_TILES;
         const int64_t walks = (int64_t)((a.pix_tiles + NTL - 1) / NTL) * a.co_tiles;
         hipLaunchKernelGGL((k_conv_stem<WPIX, 3, 3, true, NTL>), dim3((unsigned)walks), dim3(64 * WPIX), 0,
                            as_stream(stream), a, x);
+        break;
     }
-    else if (C == 3 && KH == 3 && KW == 3)
+    case DLS_STEM_KERNEL_3X3:
         hipLaunchKernelGGL((k_conv_stem<WPIX, 3, 3>), dim3((unsigned)blocks), dim3(64 * WPIX), 0,
                            as_stream(stream), a, x);
-    else
+        break;
+    default:
         hipLaunchKernelGGL(k_conv_stem<WPIX>, dim3((unsigned)blocks), dim3(64 * WPIX), 0, as_stream(stream), a, x);
+        break;
+    }
     return check_launch("dls_conv_stem_bn_act_f32");
+}
+
+int dls_conv_stem_kernel_choice(int64_t B, int32_t C, int32_t H, int32_t W, int32_t Cout, int32_t KH,
+                                int32_t KW, int32_t stride, int32_t pad) {
+    int64_t M = 0;
+    int pix_tiles = 0, co_tiles = 0;
+    if (const int rc = stem_check_shape(B, C, H, W, Cout, KH, KW, stride, pad, M, pix_tiles, co_tiles)) return rc;
+    if (M == 0) return DLS_STEM_KERNEL_NONE;
+    return stem_choose(C, H, W, KH, KW, stride, pad);
 }
 
 int dls_pool_linear_split(const uint16_t *x, int64_t B, int32_t HW, int32_t C, const float *weight,

@@ -303,7 +303,39 @@ int dls_bn_act_exact_nchw_f32(const float *x, int64_t N, int32_t C, int64_t HW,
  * (the im2col fused), w from dls_conv_pack_weights_im2col_f32 (Kp = 32).
  * dls_pool_linear_split: logits[b][o] = sum_c mean_pixels(x[b])[c] * weight[o][c]
  * + bias[o] over a split NHWC [B][HW][2C] activation (C <= 2048; bias may be
- * null), every sum in a fixed order. */
+ * null), every sum in a fixed order.
+ * The split of a value x: hi = rne_bf16(x), lo = rne_bf16(x - hi), and lo = 0
+ * whenever hi is not finite — an inf or NaN x, and a finite x that rounds to
+ * bf16 infinity (|x| >= 0x7f7f8000, as a plain bf16 conversion rounds it) — so
+ * hi + lo is never inf - inf.
+ * dls_conv_kernel_choice / dls_conv_stem_kernel_choice: host-only queries (no
+ * device call, no stream): the kernel instantiation dls_conv_bn_act_split /
+ * dls_conv_stem_bn_act_f32 launches for a shape (a DLS_CONV_KERNEL_* /
+ * DLS_STEM_KERNEL_* id below; *_NONE for an empty batch, which launches
+ * nothing), or the negative status the launch would return for that shape.
+ * The launch and the query run the same decision code; the choice depends on
+ * the shape alone. */
+#define DLS_CONV_KERNEL_NONE 0          /* B = 0: no launch */
+#define DLS_CONV_KERNEL_GENERIC64 1     /* k_conv_bf16x3<1,4>: 64 channels x 256 pixels */
+#define DLS_CONV_KERNEL_GENERIC128 2    /* k_conv_bf16x3<2,2>: 128 x 128 */
+#define DLS_CONV_KERNEL_PIPE64_H10 3    /* k_conv3x3_pipe16<1,4,10,1,2> */
+#define DLS_CONV_KERNEL_PIPE64_H12 4    /* k_conv3x3_pipe16<1,4,12,1,2> */
+#define DLS_CONV_KERNEL_PIPE128_W4 5    /* k_conv3x3_pipe16<2,2,5,1,2> */
+#define DLS_CONV_KERNEL_PIPE128_W8_H5 6 /* k_conv3x3_pipe16<2,4,5> */
+#define DLS_CONV_KERNEL_PIPE128_W8_H6 7 /* k_conv3x3_pipe16<2,4,6> */
+#define DLS_CONV_KERNEL_HALO128 8       /* k_conv3x3_halo<2,2,9,false> */
+#define DLS_CONV_KERNEL_HALO128_SKEW 9  /* k_conv3x3_halo<2,2,9,true> */
+#define DLS_CONV_KERNEL_HALO64 10       /* k_conv3x3_halo<1,4,11,false> */
+#define DLS_CONV_KERNEL_HALO64_SKEW 11  /* k_conv3x3_halo<1,4,11,true> */
+#define DLS_CONV_KERNEL_PHASE 12        /* k_conv3x3s2_phase<2,4,5> */
+#define DLS_STEM_KERNEL_NONE 0          /* B = 0: no launch */
+#define DLS_STEM_KERNEL_WINDOW 1        /* k_conv_stem<4,3,3,true,2>: 3-channel 3x3, W = 32, H % 8 = 0 */
+#define DLS_STEM_KERNEL_3X3 2           /* k_conv_stem<4,3,3> */
+#define DLS_STEM_KERNEL_GENERIC 3       /* k_conv_stem<4> */
+int dls_conv_kernel_choice(int64_t B, int32_t H, int32_t W, int32_t C, int32_t Cout, int32_t KH,
+                           int32_t KW, int32_t stride, int32_t pad);
+int dls_conv_stem_kernel_choice(int64_t B, int32_t C, int32_t H, int32_t W, int32_t Cout, int32_t KH,
+                                int32_t KW, int32_t stride, int32_t pad);
 int dls_conv_pack_input_f32(const float *x, int64_t B, int32_t C, int32_t H, int32_t W, int32_t Cp,
                             uint16_t *out, dls_stream_t stream);
 int dls_conv_pack_weights_f32(const float *w, int32_t Cout, int32_t Cin, int32_t KH, int32_t KW,

@@ -22,13 +22,17 @@ pytestmark = pytest.mark.gpu
 dev = torch.device("cuda", 0)
 TOL = 5e-5
 
-# (cin, cout, k, stride, H, W, residual, batch): every ResNet-18 shape (the LDS-DMA
-# pipeline for 3x3 stride 1, the generic kernel otherwise), ragged last tiles
-# (batch not a multiple of the images per tile), sizes the pipeline does not take
-# (28x28 -> the register-staged halo kernel; 7x7, 12x12 -> generic), Cout a
-# multiple of 64 but not of 128, a non-square image, and the stem (cin < 32:
-# im2col + the generic kernel, and the fused-im2col stem kernel, which must give
-# the same bits)
+# (cin, cout, k, stride, H, W, residual, batch), each group's kernel as
+# _native.conv_kernel_choice names it.  Every ResNet-18 shape: 3x3 stride 1 on the
+# LDS-DMA pipeline (32x32, 16x16 -> pipe<1,4,10,1,2>; 8x8 -> pipe<2,4,5>; 4x4 ->
+# pipe<2,4,6>), 3x3 stride 2 on phase<2,4,5>, the 1x1 shortcuts on generic<2,2>;
+# ragged last tiles (batch not a multiple of the images per tile); sizes no row
+# tiling takes (28x28, 12x12 with 192 channels -> generic<1,4>; 7x7 ->
+# generic<2,2>); Cout a multiple of 64 but not of 128; a non-square image (8x16
+# -> pipe<1,4,10,1,2>); and the stem (cin < 32: im2col + generic<1,4>, and the
+# fused-im2col stem kernel — window at 32x32, 3x3 at 28x28 — which must give the
+# same bits).  No shape here or in the fuzz sweep below runs the register-staged
+# halo kernel: tests/test_gpu_conv_exact.py does (64x64, 12x32, 2x32, 2x16, 4x8).
 SHAPES = [
     (3, 64, 3, 1, 32, 32, False, 4), (64, 64, 3, 1, 32, 32, False, 3), (64, 64, 3, 1, 32, 32, True, 2),
     (64, 128, 3, 2, 32, 32, False, 3), (64, 128, 1, 2, 32, 32, False, 3),
@@ -36,14 +40,16 @@ SHAPES = [
     (256, 256, 3, 1, 8, 8, True, 3), (256, 512, 3, 2, 8, 8, False, 2), (256, 512, 1, 2, 8, 8, False, 2),
     (512, 512, 3, 1, 4, 4, True, 5), (64, 64, 3, 1, 28, 28, True, 2), (128, 128, 3, 1, 7, 7, False, 3),
     (96, 192, 3, 1, 12, 12, True, 2), (64, 128, 3, 1, 8, 16, False, 3), (3, 64, 3, 1, 28, 28, False, 2),
-    # stems off the 3x3 / 3-channel fast path: a 5x5 MNIST-like one (runtime
-    # index arithmetic) and a strided one over two 64-channel output tiles
+    # stems off the 3x3 / 3-channel fast path: a 5x5 MNIST-like one (the generic
+    # stem form: runtime index arithmetic) and a strided one (the 3x3 form) over
+    # two 64-channel output tiles
     (1, 64, 5, 1, 28, 28, False, 2), (3, 128, 3, 2, 32, 32, False, 2),
     # the LDS-DMA pipeline's other cases: one channel chunk (32 channels, no
     # halo reload), 64-channel blocks over 16x16 / 8x8 images (whole images,
-    # partial last tile), 128 channels over 32x32 (4 row tiles per image), a
-    # 24-row image (row tiles at y0 > 0, 4-wave blocks), 4x4 images with two
-    # chunks and a mostly empty tile (48 of 256 pixels)
+    # partial last tile: pipe<1,4,10,1,2>), 128 channels over 32x32 (4 row tiles
+    # per image: pipe<2,4,5>), a 24-row image (row tiles at y0 > 0, 4-wave
+    # blocks: pipe<2,2,5,1,2>), 4x4 images with two chunks and a mostly empty
+    # tile (48 of 256 pixels: pipe<2,4,6>)
     (32, 64, 3, 1, 32, 32, True, 2), (64, 64, 3, 1, 16, 16, False, 3), (64, 64, 3, 1, 8, 8, True, 3),
     (128, 128, 3, 1, 32, 32, False, 2), (32, 128, 3, 1, 24, 16, True, 2), (64, 256, 3, 1, 4, 4, False, 3),
     # the stride-2 phase pipeline: a non-square image with a residual (two images
