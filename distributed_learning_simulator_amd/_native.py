@@ -20,6 +20,7 @@ FEDAVG_FMA = 1
 SIGN_NAN_MARK = 1 << 24
 QTILE_GROUPS = 10  # DLS_QTILE_GROUPS
 SUBSET_UNION_MAX = 64  # DLS_SUBSET_UNION_MAX: coalitions per dls_subset_fedavg_union_f32 call
+ROBUST_MAX_K = 64  # DLS_ROBUST_MAX_K: client rows per dls_trimmed_mean_f32 call
 
 
 def sign_words(P):
@@ -63,6 +64,7 @@ SIGNATURES = {
     "dls_subset_fedavg_f32": ([_p, _i64, _p, _p, _p, _p, _i32, _i64, _p, _i64, _p], _i32),
     "dls_subset_fedavg_union_f32": ([_p, _i64, _p, _p, _p, _i32, _p, _i32, _i64, _p, _i64, _p],
                                     _i32),
+    "dls_trimmed_mean_f32": ([_p, _i64, _p, _i32, _i32, _i64, _p, _p], _i32),
     "dls_subset_gemm_f32": ([_p, _i32, _i32, _p, _i64, _p, _i64, _p, _i64, _p], _i32),
     "dls_sign_pack_f32": ([_p, _i64, _i32, _i64, _p, _i64, _p, _p], _i32),
     "dls_sign_vote_count": ([_p, _i64, _p, _i32, _i64, _p, _p], _i32),
@@ -150,7 +152,7 @@ def _stream(stream=None, like=None):
 
 
 CSRC_HASHED = ["dls_runtime.hip", "fedavg.hip", "sign.hip", "quant.hip", "quant_fma.hip", "shapley.hip",
-               "infer.hip", "conv.hip", "lenet.hip", "loss.hip", "dls_common.h", "quant_common.h",
+               "infer.hip", "conv.hip", "lenet.hip", "loss.hip", "robust.hip", "dls_common.h", "quant_common.h",
                "loss_common.h", os.path.join("..", "..", "include", "dls_hip.h")]
 
 
@@ -185,6 +187,46 @@ def fedavg(U, rows, weight, total, P, out, mode=FEDAVG_EXACT, stream=None):
     _check(lib().dls_fedavg_f32(_ptr(U), U.stride(0), _ptr(rows), _ptr(weight), rows.numel(),
                                 float(total), P, mode, _ptr(out), _stream(stream, U)),
            "dls_fedavg_f32")
+    return out
+
+
+def trimmed_mean(U, rows, trim, P, out, stream=None):
+    """Coordinate-wise trimmed mean of the K = rows.numel() selected rows of U into
+    out[:P] (dls_trimmed_mean_f32): per coordinate the ``trim`` lowest and highest
+    values are dropped and the rest averaged in ascending order; trim = (K-1)//2 is
+    the median.  The client weights play no part.  U: fp32 [*, ld] rows with unit
+    element stride; rows: int32 [K], 1 <= K <= ROBUST_MAX_K; 0 <= 2*trim < K; P a
+    multiple of 4, at most the row length."""
+    fn = "trimmed_mean"
+    if (not torch.is_tensor(U) or U.dtype != torch.float32 or U.dim() != 2
+            or (U.shape[1] > 1 and U.stride(1) != 1)):
+        raise RuntimeError(f"{fn}: U must be an fp32 [rows, ld] matrix with unit element stride")
+    if not torch.is_tensor(rows) or rows.dtype != torch.int32 or rows.dim() != 1 \
+            or not rows.is_contiguous():
+        raise RuntimeError(f"{fn}: rows must be a contiguous int32 [K] tensor")
+    K = rows.numel()
+    if not 1 <= K <= ROBUST_MAX_K:
+        raise RuntimeError(f"{fn}: K={K} rows (1..ROBUST_MAX_K={ROBUST_MAX_K})")
+    trim, P = int(trim), int(P)
+    if trim < 0 or 2 * trim >= K:
+        raise RuntimeError(f"{fn}: trim={trim} (0 <= 2*trim < K={K})")
+    if P < 0 or P % 4 != 0 or P > U.shape[1]:
+        raise RuntimeError(f"{fn}: P={P} must be a multiple of 4 and at most the row "
+                           f"length {U.shape[1]}")
+    ldu = U.stride(0) if U.shape[0] > 1 else U.shape[1]
+    if ldu % 4 != 0 or ldu < P:
+        raise RuntimeError(f"{fn}: row pitch {ldu} must be a multiple of 4, at least P")
+    if (not torch.is_tensor(out) or out.dtype != torch.float32 or out.dim() != 1
+            or out.numel() < P or (out.numel() > 1 and out.stride(0) != 1)):
+        raise RuntimeError(f"{fn}: out must be an fp32 vector of at least P={P} elements "
+                           "with unit stride")
+    _check_same_device(fn, U, rows=rows, out=out)
+    if U.data_ptr() % 16 != 0 or out.data_ptr() % 16 != 0:
+        raise RuntimeError(f"{fn}: U and out must be 16-byte aligned")
+    if P == 0:
+        return out
+    _check(lib().dls_trimmed_mean_f32(_ptr(U), ldu, _ptr(rows), K, trim, P, _ptr(out),
+                                      _stream(stream, U)), "dls_trimmed_mean_f32")
     return out
 
 

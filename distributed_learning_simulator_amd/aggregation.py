@@ -146,6 +146,25 @@ class ClientUpdateStore:
         _native.fedavg(self.U[:, c0:], r, w, float(total), c1 - c0, out, mode=mode)
         return out
 
+    def trimmed_mean(self, rows, trim, out=None, cols=None):
+        """Coordinate-wise trimmed mean of the given rows (dls_trimmed_mean_f32): per
+        flat element the ``trim`` lowest and highest of the K values are dropped and
+        the rest averaged in ascending order.  The clients' sample counts play no
+        part, and the result is the same bits for any order of ``rows``.  K <=
+        _native.ROBUST_MAX_K, 0 <= 2*trim < K; ``cols`` as in ``fedavg``."""
+        c0, c1 = cols if cols is not None else (0, self.layout.P)
+        if out is None:
+            out = torch.empty(c1 - c0, dtype=torch.float32, device=self.device)
+        r = rows if torch.is_tensor(rows) else _i32(rows, self.device)
+        _native.trimmed_mean(self.U[:, c0:], r, trim, c1 - c0, out)
+        return out
+
+    def median(self, rows, out=None, cols=None):
+        """Coordinate-wise median of the given rows: ``trimmed_mean`` with
+        trim = (K-1)//2 (an even K averages the two middle values)."""
+        K = rows.numel() if torch.is_tensor(rows) else len(rows)
+        return self.trimmed_mean(rows, (K - 1) // 2, out=out, cols=cols)
+
     def subset_models(self, subsets, n_of_row, method="exact", out=None):
         """S subset models at once.  subsets: list of row lists (non-empty, in order)."""
         S = len(subsets)

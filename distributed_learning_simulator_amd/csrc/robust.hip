@@ -1,0 +1,236 @@
+// Coordinate-wise trimmed mean / median over K client rows for gfx950: the robust
+// counterpart of the FedAvg hook (servers/fed_server.py:44-66).
+//
+// Per flat coordinate, independently (include/dls_hip.h has the contract):
+//   sort the K values ascending (-0 below +0, every NaN above +inf), drop the
+//   `trim` lowest and highest, acc = v[trim]; acc = fl(acc + v[i]) ascending;
+//   out = fl(acc / fl32(m)), m = K - 2 trim; any NaN result is 0x7fc00000.
+// The result is a function of the column's multiset: the same bits for any
+// order of `rows`.
+//
+// One pass over the rows, FedAvg's traffic (K*P*4 read, P*4 written): a lane owns
+// 4 consecutive coordinates (one 16-byte load per row), the row indices reach the
+// wave through a per-lane table and v_readlane, and a lane's K x 4 values are
+// sorted in registers as order-preserving uint32 keys by a fully unrolled Batcher
+// odd-even merge network (v_min_u32 / v_max_u32 per comparator and coordinate),
+// instantiated for KP = 1, 2, 4, ..., 64 wires; wires K..KP-1 hold the top key.
+// Every register index is a compile-time constant (no scratch, no LDS), and one
+// lane produces each output (no atomics, no split reduction).
+#include <utility>
+
+#include "dls_common.h"
+
+namespace dls {
+namespace {
+
+constexpr int kRobustBlock = 256;
+constexpr uint32_t kTopKey = 0xffffffffu;  // the canonical NaN's key; pads wires >= K
+
+// ------------------------------------------------- the comparator network
+// Batcher's odd-even merge sort of N = 2^t wires as a compile-time list of
+// (a < b) comparators: 1, 3, 9, 25, 63 (N = 16), 191, 543 (N = 64) of them.
+struct Cmp {
+    unsigned char a, b;
+};
+
+template <typename F>
+constexpr void batcher(int n, F &&f) {
+    for (int p = 1; p < n; p *= 2)
+        for (int k = p; k >= 1; k /= 2)
+            for (int j = k % p; j + k < n; j += 2 * k)
+                for (int i = 0; i < k && i + j + k < n; ++i)
+                    if ((i + j) / (2 * p) == (i + j + k) / (2 * p)) f(i + j, i + j + k);
+}
+
+template <int N>
+constexpr int net_count() {
+    int c = 0;
+    batcher(N, [&](int, int) { ++c; });
+    return c;
+}
+
+template <int N>
+struct NetTab {
+    Cmp c[net_count<N>() + 1];
+};
+
+template <int N>
+constexpr NetTab<N> make_net() {
+    NetTab<N> t{};
+    int c = 0;
+    batcher(N, [&](int a, int b) {
+        t.c[c].a = (unsigned char)a;
+        t.c[c].b = (unsigned char)b;
+        ++c;
+    });
+    return t;
+}
+
+template <int N>
+struct Net {
+    static constexpr int count = net_count<N>();
+    static constexpr NetTab<N> tab = make_net<N>();
+};
+
+// W coordinates' keys go through the network side by side: v[w][wire]
+template <int N, int W, int I>
+__device__ __forceinline__ void net_step(uint32_t (&v)[W][N]) {
+    if constexpr (I < Net<N>::count) {
+        constexpr int a = Net<N>::tab.c[I].a, b = Net<N>::tab.c[I].b;
+        static_assert(a < b && b < N, "comparator wires");
+#pragma unroll
+        for (int w = 0; w < W; ++w) {
+            const uint32_t lo = min(v[w][a], v[w][b]);
+            v[w][b] = max(v[w][a], v[w][b]);
+            v[w][a] = lo;
+        }
+    }
+}
+
+template <int N, int W, int I0, int... Is>
+__device__ __forceinline__ void net_chunk(uint32_t (&v)[W][N], std::integer_sequence<int, Is...>) {
+    (net_step<N, W, I0 + Is>(v), ...);
+}
+
+// comparators I0, I0 + 1, ... in chunks of 32 (a fold over all 543 would pass the
+// compiler's expression nesting limit)
+template <int N, int W, int I0 = 0>
+__device__ __forceinline__ void net_sort(uint32_t (&v)[W][N]) {
+    if constexpr (I0 < Net<N>::count) {
+        net_chunk<N, W, I0>(v, std::make_integer_sequence<int, 32>{});
+        net_sort<N, W, I0 + 32>(v);
+    }
+}
+
+// ------------------------------------------------------------------- keys
+// fp32 bits -> uint32 whose unsigned order is the contract's total order: the
+// sign-flip map (negative: all bits inverted; else the sign bit set), every NaN
+// on the top key.
+__device__ __forceinline__ uint32_t to_key(uint32_t u) {
+    const uint32_t k = u ^ ((uint32_t)((int32_t)u >> 31) | 0x80000000u);
+    return (u & 0x7fffffffu) > 0x7f800000u ? kTopKey : k;
+}
+
+__device__ __forceinline__ float from_key(uint32_t k) {
+    return __uint_as_float(k ^ ((uint32_t)((int32_t)~k >> 31) | 0x80000000u));
+}
+
+__device__ __forceinline__ float quiet(float x) {
+    return (__float_as_uint(x) & 0x7fffffffu) > 0x7f800000u ? __uint_as_float(0x7fc00000u) : x;
+}
+
+// ----------------------------------------------------------------- kernel
+// Coordinates C0 .. C0 + W - 1 of the lane's four: keys, network, trim, sum, division.
+template <int KP, int W, int C0>
+__device__ __forceinline__ void reduce_coords(const f32x4 (&x)[KP], int K, int trim, f32x4 &res) {
+    uint32_t v[W][KP];
+#pragma unroll
+    for (int j = 0; j < KP; ++j)
+#pragma unroll
+        for (int w = 0; w < W; ++w)
+            v[w][j] = j < K ? to_key(__float_as_uint(x[j][C0 + w])) : kTopKey;  // wave-uniform
+    net_sort<KP, W>(v);
+    // -0 + t == t for every fp32 t (-0 and NaN included), so starting from -0
+    // makes v[trim] the first term with its own bits, and m == 1 adds nothing else
+    const int lo = trim, hi = K - 1 - trim;
+    float acc[W];
+#pragma unroll
+    for (int w = 0; w < W; ++w) acc[w] = -0.f;
+#pragma unroll
+    for (int j = 0; j < KP; ++j) {
+        const bool kept = j >= lo && j <= hi;  // wave-uniform; t + -0 == t as well
+#pragma unroll
+        for (int w = 0; w < W; ++w) acc[w] = acc[w] + (kept ? from_key(v[w][j]) : -0.f);
+    }
+    const int m = hi - lo + 1;
+    if (m > 1) {
+        const float fm = (float)m;
+#pragma unroll
+        for (int w = 0; w < W; ++w) acc[w] = div_ieee(acc[w], fm);
+    }
+#pragma unroll
+    for (int w = 0; w < W; ++w) res[C0 + w] = quiet(acc[w]);
+}
+
+// KP wires (a power of two >= K); W of the lane's 4 coordinates are sorted at a
+// time (KP = 64: two at a time, so that the 256 loaded values and the 128 keys in
+// work fit the register file without scratch).  All KP loads are unconditional and
+// issued together: lane j >= K of the row table holds the last row, so a wire
+// past K re-reads that row's 16 bytes (a cache hit) and its key is replaced by
+// the top key; no branch touches a load or an element of the register arrays.
+template <int KP, int W>
+__global__ __launch_bounds__(kRobustBlock) void k_trimmed_mean(const f32x4 *__restrict__ Uv,
+                                                               int64_t ldu4,
+                                                               const int32_t *__restrict__ rows,
+                                                               int K, int trim, int64_t P4,
+                                                               f32x4 *__restrict__ out) {
+    const int lane = __lane_id();
+    const int64_t i0 = ((int64_t)blockIdx.x * (kRobustBlock / 64) + (threadIdx.x >> 6)) * 64 + lane;
+    const int64_t iq = i0 < P4 ? i0 : P4 - 1;  // every lane stays: the table needs all 64
+    const int tr = rows[min(lane, K - 1)];
+    f32x4 x[KP];
+#pragma unroll
+    for (int j = 0; j < KP; ++j) {
+        const int64_t r = __builtin_amdgcn_readlane(tr, j);
+        x[j] = __builtin_nontemporal_load(Uv + r * ldu4 + iq);
+    }
+    f32x4 res;
+    if constexpr (W == 4) {
+        reduce_coords<KP, 4, 0>(x, K, trim, res);
+    } else {
+        static_assert(W == 2, "coordinates per pass");
+        reduce_coords<KP, 2, 0>(x, K, trim, res);
+        __builtin_amdgcn_sched_barrier(0);  // one pass's keys in registers at a time
+        reduce_coords<KP, 2, 2>(x, K, trim, res);
+    }
+    if (i0 < P4) out[i0] = res;
+}
+
+template <int KP, int W = 4>
+void launch(const float *U, int64_t ldu, const int32_t *rows, int K, int trim, int64_t P4,
+            float *out, hipStream_t st) {
+    const dim3 grid((unsigned)((P4 + kRobustBlock - 1) / kRobustBlock));
+    hipLaunchKernelGGL((k_trimmed_mean<KP, W>), grid, dim3(kRobustBlock), 0, st,
+                       reinterpret_cast<const f32x4 *>(U), ldu / 4, rows, K, trim, P4,
+                       reinterpret_cast<f32x4 *>(out));
+}
+
+}  // namespace
+}  // namespace dls
+
+using namespace dls;
+
+extern "C" int dls_trimmed_mean_f32(const float *U, int64_t ldu, const int32_t *rows, int32_t K,
+                                    int32_t trim, int64_t P, float *out, dls_stream_t stream) {
+    DLS_REQUIRE(U && rows && out, DLS_EINVAL, "dls_trimmed_mean_f32: null pointer");
+    DLS_REQUIRE(K >= 1 && K <= DLS_ROBUST_MAX_K, DLS_EINVAL,
+                "dls_trimmed_mean_f32: K=%d (1..DLS_ROBUST_MAX_K=%d)", K, DLS_ROBUST_MAX_K);
+    DLS_REQUIRE(trim >= 0 && 2 * (int64_t)trim < K, DLS_EINVAL,
+                "dls_trimmed_mean_f32: trim=%d (0 <= 2*trim < K=%d)", trim, K);
+    DLS_REQUIRE(P >= 0, DLS_EINVAL, "dls_trimmed_mean_f32: P=%lld", (long long)P);
+    DLS_REQUIRE(P % 4 == 0 && ldu % 4 == 0 && ldu >= P, DLS_ELAYOUT,
+                "dls_trimmed_mean_f32: P=%lld and ldu=%lld must be multiples of 4, ldu >= P",
+                (long long)P, (long long)ldu);
+    DLS_REQUIRE(aligned16(U) && aligned16(out), DLS_ELAYOUT,
+                "dls_trimmed_mean_f32: 16-byte alignment");
+    if (P == 0) return DLS_OK;
+    const int64_t P4 = P / 4;
+    DLS_REQUIRE((P4 + kRobustBlock - 1) / kRobustBlock < (int64_t)1 << 31, DLS_EINVAL,
+                "dls_trimmed_mean_f32: grid too large");
+    hipStream_t st = as_stream(stream);
+    if (K == 1)
+        launch<1>(U, ldu, rows, K, trim, P4, out, st);
+    else if (K == 2)
+        launch<2>(U, ldu, rows, K, trim, P4, out, st);
+    else if (K <= 4)
+        launch<4>(U, ldu, rows, K, trim, P4, out, st);
+    else if (K <= 8)
+        launch<8>(U, ldu, rows, K, trim, P4, out, st);
+    else if (K <= 16)
+        launch<16>(U, ldu, rows, K, trim, P4, out, st);
+    else if (K <= 32)
+        launch<32>(U, ldu, rows, K, trim, P4, out, st);
+    else
+        launch<64, 2>(U, ldu, rows, K, trim, P4, out, st);
+    return check_launch("dls_trimmed_mean_f32");
+}

@@ -142,9 +142,17 @@ class ShardedFedServer(_ShardedMixin, FedServer):
     reference's it depends on thread timing, so two runs can give different
     bits; the clock is only comparable within one node, so when the ranks span
     several hosts the server falls back to ``"worker_id"`` (with a warning).
-    ``"worker_id"`` sorts by id: the same bits on every run."""
+    ``"worker_id"`` sorts by id: the same bits on every run.
+
+    ``aggregation_rule`` other than "mean" raises ``ValueError``: a rank holds only
+    its own clients' rows, and a coordinate's median is not a sum over ranks."""
+
+    _robust_unsupported = ("the sharded servers reduce each rank's own clients and sum over "
+                           "ranks, which a coordinate-wise order statistic is not")
 
     def __init__(self, group=None, chunks=3, exchange="allreduce", order="arrival", **kwargs):
+        self._check_rule(kwargs.get("aggregation_rule", "mean"), kwargs.get("trim", 0),
+                         kwargs.get("aggregation_mode", "exact"), kwargs.get("worker_number"))
         if exchange not in ("allreduce", "alltoall"):
             raise ValueError(f"exchange must be 'allreduce' or 'alltoall', not {exchange!r}")
         if order not in ("arrival", "worker_id"):

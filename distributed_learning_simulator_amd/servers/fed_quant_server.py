@@ -46,7 +46,12 @@ class FedQuantServer(FedServer):
     ``aggregation_mode="fma"`` runs the fused dequant-FedAvg with one constant per
     (client, channel) (dls_dequant_fedavg_mode, DLS_FEDAVG_FMA: within the
     north-star 1e-6 FedAvg tolerance, not bit-exact); the default "exact" is
-    bit-exact with the reference's dequant-then-average."""
+    bit-exact with the reference's dequant-then-average.
+
+    ``aggregation_rule`` other than "mean" raises ``ValueError``: the weighted mean is
+    fused with the dequantization here."""
+
+    _robust_unsupported = "its weighted mean is fused with the dequantization of the int payloads"
 
     def __init__(self, quantization_level=256, stochastic=False, seed=0, granularity="model",
                  **kwargs):

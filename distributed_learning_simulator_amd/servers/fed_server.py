@@ -17,21 +17,69 @@ from .server import Server
 log = logging.getLogger("distributed_learning_simulator_amd")
 
 _MODES = {"exact": _native.FEDAVG_EXACT, "fma": _native.FEDAVG_FMA}
+_RULES = ("mean", "median", "trimmed_mean")
 
 
 class FedServer(Server):
-    def __init__(self, aggregation_mode="exact", **kwargs):
+    """``aggregation_rule`` selects what a round (and ``get_subset_model``) computes
+    from the clients' rows:
+
+    * ``"mean"`` (default): the reference's weighted mean, ``aggregation_mode``
+      "exact" or "fma" (dls_fedavg_f32);
+    * ``"trimmed_mean"``: per coordinate, the ``trim`` lowest and ``trim`` highest
+      client values are dropped and the rest averaged (Yin et al. 2018;
+      dls_trimmed_mean_f32); ``"median"``: the coordinate-wise median.
+
+    The robust rules ignore the clients' sample counts n_i (every client counts
+    once), take at most ``_native.ROBUST_MAX_K`` clients and are bit-identical for
+    any arrival order.  Hooks, ``prev_model``, ``get_metric`` and the round protocol
+    are the same for every rule."""
+
+    # why a subclass cannot run the robust rules (None: it can)
+    _robust_unsupported = None
+
+    def __init__(self, aggregation_mode="exact", aggregation_rule="mean", trim=0, **kwargs):
         if aggregation_mode not in _MODES:
             raise ValueError(f"aggregation_mode must be one of {sorted(_MODES)}, not {aggregation_mode!r}")
+        self._check_rule(aggregation_rule, trim, aggregation_mode, kwargs.get("worker_number"))
         super().__init__(**kwargs)
         _native.require_gpu()
         self.round = 0
         self.aggregation_mode = aggregation_mode
+        self.aggregation_rule = aggregation_rule
+        self.trim = int(trim)
         self.parameters: ClientParameters = ClientParameters(self._make_store)
         self.__prev_model = copy.deepcopy(
             ModelUtil(self.tester.model).get_parameter_dict()) if self.tester is not None else {}
         self.worker_data_queue.put_result(
             RepeatedResult(data=self.prev_model, num=self.clients_per_round))
+
+    @classmethod
+    def _check_rule(cls, rule, trim, mode, worker_number):
+        if rule not in _RULES:
+            raise ValueError(f"aggregation_rule must be one of {list(_RULES)}, not {rule!r}")
+        if isinstance(trim, bool) or not isinstance(trim, int) or trim < 0:
+            raise ValueError(f"trim must be a non-negative integer, not {trim!r}")
+        if rule != "trimmed_mean" and trim != 0:
+            raise ValueError(f"trim={trim} needs aggregation_rule='trimmed_mean', not {rule!r}")
+        if rule == "mean":
+            return
+        if cls._robust_unsupported is not None:
+            raise ValueError(
+                f"{cls.__name__} does not support aggregation_rule={rule!r} "
+                f"({cls._robust_unsupported}); the one-process FedServer "
+                "(factory.get_server('fed', ...)) is the server that runs the median and "
+                "trimmed-mean rules")
+        if mode != "exact":
+            raise ValueError(f"aggregation_mode={mode!r} applies to aggregation_rule='mean' only; "
+                             f"{rule!r} has one arithmetic")
+        if worker_number is not None:
+            if worker_number > _native.ROBUST_MAX_K:
+                raise ValueError(f"aggregation_rule={rule!r} takes at most ROBUST_MAX_K="
+                                 f"{_native.ROBUST_MAX_K} clients, not worker_number={worker_number}")
+            if 2 * trim >= worker_number:
+                raise ValueError(f"trim={trim} leaves nothing of worker_number={worker_number} "
+                                 "clients (2*trim < worker_number is needed)")
 
     @property
     def clients_per_round(self):
@@ -87,7 +135,18 @@ class FedServer(Server):
         return store.layout.views(flat)
 
     def _aggregate(self, store, rows, ns, total=None):
-        return store.fedavg(rows, ns, mode=_MODES[self.aggregation_mode], total=total)
+        if self.aggregation_rule == "mean":
+            return store.fedavg(rows, ns, mode=_MODES[self.aggregation_mode], total=total)
+        K = len(rows)
+        if K > _native.ROBUST_MAX_K:
+            raise ValueError(f"aggregation_rule={self.aggregation_rule!r} takes at most "
+                             f"ROBUST_MAX_K={_native.ROBUST_MAX_K} clients, not {K}")
+        if self.aggregation_rule == "median":
+            return store.median(rows)
+        if 2 * self.trim >= K:
+            raise ValueError(f"trim={self.trim} leaves nothing of a subset of {K} clients "
+                             "(2*trim < len(subset) is needed)")
+        return store.trimmed_mean(rows, self.trim)
 
     def _process_worker_data(self, data, __):
         worker_id, training_dataset_size, parameter_dict = data

@@ -28,6 +28,8 @@ from .fed_server import FedServer
 
 
 class ShapleyValueServer(FedServer):
+    _robust_unsupported = "coalition models come from the batched subset-mean kernels"
+
     def __init__(self, subset_method="exact", subset_batch=None, eval_streams=1,
                  utility_metric="acc", **kwargs):
         if utility_metric not in ("acc", "loss"):

@@ -3,6 +3,7 @@
     python -m distributed_learning_simulator_amd.simulator --dataset_name MNIST \\
         --model_name LeNet5 --distributed_algorithm fed --worker_number 10 --round 5 \\
         --epoch 1 --learning_rate 0.01 --log_level INFO [--aggregation_mode fma]
+        [--aggregation_rule median | --aggregation_rule trimmed_mean --trim 2]
 
 Same flags and flow as the reference: IID split of the training set over the
 workers (:48-50), a tester on the test split (:51), ``factory.get_server``
@@ -58,19 +59,33 @@ def get_config(argv=None):
     # accuracy ("acc", the reference's) or its mean cross-entropy ("loss",
     # get_metric(model, "loss"), unnegated), both on the deterministic evaluation path
     ap.add_argument("--utility_metric", type=str, default="acc", choices=("acc", "loss"))
-    return ap.parse_args(argv)
+    # what the fed server computes from a round's client updates: the reference's
+    # weighted mean, or a robust coordinate-wise rule (FedServer): the median, or the
+    # trimmed mean that drops the --trim lowest and highest values of every
+    # coordinate.  The robust rules ignore the clients' sample counts.
+    ap.add_argument("--aggregation_rule", type=str, default="mean",
+                    choices=("mean", "median", "trimmed_mean"))
+    ap.add_argument("--trim", type=int, default=0)
+    config = ap.parse_args(argv)
+    if config.distributed_algorithm == "sign_SGD" and config.aggregation_rule != "mean":
+        ap.error("--aggregation_rule applies to the FedAvg-based servers; sign_SGD votes")
+    return config
 
 
 def server_kwargs(config):
     """The keyword arguments run() passes to factory.get_server beside tester /
     worker_number / multi_process: the aggregation mode for the FedAvg-based
-    servers (sign_SGD votes; it has no FedAvg), and the utility metric for the two
-    Shapley servers."""
+    servers (sign_SGD votes; it has no FedAvg), the utility metric for the two
+    Shapley servers, and the aggregation rule and its trim count when the rule is
+    not the default mean."""
     if config.distributed_algorithm == "sign_SGD":
         return {}
     kwargs = {"aggregation_mode": config.aggregation_mode}
     if config.distributed_algorithm in ("GTG_shapley_value", "multiround_shapley_value"):
         kwargs["utility_metric"] = getattr(config, "utility_metric", "acc")
+    if getattr(config, "aggregation_rule", "mean") != "mean":
+        kwargs["aggregation_rule"] = config.aggregation_rule
+        kwargs["trim"] = getattr(config, "trim", 0)
     return kwargs
 
 

@@ -113,6 +113,31 @@ int dls_subset_fedavg_union_f32(const float *U, int64_t ldu, const int32_t *urow
                                 const float *sub_total, int32_t S, int64_t P, float *out,
                                 int64_t ldo, dls_stream_t stream);
 
+/* Robust coordinate-wise aggregation: the trimmed mean (Yin et al. 2018) and, as
+ * its case trim = (K-1)/2, the median of K client rows.  Generalises the hook
+ * FedServer.get_subset_model (servers/fed_server.py:44-66) replaces by a
+ * weighted mean: same operands and layout rules as dls_fedavg_f32 (rows device
+ * int32 [K]; P, ldu multiples of 4, ldu >= P; U and out 16-byte aligned), but the
+ * client weights n_i play no part.  Per flat coordinate, independently:
+ *   1. order the K values ascending by IEEE value, -0.0 below +0.0 and every
+ *      NaN (any sign or payload) above +inf: a total order, values with equal
+ *      bits are interchangeable;
+ *   2. drop the `trim` lowest and the `trim` highest: v[trim] .. v[K-1-trim],
+ *      m = K - 2*trim >= 1 values, are kept;
+ *   3. acc = v[trim]; acc = fl32(acc + v[i]) for i ascending (one rounding
+ *      each); out = fl32(acc / fl32(m)), correctly rounded.  m == 1: out is
+ *      v[trim]'s own bits (no addition, no division: -0.0 stays -0.0).
+ * A NaN result — a kept NaN, or inf + -inf inside the sum — is the canonical
+ * quiet NaN 0x7fc00000.  The median of an even K is fl32(fl32(lo + hi) / 2);
+ * trim = 0 is the unweighted mean summed in ascending order (not FedAvg's
+ * arithmetic).  The result depends only on the multiset of each column: the
+ * same bits for any permutation of `rows`.
+ * 1 <= K <= DLS_ROBUST_MAX_K and 0 <= 2*trim < K, checked (with the null
+ * pointers) before any device call; P == 0 returns 0 without a launch. */
+#define DLS_ROBUST_MAX_K 64
+int dls_trimmed_mean_f32(const float *U, int64_t ldu, const int32_t *rows, int32_t K,
+                         int32_t trim, int64_t P, float *out, dls_stream_t stream);
+
 /* Subset aggregation as a dense fp32 MFMA contraction: out[S, P] = C[S, K] · U[rows, P]
  * (C row-major [S, K], c_si = n_i / N_S; rows[K] selects the K client rows of U).
  * fp32 in / fp32 accumulate (v_mfma_f32_32x32x2_f32): an fma chain in client
