@@ -344,8 +344,9 @@ def quantize(x, seg_off, total, scale, zp, q, deq=None, qmin=0, qmax=255, stocha
 
 
 def quantize_u8(x, seg_off, total, scale, zp, q, deq=None, stochastic=False, seed=0,
-                stream=None):
-    quantize(x, seg_off, total, scale, zp, q, deq, 0, 255, stochastic, seed, stream)
+                stream=None, qmax=255):
+    """Unsigned bytes in [0, qmax] (qmax = levels - 1 of the qparams)."""
+    quantize(x, seg_off, total, scale, zp, q, deq, 0, qmax, stochastic, seed, stream)
 
 
 # ----------------------------------------------------------- utility evaluation

@@ -1175,14 +1175,20 @@ __global__ __launch_bounds__(kBlock) void k_dequant_general(
 }
 
 // ------------------------------------------------------------- min / max
+// fp32 min / max through integer atomics (v is never NaN): values with a clear
+// sign bit order like signed ints, values with the sign bit set in reverse
+// unsigned order.  The branch is taken on the sign BIT, not on v >= 0: -0.0
+// has the bits of INT_MIN, which the signed atomic would order below every
+// negative value (min) and below the identity -inf (max).  By its bit -0.0
+// lies below +0.0 and above every negative in both helpers.
 __device__ __forceinline__ void atomic_min_f32(float *a, float v) {
-    if (v >= 0.f)
+    if (!(__float_as_uint(v) >> 31))
         atomicMin(reinterpret_cast<int *>(a), __float_as_int(v));
     else
         atomicMax(reinterpret_cast<unsigned int *>(a), __float_as_uint(v));
 }
 __device__ __forceinline__ void atomic_max_f32(float *a, float v) {
-    if (v >= 0.f)
+    if (!(__float_as_uint(v) >> 31))
         atomicMax(reinterpret_cast<int *>(a), __float_as_int(v));
     else
         atomicMin(reinterpret_cast<unsigned int *>(a), __float_as_uint(v));

@@ -117,8 +117,13 @@ class FedQuantServer(FedServer):
             _native.qparams_minmax(mins, maxs, scale, zp, 0, qmax)
         q = torch.empty(layout.P, dtype=torch.uint8, device=dev)
         deq = torch.empty(layout.P, dtype=torch.float32, device=dev)
+        # clamp at the level's qmax, not the byte's: rne(hi / scale) - rne(lo / scale) is
+        # qmax + 1 when both are ties that round apart
+        # (the byte's own 255 is quantize_u8's default: named only when it differs, so a
+        # stand-in for quantize_u8 with the 8-bit signature serves the default level)
+        level = {} if qmax == 255 else {"qmax": qmax}
         _native.quantize_u8(flat, seg, layout.P, scale, zp, q, deq, stochastic=self.stochastic,
-                            seed=self.seed + self.round)
+                            seed=self.seed + self.round, **level)
         if self.granularity == "model":
             self.quantized_parameter = (self._compact(layout, q), scale1, zp1)
         else:

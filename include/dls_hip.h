@@ -246,7 +246,11 @@ int dls_dequant_fedavg_mode(const dls_qtile *tiles, int32_t ntiles, const int32_
 
 /* Per-segment min / max of x over [seg_off[s], seg_off[s+1]) (torch.aminmax);
  * seg_off is device int64 [nseg+1] with seg_off[nseg] == total.  NaNs are
- * ignored (fminf/fmaxf). */
+ * ignored (fminf/fmaxf); an empty or all-NaN segment gives the identities
+ * (+inf, -inf).  Zeros compare by value: the sign of a zero result is not
+ * defined (a segment of -0.0 alone has min == max == 0), +-inf are ordinary
+ * values.  x needs fp32 alignment only (16-byte aligned chunks load as
+ * vectors). */
 int dls_segment_minmax_f32(const float *x, const int64_t *seg_off, int32_t nseg, float *mins,
                            float *maxs, int64_t total, dls_stream_t stream);
 
@@ -254,7 +258,15 @@ int dls_segment_minmax_f32(const float *x, const int64_t *seg_off, int32_t nseg,
  *   affine:    scale = max((max(hi,0) - min(lo,0)) / (qmax - qmin), eps),
  *              zp = clamp(qmin - rne(min(lo,0) / scale), qmin, qmax);
  *   symmetric: scale = max(max(-min(lo,0), max(hi,0)) / ((qmax - qmin) / 2), eps),
- *              zp = 0 (signed range) or (qmin + qmax + 1) / 2 (unsigned). */
+ *              zp = 0 (signed range) or (qmin + qmax + 1) / 2 (unsigned).
+ * Every operation rounds once to fp32, eps = 2^-23, min / max are fminf /
+ * fmaxf (a NaN operand is dropped).  So the identities (+inf, -inf) of an empty
+ * segment give the range [0, 0]: scale = eps, affine zp = qmin.  A non-finite
+ * bound gives scale = +inf; the affine zp is then qmin (lo / inf = -0, and for
+ * lo = -inf the NaN of inf / inf is dropped by the clamp's fmaxf).  The
+ * unsigned symmetric zp is the up-rounded midpoint, 128 for [0, 255] like
+ * torch's quint8 default; torch's observers take the down-rounded midpoint when
+ * given a custom range, and choose by dtype, not by the sign of qmin. */
 int dls_qparams_minmax(const float *mins, const float *maxs, int32_t nseg, int32_t qmin,
                        int32_t qmax, int32_t symmetric, float *scale, int32_t *zp,
                        dls_stream_t stream);
@@ -263,7 +275,11 @@ int dls_qparams_minmax(const float *mins, const float *maxs, int32_t nseg, int32
  * q = clamp(rne(x * fl(1/scale)) + zp, qmin, qmax) stored as one byte (int8 for
  * qmin < 0, else uint8); stochastic=1 replaces rne by floor(v + u),
  * u = counter-based uniform(seed, element) (parity unpinned).  deq (optional)
- * = fl(fl(q - zp) * scale), the client-side dequant formula. */
+ * = fl(fl(q - zp) * scale), the client-side dequant formula.  A NaN quantizes
+ * to qmin (the clamp's fmaxf drops it), +inf to qmax and -inf to qmin, in
+ * either rounding mode; -0.0 quantizes like +0.0.  Only bytes [0, total) of q
+ * and floats [0, total) of deq are written; q needs no alignment.  The uniform
+ * of an element depends on (seed, element index) alone, not on the segments. */
 int dls_quantize_affine(const float *x, const int64_t *seg_off, int32_t nseg, const float *scale,
                         const int32_t *zp, int32_t qmin, int32_t qmax, void *q, float *deq,
                         int32_t stochastic, uint64_t seed, int64_t total, dls_stream_t stream);

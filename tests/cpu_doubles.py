@@ -160,7 +160,8 @@ def qparams_minmax(mins, maxs, scale, zp, qmin=0, qmax=255, symmetric=False, str
         zp[i] = int(z)
 
 
-def quantize_u8(x, seg_off, total, scale, zp, q, deq=None, stochastic=False, seed=0, stream=None):
+def quantize_u8(x, seg_off, total, scale, zp, q, deq=None, stochastic=False, seed=0, stream=None,
+                qmax=255):
     from oracle import quant as oq
     assert not stochastic
     xn = _f32(x)
@@ -170,7 +171,7 @@ def quantize_u8(x, seg_off, total, scale, zp, q, deq=None, stochastic=False, see
     sc, zz = _f32(scale), _f32(zp)
     for s_ in range(off.size - 1):
         a, b = off[s_], off[s_ + 1]
-        qs = oq.quantize_affine(xn[a:b], sc[s_], int(zz[s_]))
+        qs = oq.quantize_affine(xn[a:b], sc[s_], int(zz[s_]), 0, qmax)
         qn[a:b] = qs
         dn[a:b] = oq.dequant_affine(qs, sc[s_], int(zz[s_]))
     q.copy_(torch.from_numpy(qn))
