@@ -65,6 +65,8 @@ SIGNATURES = {
     "dls_subset_fedavg_union_f32": ([_p, _i64, _p, _p, _p, _i32, _p, _i32, _i64, _p, _i64, _p],
                                     _i32),
     "dls_trimmed_mean_f32": ([_p, _i64, _p, _i32, _i32, _i64, _p, _p], _i32),
+    "dls_pairwise_sqdist_workspace": ([_i32, _i64], _i64),
+    "dls_pairwise_sqdist_f32": ([_p, _i64, _p, _i32, _i64, _p, _p, _p], _i32),
     "dls_subset_gemm_f32": ([_p, _i32, _i32, _p, _i64, _p, _i64, _p, _i64, _p], _i32),
     "dls_sign_pack_f32": ([_p, _i64, _i32, _i64, _p, _i64, _p, _p], _i32),
     "dls_sign_vote_count": ([_p, _i64, _p, _i32, _i64, _p, _p], _i32),
@@ -152,7 +154,7 @@ def _stream(stream=None, like=None):
 
 
 CSRC_HASHED = ["dls_runtime.hip", "fedavg.hip", "sign.hip", "quant.hip", "quant_fma.hip", "shapley.hip",
-               "infer.hip", "conv.hip", "lenet.hip", "loss.hip", "robust.hip", "dls_common.h", "quant_common.h",
+               "infer.hip", "conv.hip", "lenet.hip", "loss.hip", "robust.hip", "pairdist.hip", "dls_common.h", "quant_common.h",
                "loss_common.h", os.path.join("..", "..", "include", "dls_hip.h")]
 
 
@@ -227,6 +229,51 @@ def trimmed_mean(U, rows, trim, P, out, stream=None):
         return out
     _check(lib().dls_trimmed_mean_f32(_ptr(U), ldu, _ptr(rows), K, trim, P, _ptr(out),
                                       _stream(stream, U)), "dls_trimmed_mean_f32")
+    return out
+
+
+def pairwise_sqdist(U, rows, P, out=None, stream=None):
+    """Squared Euclidean distances between the K = rows.numel() selected rows of U over
+    their first P elements (dls_pairwise_sqdist_f32): an fp64 [K, K] device tensor,
+    symmetric in bits with a +0.0 diagonal, each entry within 2^-17 relative of the
+    exact squared distance of the fp32 rows; an entry of a row that holds inf or NaN
+    is +inf or NaN.  U: fp32 [*, ld] rows with unit element stride; rows: int32 [K],
+    1 <= K <= ROBUST_MAX_K; P a multiple of 4, at most the row length; out: a
+    contiguous fp64 [K, K] tensor (default: a new one)."""
+    fn = "pairwise_sqdist"
+    if (not torch.is_tensor(U) or U.dtype != torch.float32 or U.dim() != 2
+            or (U.shape[1] > 1 and U.stride(1) != 1)):
+        raise RuntimeError(f"{fn}: U must be an fp32 [rows, ld] matrix with unit element stride")
+    if not torch.is_tensor(rows) or rows.dtype != torch.int32 or rows.dim() != 1 \
+            or not rows.is_contiguous():
+        raise RuntimeError(f"{fn}: rows must be a contiguous int32 [K] tensor")
+    K = rows.numel()
+    if not 1 <= K <= ROBUST_MAX_K:
+        raise RuntimeError(f"{fn}: K={K} rows (1..ROBUST_MAX_K={ROBUST_MAX_K})")
+    P = int(P)
+    if P < 0 or P % 4 != 0 or P > U.shape[1]:
+        raise RuntimeError(f"{fn}: P={P} must be a multiple of 4 and at most the row "
+                           f"length {U.shape[1]}")
+    ldu = U.stride(0) if U.shape[0] > 1 else U.shape[1]
+    if ldu % 4 != 0 or ldu < P:
+        raise RuntimeError(f"{fn}: row pitch {ldu} must be a multiple of 4, at least P")
+    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.float64
+                            or tuple(out.shape) != (K, K) or not out.is_contiguous()):
+        raise RuntimeError(f"{fn}: out must be a contiguous fp64 [K, K] = [{K}, {K}] tensor")
+    _check_same_device(fn, U, rows=rows, out=out)
+    if U.data_ptr() % 16 != 0:
+        raise RuntimeError(f"{fn}: U must be 16-byte aligned")
+    if out is None:
+        out = torch.empty((K, K), dtype=torch.float64, device=U.device)
+    _ptr(U), _ptr(rows), _ptr(out)  # no CPU path
+    nbytes = int(lib().dls_pairwise_sqdist_workspace(K, P))
+    if nbytes < 0:
+        _check(nbytes, "dls_pairwise_sqdist_workspace")
+    work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=U.device)
+    _check(lib().dls_pairwise_sqdist_f32(_ptr(U), ldu, _ptr(rows), K, P, _ptr(out), _ptr(work),
+                                         _stream(stream, U)), "dls_pairwise_sqdist_f32")
+    if stream is not None:
+        work.record_stream(stream)
     return out
 
 

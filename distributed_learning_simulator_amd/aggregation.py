@@ -12,6 +12,7 @@ HBM layout:
   reference hooks and user code still see per-tensor dicts.
 """
 import heapq
+import math
 import threading
 
 import torch
@@ -75,6 +76,41 @@ def union_batch(subsets, n_of_row, device):
     totals = [float(sum(int(n_of_row[r]) for r in sub)) for sub in subsets]
     return (_i32(order, device), _f32([int(n_of_row[r]) for r in order], device),
             torch.tensor(member, dtype=torch.int64).to(device, non_blocking=True), totals)
+
+
+def multi_krum_select(D, ids, byzantine, select):
+    """The multi-Krum choice (Blanchard et al. 2017) from a [K, K] matrix of squared
+    distances, on the host: (selected_ids, scores).
+
+    ``D`` is any [K, K] array-like of float64 (row i belongs to client ``ids[i]``);
+    non-finite entries count as +inf.  Client i's score is the sum, ascending in
+    fp64, of the K - f - 2 smallest off-diagonal entries of row i (f =
+    ``byzantine``).  The clients are ordered by (score, id) ascending (the id
+    breaks ties, the arrival order never does) and the first ``select`` ids are
+    returned with the scores in the order of ``ids``.  ValueError: K < 2f + 3,
+    ``select`` outside 1..K - f, or fewer than ``select`` finite scores."""
+    ids = list(ids)
+    K, f, m = len(ids), int(byzantine), int(select)
+    rows = [[float(v) for v in row] for row in D]
+    if len(rows) != K or any(len(r) != K for r in rows):
+        raise ValueError(f"D must be a [{K}, {K}] matrix for {K} ids")
+    if f < 0 or K < 2 * f + 3:
+        raise ValueError(f"multi-Krum needs 2*byzantine + 3 <= K (byzantine={f}, K={K})")
+    if not 1 <= m <= K - f:
+        raise ValueError(f"select={m} must be in 1..K - byzantine = {K - f}")
+    scores = []
+    for i, row in enumerate(rows):
+        near = sorted(v if math.isfinite(v) else math.inf
+                      for j, v in enumerate(row) if j != i)[:K - f - 2]
+        sc = 0.0
+        for v in near:
+            sc += v
+        scores.append(sc)
+    order = sorted(range(K), key=lambda i: (scores[i], ids[i]))
+    if not math.isfinite(scores[order[m - 1]]):
+        finite = sum(1 for v in scores if math.isfinite(v))
+        raise ValueError(f"fewer than select={m} clients have a finite score ({finite} of {K})")
+    return [ids[i] for i in order[:m]], scores
 
 
 class ClientUpdateStore:
@@ -164,6 +200,29 @@ class ClientUpdateStore:
         trim = (K-1)//2 (an even K averages the two middle values)."""
         K = rows.numel() if torch.is_tensor(rows) else len(rows)
         return self.trimmed_mean(rows, (K - 1) // 2, out=out, cols=cols)
+
+    def pairwise_sqdist(self, rows, cols=None):
+        """Squared Euclidean distances between the given rows (dls_pairwise_sqdist_f32):
+        an fp64 [K, K] device tensor, symmetric in bits, +0.0 on the diagonal, the
+        same bits under any permutation of ``rows`` (permuted).  K <=
+        _native.ROBUST_MAX_K; ``cols`` as in ``fedavg``."""
+        c0, c1 = cols if cols is not None else (0, self.layout.P)
+        r = rows if torch.is_tensor(rows) else _i32(rows, self.device)
+        return _native.pairwise_sqdist(self.U[:, c0:], r, c1 - c0)
+
+    def multi_krum(self, rows, ids, byzantine, select, out=None):
+        """Multi-Krum over the given rows (client ``ids[i]`` in ``rows[i]``): one distance
+        launch, one copy of D to the host, ``multi_krum_select``, then the unweighted
+        ascending mean of the selected rows (``trimmed_mean`` with trim 0), which is
+        the same bits for any arrival order; ``select == 1`` returns the chosen row's
+        own bits.  Returns (flat, selected_ids, scores)."""
+        rows = [int(r) for r in rows]
+        ids = list(ids)
+        D = self.pairwise_sqdist(rows).cpu().tolist()
+        selected, scores = multi_krum_select(D, ids, byzantine, select)
+        row_of = dict(zip(ids, rows))
+        flat = self.trimmed_mean([row_of[i] for i in selected], 0, out=out)
+        return flat, selected, scores
 
     def subset_models(self, subsets, n_of_row, method="exact", out=None):
         """S subset models at once.  subsets: list of row lists (non-empty, in order)."""

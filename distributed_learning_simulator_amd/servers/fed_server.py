@@ -17,7 +17,7 @@ from .server import Server
 log = logging.getLogger("distributed_learning_simulator_amd")
 
 _MODES = {"exact": _native.FEDAVG_EXACT, "fma": _native.FEDAVG_FMA}
-_RULES = ("mean", "median", "trimmed_mean")
+_RULES = ("mean", "median", "trimmed_mean", "multi_krum")
 
 
 class FedServer(Server):
@@ -28,7 +28,13 @@ class FedServer(Server):
       "exact" or "fma" (dls_fedavg_f32);
     * ``"trimmed_mean"``: per coordinate, the ``trim`` lowest and ``trim`` highest
       client values are dropped and the rest averaged (Yin et al. 2018;
-      dls_trimmed_mean_f32); ``"median"``: the coordinate-wise median.
+      dls_trimmed_mean_f32); ``"median"``: the coordinate-wise median;
+    * ``"multi_krum"``: whole updates are scored by the sum of their squared
+      distances to their K - ``byzantine`` - 2 nearest neighbours
+      (dls_pairwise_sqdist_f32) and the ``krum_select`` best-scored ones (default
+      K - ``byzantine``) are averaged unweighted (Blanchard et al. 2017);
+      ``krum_select=1`` is classic Krum.  ``last_selection`` / ``last_scores``
+      hold the latest choice.
 
     The robust rules ignore the clients' sample counts n_i (every client counts
     once), take at most ``_native.ROBUST_MAX_K`` clients and are bit-identical for
@@ -38,16 +44,22 @@ class FedServer(Server):
     # why a subclass cannot run the robust rules (None: it can)
     _robust_unsupported = None
 
-    def __init__(self, aggregation_mode="exact", aggregation_rule="mean", trim=0, **kwargs):
+    def __init__(self, aggregation_mode="exact", aggregation_rule="mean", trim=0, byzantine=0,
+                 krum_select=None, **kwargs):
         if aggregation_mode not in _MODES:
             raise ValueError(f"aggregation_mode must be one of {sorted(_MODES)}, not {aggregation_mode!r}")
-        self._check_rule(aggregation_rule, trim, aggregation_mode, kwargs.get("worker_number"))
+        self._check_rule(aggregation_rule, trim, aggregation_mode, kwargs.get("worker_number"),
+                         byzantine, krum_select)
         super().__init__(**kwargs)
         _native.require_gpu()
         self.round = 0
         self.aggregation_mode = aggregation_mode
         self.aggregation_rule = aggregation_rule
         self.trim = int(trim)
+        self.byzantine = int(byzantine)
+        self.krum_select = None if krum_select is None else int(krum_select)
+        self.last_selection = ()
+        self.last_scores = {}
         self.parameters: ClientParameters = ClientParameters(self._make_store)
         self.__prev_model = copy.deepcopy(
             ModelUtil(self.tester.model).get_parameter_dict()) if self.tester is not None else {}
@@ -55,13 +67,21 @@ class FedServer(Server):
             RepeatedResult(data=self.prev_model, num=self.clients_per_round))
 
     @classmethod
-    def _check_rule(cls, rule, trim, mode, worker_number):
+    def _check_rule(cls, rule, trim, mode, worker_number, byzantine=0, krum_select=None):
         if rule not in _RULES:
             raise ValueError(f"aggregation_rule must be one of {list(_RULES)}, not {rule!r}")
         if isinstance(trim, bool) or not isinstance(trim, int) or trim < 0:
             raise ValueError(f"trim must be a non-negative integer, not {trim!r}")
         if rule != "trimmed_mean" and trim != 0:
             raise ValueError(f"trim={trim} needs aggregation_rule='trimmed_mean', not {rule!r}")
+        if isinstance(byzantine, bool) or not isinstance(byzantine, int) or byzantine < 0:
+            raise ValueError(f"byzantine must be a non-negative integer, not {byzantine!r}")
+        if krum_select is not None and (isinstance(krum_select, bool)
+                                        or not isinstance(krum_select, int)):
+            raise ValueError(f"krum_select must be an integer or None, not {krum_select!r}")
+        if rule != "multi_krum" and (byzantine != 0 or krum_select is not None):
+            raise ValueError(f"byzantine={byzantine} / krum_select={krum_select} needs "
+                             f"aggregation_rule='multi_krum', not {rule!r}")
         if rule == "mean":
             return
         if cls._robust_unsupported is not None:
@@ -80,6 +100,15 @@ class FedServer(Server):
             if 2 * trim >= worker_number:
                 raise ValueError(f"trim={trim} leaves nothing of worker_number={worker_number} "
                                  "clients (2*trim < worker_number is needed)")
+            if rule == "multi_krum":
+                if 2 * byzantine + 3 > worker_number:
+                    raise ValueError(f"byzantine={byzantine} is too many for worker_number="
+                                     f"{worker_number} (2*byzantine + 3 <= worker_number is needed)")
+                if krum_select is not None and not 1 <= krum_select <= worker_number - byzantine:
+                    raise ValueError(f"krum_select={krum_select} must be in 1..worker_number - "
+                                     f"byzantine = {worker_number - byzantine}")
+        elif rule == "multi_krum" and krum_select is not None and krum_select < 1:
+            raise ValueError(f"krum_select={krum_select} must be at least 1")
 
     @property
     def clients_per_round(self):
@@ -130,11 +159,14 @@ class FedServer(Server):
             return self.__prev_model
         ids = list(client_subset)
         store = self.parameters.store
+        # multi-Krum reports and breaks ties by worker id (no subclass that overrides
+        # _aggregate runs that rule)
+        extra = {"ids": ids} if self.aggregation_rule == "multi_krum" else {}
         flat = self._aggregate(store, [self.parameters.row_of(i) for i in ids],
-                               [self.parameters.n_of(i) for i in ids])
+                               [self.parameters.n_of(i) for i in ids], **extra)
         return store.layout.views(flat)
 
-    def _aggregate(self, store, rows, ns, total=None):
+    def _aggregate(self, store, rows, ns, total=None, ids=None):
         if self.aggregation_rule == "mean":
             return store.fedavg(rows, ns, mode=_MODES[self.aggregation_mode], total=total)
         K = len(rows)
@@ -143,10 +175,28 @@ class FedServer(Server):
                              f"ROBUST_MAX_K={_native.ROBUST_MAX_K} clients, not {K}")
         if self.aggregation_rule == "median":
             return store.median(rows)
+        if self.aggregation_rule == "multi_krum":
+            return self._multi_krum(store, rows, list(range(K)) if ids is None else ids)
         if 2 * self.trim >= K:
             raise ValueError(f"trim={self.trim} leaves nothing of a subset of {K} clients "
                              "(2*trim < len(subset) is needed)")
         return store.trimmed_mean(rows, self.trim)
+
+    def _multi_krum(self, store, rows, ids):
+        K, f = len(rows), self.byzantine
+        if 2 * f + 3 > K:
+            raise ValueError(f"byzantine={f} is too many for a subset of {K} clients "
+                             "(2*byzantine + 3 <= len(subset) is needed)")
+        select = K - f if self.krum_select is None else self.krum_select
+        if select > K - f:
+            raise ValueError(f"krum_select={select} exceeds len(subset) - byzantine = {K - f}")
+        flat, selected, scores = store.multi_krum(rows, ids, f, select)
+        self.last_selection = tuple(selected)
+        self.last_scores = dict(zip(ids, scores))
+        chosen = set(selected)
+        log.info("multi_krum: kept %s of %s clients, rejected workers %s", len(selected), K,
+                 [i for i in ids if i not in chosen])
+        return flat
 
     def _process_worker_data(self, data, __):
         worker_id, training_dataset_size, parameter_dict = data

@@ -3,7 +3,8 @@
     python -m distributed_learning_simulator_amd.simulator --dataset_name MNIST \\
         --model_name LeNet5 --distributed_algorithm fed --worker_number 10 --round 5 \\
         --epoch 1 --learning_rate 0.01 --log_level INFO [--aggregation_mode fma]
-        [--aggregation_rule median | --aggregation_rule trimmed_mean --trim 2]
+        [--aggregation_rule median | --aggregation_rule trimmed_mean --trim 2 |
+         --aggregation_rule multi_krum --byzantine 2 [--krum_select 1]]
 
 Same flags and flow as the reference: IID split of the training set over the
 workers (:48-50), a tester on the test split (:51), ``factory.get_server``
@@ -62,10 +63,15 @@ def get_config(argv=None):
     # what the fed server computes from a round's client updates: the reference's
     # weighted mean, or a robust coordinate-wise rule (FedServer): the median, or the
     # trimmed mean that drops the --trim lowest and highest values of every
-    # coordinate.  The robust rules ignore the clients' sample counts.
+    # coordinate, or multi-Krum, which scores whole updates by their squared
+    # distances to their nearest neighbours, assuming --byzantine bad clients, and
+    # averages the --krum_select best-scored ones (default: all but --byzantine;
+    # 1 is classic Krum).  The robust rules ignore the clients' sample counts.
     ap.add_argument("--aggregation_rule", type=str, default="mean",
-                    choices=("mean", "median", "trimmed_mean"))
+                    choices=("mean", "median", "trimmed_mean", "multi_krum"))
     ap.add_argument("--trim", type=int, default=0)
+    ap.add_argument("--byzantine", type=int, default=0)
+    ap.add_argument("--krum_select", type=int, default=None)
     config = ap.parse_args(argv)
     if config.distributed_algorithm == "sign_SGD" and config.aggregation_rule != "mean":
         ap.error("--aggregation_rule applies to the FedAvg-based servers; sign_SGD votes")
@@ -76,8 +82,8 @@ def server_kwargs(config):
     """The keyword arguments run() passes to factory.get_server beside tester /
     worker_number / multi_process: the aggregation mode for the FedAvg-based
     servers (sign_SGD votes; it has no FedAvg), the utility metric for the two
-    Shapley servers, and the aggregation rule and its trim count when the rule is
-    not the default mean."""
+    Shapley servers, the aggregation rule and its trim count when the rule is not the
+    default mean, and multi-Krum's byzantine / krum_select for that rule alone."""
     if config.distributed_algorithm == "sign_SGD":
         return {}
     kwargs = {"aggregation_mode": config.aggregation_mode}
@@ -86,6 +92,9 @@ def server_kwargs(config):
     if getattr(config, "aggregation_rule", "mean") != "mean":
         kwargs["aggregation_rule"] = config.aggregation_rule
         kwargs["trim"] = getattr(config, "trim", 0)
+        if config.aggregation_rule == "multi_krum":
+            kwargs["byzantine"] = getattr(config, "byzantine", 0)
+            kwargs["krum_select"] = getattr(config, "krum_select", None)
     return kwargs
 
 

@@ -138,6 +138,38 @@ int dls_subset_fedavg_union_f32(const float *U, int64_t ldu, const int32_t *urow
 int dls_trimmed_mean_f32(const float *U, int64_t ldu, const int32_t *rows, int32_t K,
                          int32_t trim, int64_t P, float *out, dls_stream_t stream);
 
+/* Pairwise squared distances between K client rows: the hot path of the
+ * distance-based robust rules (Krum / multi-Krum, Blanchard et al. 2017) and of
+ * client similarity.  Operands and layout rules of dls_trimmed_mean_f32 (rows
+ * device int32 [K]; P, ldu multiples of 4, ldu >= P; U 16-byte aligned;
+ * 1 <= K <= DLS_ROBUST_MAX_K); D is device fp64 [K*K] row-major (8-byte aligned);
+ * workspace is device memory of dls_pairwise_sqdist_workspace(K, P) bytes (a
+ * function of K and P alone; 16-byte aligned), scratch for this call only.
+ * Every check, the null pointers included, runs before any device call; P == 0
+ * writes an all-zero D.
+ *   D[a][b] ~ sum_p (U[rows[a]][p] - U[rows[b]][p])^2,
+ * every term formed from the difference of the two values (never the Gram form
+ * |x|^2 + |y|^2 - 2 x.y, which cancels catastrophically when clients differ in
+ * the 3rd or 4th digit):
+ *   d = fl32(x - y); acc = fmaf(d, d, acc) in fp32 chains of at most 120 terms;
+ *   the chain results are converted to fp64 and added in fp64 in a fixed order.
+ * All terms are non-negative, so for finite inputs whose terms neither overflow
+ * nor underflow D[a][b] is within (120 + 8) * 2^-24 = 2^-17 relative of the
+ * exact squared distance of the fp32 inputs.
+ * Exact properties: D[a][a] is +0.0 (written, not computed); D[a][b] has the bits
+ * of D[b][a]; repeated calls give the same bits on any stream; the summation
+ * order is a function of P and K alone (not of the device's CU count, ldu, the
+ * rows' position in U or the order of `rows`), so permuting `rows` permutes D
+ * without changing a bit, and rows of equal contents get equal distances to
+ * every third row.  No atomics: a second launch adds the per-wave partials of
+ * `workspace` in ascending order.
+ * If a row of the pair holds an inf or NaN, or a chain overflows, D[a][b]
+ * (a != b) is +inf or NaN; callers treat both as +inf.  Pairs of clean rows are
+ * unaffected. */
+int64_t dls_pairwise_sqdist_workspace(int32_t K, int64_t P);
+int dls_pairwise_sqdist_f32(const float *U, int64_t ldu, const int32_t *rows, int32_t K, int64_t P,
+                            double *D, void *workspace, dls_stream_t stream);
+
 /* Subset aggregation as a dense fp32 MFMA contraction: out[S, P] = C[S, K] · U[rows, P]
  * (C row-major [S, K], c_si = n_i / N_S; rows[K] selects the K client rows of U).
  * fp32 in / fp32 accumulate (v_mfma_f32_32x32x2_f32): an fma chain in client
