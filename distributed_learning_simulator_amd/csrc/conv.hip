@@ -32,15 +32,13 @@
 // output tile = 2 x 2 MFMA tiles; operands are staged in chunks of 32 channels
 // through LDS (register staging, rows padded by 16 B: conflict-free
 // ds_read_b128 fragments).  Kernels:
-//   k_conv3x3_pipe16  3x3 stride-1 convolutions (the default): k_conv3x3_pipe's
-//                   pipeline on v_mfma_f32_16x16x32_bf16 (4 x 4 tiles of 16 x 16
-//                   per wave; -0.9 % per forward, profiles/r06_forward_mf16_ab.txt);
-//   k_conv3x3_pipe  3x3 stride-1 convolutions: the block's pixels are whole
+//   k_conv3x3_pipe16  3x3 stride-1 convolutions: the block's pixels are whole
 //                   output rows, so its input is ONE halo tile staged once per
 //                   channel chunk and read by all 9 taps at shifted rows; every
 //                   operand staged by LDS-DMA into XOR-swizzled rows and kept in
 //                   flight across the barriers (a 3-slot weight ring, 1 or 2
-//                   halo buffers);
+//                   halo buffers); v_mfma_f32_16x16x32_bf16, 4 x 4 tiles of
+//                   16 x 16 per wave;
 //   k_conv3x3_halo  the same tiling register-staged (shapes whose halo tile the
 //                   pipeline's LDS budget does not fit; none of ResNet-18's);
 //   k_conv3x3s2_phase  3x3 stride-2 convolutions as four stride-1 ones over
@@ -63,34 +61,6 @@
 #include "dls_common.h"
 
 #include <mutex>
-
-#ifndef DLS_CONV_GENERIC_ONLY
-#define DLS_CONV_GENERIC_ONLY 0
-#endif
-#ifndef DLS_CONV_PHASE  // probe knob: 0 = the generic kernel for 3x3 stride-2 shapes
-#define DLS_CONV_PHASE 1
-#endif
-#ifndef DLS_STEM_WINDOW  // probe knob: 0 = the stem's 27 terms gathered from global memory
-#define DLS_STEM_WINDOW 1
-#endif
-#ifndef DLS_CONV_MF16  // probe knob: 0 = the 3x3 stride-1 pipeline on 32x32x16 MFMAs (k_conv3x3_pipe)
-#define DLS_CONV_MF16 1
-#endif
-#ifndef DLS_STEM_TILES  // probe knob: pixel tiles per block of the CIFAR stem (k_conv_stem, XT)
-#define DLS_STEM_TILES 2
-#endif
-#ifndef DLS_CONV_SERPENTINE  // probe knob: 0 = every launch walks its tiles forward
-#define DLS_CONV_SERPENTINE 1
-#endif
-#ifndef DLS_PIPE_NARROW  // probe knob: bit 0/1/2 = 128-channel-multiple layers 16/8/4 wide in 64-channel 4-wave blocks
-#define DLS_PIPE_NARROW 1  // 16 wide: -0.9 % per forward; 8 wide: null; 4 wide: +0.6 % (profiles/r06_forward_narrow_ab.txt)
-#endif
-#ifndef DLS_STEM_PIXSPLIT  // probe knob: 1 = the stem's two epilogue passes split the pixels, not the channels
-#define DLS_STEM_PIXSPLIT 1
-#endif
-#ifndef DLS_CONV_PIPE  // probe knob: 0 = no LDS-DMA pipeline (k_conv3x3_halo for every 3x3 stride-1 shape)
-#define DLS_CONV_PIPE 1
-#endif
 
 namespace dls {
 namespace {
@@ -371,6 +341,19 @@ __device__ __forceinline__ void tile_of_block(int co_tiles, int &co_t, int &pix_
     const int t = x * q + (x < rmd ? x : rmd) + k;
     co_t = t % co_tiles;
     pix_t = t / co_tiles;
+}
+
+// The first image b0 and first row y0 of pixel tile pt: TI whole images of
+// `rows` rows (TR == rows), or TR rows of one image
+__device__ __forceinline__ void tile_origin(int pt, int TI, int TR, int rows, int &b0, int &y0) {
+    if (TR == rows) {
+        b0 = pt * TI;
+        y0 = 0;
+    } else {
+        const int tpi = rows / TR;
+        b0 = pt / tpi;
+        y0 = (pt - b0 * tpi) * TR;
+    }
 }
 
 // ---------------------------------------------------------------- generic
@@ -661,13 +644,13 @@ __global__ __launch_bounds__(64 * WCO * WPIX, 2) void k_conv3x3_halo(ConvArgs a)
 // 8x8 and -14 % on 4x4 (8-wave, NHB = 2), -1 to -2 % on 32x32 (64 channels,
 // 4-wave, NHB = 1).
 // LDS rows are 128 B (32 hi + 32 lo bf16) with the 16-B pieces XOR-swizzled by
-// (s >> 1) & 7, s = the row's position in the MFMA lane order (the weight row;
-// for a halo row, the output pixel it is under tap (0, 0) — consecutive along
-// the tile's pixels at every tap): every ds_read_b128 lane group of 16 lanes hits
-// 16 distinct 4-bank groups.  The DMA writes each wave-instruction's 64 pieces
+// a key of s, the row's position in the MFMA lane order (the weight row; for a
+// halo row, the output pixel it is under tap (0, 0) — consecutive along the
+// tile's pixels at every tap): (s >> 1) & 7 for the 32-row fragments of
+// 32x32x16 MFMAs (k_conv3x3s2_phase), s & 7 for the 16-row ones of 16x16x32
+// (k_conv3x3_pipe16), so every ds_read_b128 lane group of 16 lanes hits 16
+// distinct 4-bank groups.  The DMA writes each wave-instruction's 64 pieces
 // lane-linearly, so the swizzle is applied to the lanes' SOURCE addresses.
-// Every output element is reduced in the halo kernel's order (chunks, taps,
-// k-steps, lo*hi, hi*lo, hi*hi): the same bits.
 __device__ __attribute__((aligned(16))) uint32_t kZeroPiece[4];  // source of the halo's padding pieces
 
 __device__ __forceinline__ void glds16(const uint16_t *src, uint8_t *lds_base) {
@@ -687,195 +670,65 @@ __device__ __forceinline__ void retire_and_barrier(bool piece_in_flight) {
     asm volatile("" ::: "memory");
 }
 
-// NHB = 1 (one halo buffer, blocks of <= 80 KB that fit two to a CU): the next
-// chunk's halo is loaded after the chunk's last tap, its latency exposed in this
-// block and covered by the other block on the CU.
-template <int WCO, int WPIX, int NHI, int NHB = 2, int OCC = 1>
-__global__ __launch_bounds__(64 * WCO * WPIX, OCC) void k_conv3x3_pipe(ConvArgs a) {
-    constexpr int NW = WCO * WPIX, NT = 64 * NW;
-    constexpr int BMC = kWaveTile * WCO, BNP = kWaveTile * WPIX;
-    constexpr int RB = 128;                 // LDS row: 32 hi + 32 lo bf16
-    constexpr int HROWS = 8 * NW * NHI;     // halo rows per buffer (8 rows per wave-instruction)
-    constexpr int HB = HROWS * RB, AB = BMC * RB;
-    constexpr int NAI = BMC / (8 * NW);     // weight DMAs per wave per step
-    constexpr int STAGE = NHB * HB + 3 * AB + 2 * RB;  // + the zero rows
-    constexpr int EPI = BNP * (4 * BMC + 16);
+// What the two LDS-DMA pipelines (k_conv3x3_pipe16, k_conv3x3s2_phase) share.
+// A block's LDS: NHB halo buffers of 8 * NW * NHI rows (8 rows per
+// wave-instruction, NHI DMAs per wave), the 3-slot weight ring, two zero rows.
+template <int WCO, int WPIX, int NHI, int NHB>
+struct PipeLds {
+    static constexpr int NW = WCO * WPIX, NT = 64 * NW;
+    static constexpr int BMC = kWaveTile * WCO, BNP = kWaveTile * WPIX;
+    static constexpr int RB = 128;              // LDS row: 32 hi + 32 lo bf16
+    static constexpr int HROWS = 8 * NW * NHI;  // halo rows per buffer
+    static constexpr int HB = HROWS * RB, AB = BMC * RB;
+    static constexpr int NAI = BMC / (8 * NW);  // weight DMAs per wave per step
+    static constexpr int STAGE = NHB * HB + 3 * AB + 2 * RB;
+    static constexpr int EPI = BNP * (4 * BMC + 16);
+    static constexpr int BYTES = STAGE > EPI ? STAGE : EPI;
     static_assert(BMC % (8 * NW) == 0 && NAI >= 1, "weight rows per wave");
-    static_assert(NHB == 1 || NHI <= 7, "the halo pieces go out in taps 0..6");
     static_assert(NHB == 1 || NHB == 2, "halo buffers");
     static_assert(kBK == 32, "128-byte rows");
-    __shared__ __attribute__((aligned(16))) uint8_t smem[STAGE > EPI ? STAGE : EPI];
-    uint8_t *const hbuf0 = smem;
-    uint8_t *const abuf0 = smem + NHB * HB;
-    // what a tap reads left / right of the image: two zero rows (256-B aligned),
-    // each lane reading the one of its row's parity, so that it hits the banks a
-    // halo row of its position would (no conflicts with the other lanes)
-    uint8_t *const zrow = abuf0 + 3 * AB;
+};
 
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int wc = wv / WPIX, wp = wv % WPIX;
-    int co_t, pt;
-    tile_of_block(a.co_tiles, co_t, pt, a.rev);
-    const int co0 = co_t * BMC;
-    const int pix0 = pt * BNP;
-    const int W = a.W, H = a.H, TR = a.TR;
-    const int hrows_img = (TR + 2) * W;  // TR + 2 image rows, no padding columns
-    int b0, y0;
-    if (TR == H) {
-        b0 = pt * a.TI;
-        y0 = 0;
-    } else {
-        const int tpi = H / TR;
-        b0 = pt / tpi;
-        y0 = (pt - b0 * tpi) * TR;
-    }
-
-    // DMA sources: lane l of a wave-instruction fills slot l & 7 of row l >> 3 of
-    // its 8 rows with the piece (l & 7) ^ swizzle(row)
-    // a halo DMA lane's source, one register per DMA: input pixel * 8 + piece, or
-    // -1 for the zero piece
-    const int sl = lane & 7, lr = lane >> 3;
-    int hsrc[NHI];
-#pragma unroll
-    for (int u = 0; u < NHI; ++u) {
-        const int hr = 8 * (u * NW + wv) + lr;
-        int pix = -1, s = 0;
-        if (hr < a.NH) {
-            const int ti = hr / hrows_img, rem = hr - ti * hrows_img;
-            const int ry = rem / W, rx = rem - ry * W;
-            s = hr - 2 * W * ti;  // = the row's pixel under tap (1, 1): consecutive along a tile
-            const int b = b0 + ti, iy = y0 - 1 + ry;
-            if (b < a.B && (unsigned)iy < (unsigned)H) pix = (b * H + iy) * W + rx;
-        }
-        hsrc[u] = pix >= 0 ? pix * 8 + (sl ^ ((s >> 1) & 7)) : -1;
-    }
-    // the zero piece's address, opaque to the compiler: computed once, not
-    // re-loaded from the GOT in the loop (a scalar load there would make every
-    // lgkmcnt wait a full drain)
+// The zero piece's address, opaque to the compiler: computed once, not re-loaded
+// from the GOT in the loop (a scalar load there would make every lgkmcnt wait a
+// full drain)
+__device__ __forceinline__ const uint16_t *zero_piece() {
     const uint16_t *zero = reinterpret_cast<const uint16_t *>(kZeroPiece);
     asm volatile("" : "+s"(zero));
-    const uint16_t *asrc[NAI];
-#pragma unroll
-    for (int u = 0; u < NAI; ++u) {
-        const int row = 8 * (wv * NAI + u) + lr;
-        const int p = sl ^ ((row >> 1) & 7);
-        asrc[u] = a.w + (int64_t)(co0 + row) * (2 * a.K) + ((p & 4) ? a.K : 0) + 8 * (p & 3);
-    }
-    auto issue_weights = [&](int step, int slot) {  // step's weights into ring slot slot % 3
-        const int cc = step / 9, tap = step - 9 * cc;
-        const int kc = tap * a.C + cc * kBK;
-        uint8_t *dst = abuf0 + (slot % 3) * AB;
-#pragma unroll
-        for (int u = 0; u < NAI; ++u) glds16(asrc[u] + kc, dst + (wv * NAI + u) * 8 * RB);
-    };
-    auto issue_halo = [&](int u, int cc) {
-        const int v = hsrc[u], p = v & 7;
-        const uint16_t *src =
-            v >= 0 ? a.x + (int64_t)(v >> 3) * (2 * a.C) + ((p & 4) ? a.C : 0) + 8 * (p & 3) + cc * kBK : zero;
-        glds16(src, hbuf0 + (NHB == 2 ? (cc & 1) * HB : 0) + (u * NW + wv) * 8 * RB);
-    };
-
-    // fragment addresses: lane (r, h) reads A rows wc*64 + 32 i + r and the halo
-    // rows of pixels wp*64 + 32 j + r
-    const int r = lane & 31, h = lane >> 5;
-    const int fa = (r >> 1) & 7;
-    const int arow = (wc * kWaveTile + r) * RB;
-    // pixel tile 1 is tile 0 shifted by 32 pixels: W divides 32 (try_launch_pipe),
-    // so it has tile 0's columns, and its halo rows sit a block-uniform dhb further
-    int hb0, pl0, ox0;
-    {
-        pl0 = wp * kWaveTile + r;
-        const int tw = TR * W;
-        const int ti = pl0 / tw, rem = pl0 - ti * tw;
-        const int oy = rem / W;
-        ox0 = rem - oy * W;
-        hb0 = ti * hrows_img + oy * W + ox0;  // its halo row under tap (0, 1)
-    }
-    const int dhb = TR * W >= 32 ? 32 : (32 / (TR * W)) * hrows_img;
-    auto frag = [&](Frag &f, int step, int tap, int s) {
-        const uint8_t *ab = abuf0 + (step % 3) * AB + arow;
-        const uint8_t *hbb = hbuf0 + (NHB == 2 ? ((step / 9) & 1) * HB : 0);
-        const int qh = 16 * ((2 * s + h) ^ fa), ql = 16 * ((4 + 2 * s + h) ^ fa);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            f.ah[i] = *reinterpret_cast<const bf16x8 *>(ab + i * 32 * RB + qh);
-            f.al[i] = *reinterpret_cast<const bf16x8 *>(ab + i * 32 * RB + ql);
-        }
-        const int ky = tap / 3, kx = tap - 3 * ky;
-        const int sh = ky * W + kx - 1;
-        const bool in = (unsigned)(ox0 + kx - 1) < (unsigned)W;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int fb = ((pl0 + 32 * j + sh) >> 1) & 7;
-            const uint8_t *row = in ? hbb + (hb0 + j * dhb + sh) * RB : zrow + ((pl0 + sh) & 1) * RB;
-            f.bh[j] = *reinterpret_cast<const bf16x8 *>(row + 16 * ((2 * s + h) ^ fb));
-            f.bl[j] = *reinterpret_cast<const bf16x8 *>(row + 16 * ((4 + 2 * s + h) ^ fb));
-        }
-    };
-
-    WaveAcc acc;
-    zero_acc(acc);
-    const int nc = a.C / kBK, T = 9 * nc;
-    if (tid < 2 * RB / 16) *reinterpret_cast<u32x4 *>(zrow + 16 * tid) = u32x4{0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int u = 0; u < NHI; ++u) issue_halo(u, 0);
-    issue_weights(0, 0);
-    issue_weights(T > 1 ? 1 : 0, 1);
-    retire_and_barrier<NW>(false);
-    Frag f0, f1;
-    frag(f0, 0, 0, 0);
-    for (int cc = 0; cc < nc; ++cc) {
-        const bool more = cc + 1 < nc;
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {
-            // unconditional in every step (the last steps re-load the last
-            // weights into a buffer no later step reads; the fragments past the
-            // last step read stale LDS), so that the compiler's lgkmcnt / vmcnt
-            // counts stay exact
-            const int t = 9 * cc + tap;
-            const bool piece = NHB == 2 && more && tap < NHI;
-            issue_weights(t + 2 < T ? t + 2 : T - 1, t + 2);
-            if (piece) issue_halo(tap, cc + 1);
-            // the order is pinned: each k-step's reads go out a whole k-step of
-            // MFMAs ahead of their use (left alone, the compiler sinks them next
-            // to their MFMAs to save registers)
-            __builtin_amdgcn_s_waitcnt(kWaitLgkm0);
-            frag(f1, t, tap, 1);
-            __builtin_amdgcn_sched_barrier(0);
-            mfma_frag(acc, f0);
-            __builtin_amdgcn_sched_barrier(0);
-            const bool reload = NHB == 1 && tap == 8 && more;  // the next chunk's halo is not in yet
-            if (!reload) {
-                __builtin_amdgcn_s_waitcnt(kWaitLgkm0);
-                frag(f0, t + 1, tap == 8 ? 0 : tap + 1, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            mfma_frag(acc, f1);
-            retire_and_barrier<NW>(piece);
-            if (reload) {  // every wave is past its reads of this chunk's halo
-#pragma unroll
-                for (int u = 0; u < NHI; ++u) issue_halo(u, cc + 1);
-                retire_and_barrier<NW>(false);
-                frag(f0, t + 1, 0, 0);
-            }
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();  // every wave is past its last fragment read
-    epilogue_lds<BMC, BNP, NT>(acc, smem, a, co0, pix0, wc, wp, tid);
+    return zero;
 }
 
-// k_conv3x3_pipe on v_mfma_f32_16x16x32_bf16: a wave's 64 x 64 tile as 4 x 4
-// tiles of 16 x 16, one MFMA per (tile, product) covering the whole 32-channel
-// step (the 16 A / B fragment reads per step are k_conv3x3_pipe's 16).  Under
-// load the chip holds a higher clock on this shape than on 32x32x16
-// (MI355X_MICROARCH.md, DVFS give-back item 7).  The 16-B pieces are swizzled
+// What a tap reads left / right of the image: two zero rows (256-B aligned),
+// each lane reading the one of its row's parity, so that it hits the banks a
+// halo row of its position would (no conflicts with the other lanes)
+template <class L>
+__device__ __forceinline__ void zero_rows(uint8_t *zrow, int tid) {
+    if (tid < 2 * L::RB / 16) *reinterpret_cast<u32x4 *>(zrow + 16 * tid) = u32x4{0u, 0u, 0u, 0u};
+}
+
+// A step's weights (element offset kc of every row) into ring slot slot % 3
+template <class L>
+__device__ __forceinline__ void issue_weight_ring(const uint16_t *const (&asrc)[L::NAI], int kc,
+                                                  uint8_t *abuf0, int slot, int wv) {
+    uint8_t *dst = abuf0 + (slot % 3) * L::AB;
+#pragma unroll
+    for (int u = 0; u < L::NAI; ++u) glds16(asrc[u] + kc, dst + (wv * L::NAI + u) * 8 * L::RB);
+}
+
+// The stride-1 pipeline runs on v_mfma_f32_16x16x32_bf16: a wave's 64 x 64 tile
+// as 4 x 4 tiles of 16 x 16, one MFMA per (tile, product) covering the whole
+// 32-channel step (16 A / B fragment reads per step).  Under load the chip holds
+// a higher clock on this shape than on 32x32x16 (-0.9 % per forward,
+// profiles/r06_forward_mf16_ab.txt).  The 16-B pieces are swizzled
 // by row & 7 (a 16-row fragment read at any row offset is conflict-free; the
 // 32-row form's (row >> 1) & 7 is 2-way at odd offsets).  A step's fragments are
 // read whole a step ahead (two sets in registers), the next step's during this
 // step's 48 MFMAs.  Reduction order per output: chunks, taps, then per step the
-// products lo*hi, hi*lo, hi*hi over the 32 channels inside the MFMA — not
-// k_conv3x3_pipe's bits.
+// products lo*hi, hi*lo, hi*hi over the 32 channels inside the MFMA — not the
+// halo kernel's bits.
+// NHB = 1 (one halo buffer, blocks of <= 80 KB that fit two to a CU): the next
+// chunk's halo is loaded after the chunk's last tap, its latency exposed in this
+// block and covered by the other block on the CU.
 // A step's fragments in two parts: A (all four channel tiles) with pixel tiles
 // 0-1, and pixel tiles 2-3 (read during the MFMAs of the first part)
 struct Frag16A {
@@ -901,19 +754,10 @@ __device__ __forceinline__ void mfma_half16(WaveAcc16 &acc, const Frag16A &fa, c
 
 template <int WCO, int WPIX, int NHI, int NHB = 2, int OCC = 1>
 __global__ __launch_bounds__(64 * WCO * WPIX, OCC) void k_conv3x3_pipe16(ConvArgs a) {
-    constexpr int NW = WCO * WPIX, NT = 64 * NW;
-    constexpr int BMC = kWaveTile * WCO, BNP = kWaveTile * WPIX;
-    constexpr int RB = 128;
-    constexpr int HROWS = 8 * NW * NHI;
-    constexpr int HB = HROWS * RB, AB = BMC * RB;
-    constexpr int NAI = BMC / (8 * NW);
-    constexpr int STAGE = NHB * HB + 3 * AB + 2 * RB;
-    constexpr int EPI = BNP * (4 * BMC + 16);
-    static_assert(BMC % (8 * NW) == 0 && NAI >= 1, "weight rows per wave");
+    using L = PipeLds<WCO, WPIX, NHI, NHB>;
+    constexpr int NW = L::NW, NT = L::NT, BMC = L::BMC, BNP = L::BNP, RB = L::RB, HB = L::HB, AB = L::AB;
     static_assert(NHB == 1 || NHI <= 7, "the halo pieces go out in taps 0..6");
-    static_assert(NHB == 1 || NHB == 2, "halo buffers");
-    static_assert(kBK == 32, "128-byte rows");
-    __shared__ __attribute__((aligned(16))) uint8_t smem[STAGE > EPI ? STAGE : EPI];
+    __shared__ __attribute__((aligned(16))) uint8_t smem[L::BYTES];
     uint8_t *const hbuf0 = smem;
     uint8_t *const abuf0 = smem + NHB * HB;
     uint8_t *const zrow = abuf0 + 3 * AB;
@@ -925,18 +769,12 @@ __global__ __launch_bounds__(64 * WCO * WPIX, OCC) void k_conv3x3_pipe16(ConvArg
     const int co0 = co_t * BMC;
     const int pix0 = pt * BNP;
     const int W = a.W, H = a.H, TR = a.TR;
-    const int hrows_img = (TR + 2) * W;
+    const int hrows_img = (TR + 2) * W;  // TR + 2 image rows, no padding columns
     int b0, y0;
-    if (TR == H) {
-        b0 = pt * a.TI;
-        y0 = 0;
-    } else {
-        const int tpi = H / TR;
-        b0 = pt / tpi;
-        y0 = (pt - b0 * tpi) * TR;
-    }
+    tile_origin(pt, a.TI, TR, H, b0, y0);
 
-    // DMA sources as k_conv3x3_pipe's, the piece swizzled by the row's key & 7
+    // a halo DMA lane's source, one register per DMA: input pixel * 8 + piece
+    // (swizzled by the row's key & 7), or -1 for the zero piece
     const int sl = lane & 7, lr = lane >> 3;
     int hsrc[NHI];
 #pragma unroll
@@ -946,29 +784,28 @@ __global__ __launch_bounds__(64 * WCO * WPIX, OCC) void k_conv3x3_pipe16(ConvArg
         if (hr < a.NH) {
             const int ti = hr / hrows_img, rem = hr - ti * hrows_img;
             const int ry = rem / W, rx = rem - ry * W;
-            s = hr - 2 * W * ti;
+            s = hr - 2 * W * ti;  // = the row's pixel under tap (1, 1): consecutive along a tile
             const int b = b0 + ti, iy = y0 - 1 + ry;
             if (b < a.B && (unsigned)iy < (unsigned)H) pix = (b * H + iy) * W + rx;
         }
         hsrc[u] = pix >= 0 ? pix * 8 + (sl ^ (s & 7)) : -1;
     }
-    const uint16_t *zero = reinterpret_cast<const uint16_t *>(kZeroPiece);
-    asm volatile("" : "+s"(zero));
-    const uint16_t *asrc[NAI];
+    const uint16_t *zero = zero_piece();
+    // weight DMA sources: lane l of a wave-instruction fills slot l & 7 of row
+    // l >> 3 of its 8 rows with the piece (l & 7) ^ key(row); pieces 0-3 are the
+    // row's hi run, 4-7 its lo run
+    const uint16_t *asrc[L::NAI];
 #pragma unroll
-    for (int u = 0; u < NAI; ++u) {
-        const int row = 8 * (wv * NAI + u) + lr;
+    for (int u = 0; u < L::NAI; ++u) {
+        const int row = 8 * (wv * L::NAI + u) + lr;
         const int p = sl ^ (row & 7);
         asrc[u] = a.w + (int64_t)(co0 + row) * (2 * a.K) + ((p & 4) ? a.K : 0) + 8 * (p & 3);
     }
-    auto issue_weights = [&](int step, int slot) {
+    auto issue_weights = [&](int step, int slot) {  // step's weights into ring slot slot % 3
         const int cc = step / 9, tap = step - 9 * cc;
         int Cv = a.C;  // opaque per step: no per-tap source addresses hoisted out of the loop
         asm volatile("" : "+s"(Cv));
-        const int kc = tap * Cv + cc * kBK;
-        uint8_t *dst = abuf0 + (slot % 3) * AB;
-#pragma unroll
-        for (int u = 0; u < NAI; ++u) glds16(asrc[u] + kc, dst + (wv * NAI + u) * 8 * RB);
+        issue_weight_ring<L>(asrc, tap * Cv + cc * kBK, abuf0, slot, wv);
     };
     auto issue_halo = [&](int u, int cc) {
         const int v = hsrc[u], p = v & 7;
@@ -1027,7 +864,7 @@ __global__ __launch_bounds__(64 * WCO * WPIX, OCC) void k_conv3x3_pipe16(ConvArg
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int nc = a.C / kBK, T = 9 * nc;
-    if (tid < 2 * RB / 16) *reinterpret_cast<u32x4 *>(zrow + 16 * tid) = u32x4{0u, 0u, 0u, 0u};
+    zero_rows<L>(zrow, tid);
 #pragma unroll
     for (int u = 0; u < NHI; ++u) issue_halo(u, 0);
     issue_weights(0, 0);
@@ -1040,6 +877,12 @@ __global__ __launch_bounds__(64 * WCO * WPIX, OCC) void k_conv3x3_pipe16(ConvArg
         const bool more = cc + 1 < nc;
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
+            // the issues are unconditional in every step (the last steps re-load
+            // the last weights into a buffer no later step reads; the fragments
+            // past the last step read stale LDS), so that the compiler's lgkmcnt /
+            // vmcnt counts stay exact; the order of reads and MFMAs is pinned:
+            // each part's reads go out a whole part of MFMAs ahead of their use
+            // (left alone, the compiler sinks them next to their MFMAs)
             const int t = 9 * cc + tap;
             const bool piece = NHB == 2 && more && tap < NHI;
             issue_weights(t + 2 < T ? t + 2 : T - 1, t + 2);
@@ -1079,8 +922,8 @@ __global__ __launch_bounds__(64 * WCO * WPIX, OCC) void k_conv3x3_pipe16(ConvArg
 // phase's halo is TI x (TR + 1) x Wo rows (output tile + one row above; no
 // padding columns: a tap left of the image reads a zero row), so each input pixel
 // is staged once per channel chunk — the gather kernel stages 2.25 per output
-// pixel per chunk, 9 B tiles.  k_conv3x3_pipe's machinery otherwise: 8-wave
-// blocks, LDS-DMA into swizzled 128-B rows, a 3-slot weight ring two steps ahead,
+// pixel per chunk, 9 B tiles.  The stride-1 pipeline's machinery otherwise, on
+// 32x32x16 MFMAs (two k-steps of 16 channels per step): 8-wave blocks, LDS-DMA into swizzled 128-B rows, a 3-slot weight ring two steps ahead,
 // two halo buffers (phase g + 1's rows go out in phase g's first step); the next
 // step's first fragments are read before the barrier within a phase, after it
 // across phases (the next phase's halo lands by the phase's end).  Reduction
@@ -1090,20 +933,12 @@ __device__ constexpr int kPhaseTap[9] = {0, 2, 6, 8, 1, 7, 3, 5, 4};  // step ->
 
 template <int WCO, int WPIX, int NHI>
 __global__ __launch_bounds__(64 * WCO * WPIX, 1) void k_conv3x3s2_phase(ConvArgs a) {
-    constexpr int NW = WCO * WPIX, NT = 64 * NW;
-    constexpr int BMC = kWaveTile * WCO, BNP = kWaveTile * WPIX;
-    constexpr int RB = 128;
-    constexpr int HROWS = 8 * NW * NHI;
-    constexpr int HB = HROWS * RB, AB = BMC * RB;
-    constexpr int NAI = BMC / (8 * NW);
-    constexpr int STAGE = 2 * HB + 3 * AB + 2 * RB;
-    constexpr int EPI = BNP * (4 * BMC + 16);
-    static_assert(BMC % (8 * NW) == 0 && NAI >= 1, "weight rows per wave");
-    static_assert(kBK == 32, "128-byte rows");
-    __shared__ __attribute__((aligned(16))) uint8_t smem[STAGE > EPI ? STAGE : EPI];
+    using L = PipeLds<WCO, WPIX, NHI, 2>;
+    constexpr int NW = L::NW, NT = L::NT, BMC = L::BMC, BNP = L::BNP, RB = L::RB, HB = L::HB, AB = L::AB;
+    __shared__ __attribute__((aligned(16))) uint8_t smem[L::BYTES];
     uint8_t *const hbuf0 = smem;
     uint8_t *const abuf0 = smem + 2 * HB;
-    uint8_t *const zrow = abuf0 + 3 * AB;  // two zero rows, read by parity (k_conv3x3_pipe)
+    uint8_t *const zrow = abuf0 + 3 * AB;
 
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int wc = wv / WPIX, wp = wv % WPIX;
@@ -1114,14 +949,7 @@ __global__ __launch_bounds__(64 * WCO * WPIX, 1) void k_conv3x3s2_phase(ConvArgs
     const int H = a.H, W = a.W, Ho = a.Ho, Wo = a.Wo, TR = a.TR;
     const int hrows_img = (TR + 1) * Wo;
     int b0, y0;
-    if (TR == Ho) {
-        b0 = pt * a.TI;
-        y0 = 0;
-    } else {
-        const int tpi = Ho / TR;
-        b0 = pt / tpi;
-        y0 = (pt - b0 * tpi) * TR;
-    }
+    tile_origin(pt, a.TI, TR, Ho, b0, y0);
 
     // halo DMA lane sources: the input pixel of phase (1,1) — (2q + 1, 2r + 1) —
     // or -1, and the piece; phase (a, b) reads (2q + a, 2r + b), 1 - a rows and
@@ -1142,21 +970,17 @@ __global__ __launch_bounds__(64 * WCO * WPIX, 1) void k_conv3x3s2_phase(ConvArgs
         hpix[u] = v;
         hpc[u] = sl ^ ((s >> 1) & 7);
     }
-    const uint16_t *zero = reinterpret_cast<const uint16_t *>(kZeroPiece);
-    asm volatile("" : "+s"(zero));
-    const uint16_t *asrc[NAI];
+    const uint16_t *zero = zero_piece();
+    const uint16_t *asrc[L::NAI];
 #pragma unroll
-    for (int u = 0; u < NAI; ++u) {
-        const int row = 8 * (wv * NAI + u) + lr;
+    for (int u = 0; u < L::NAI; ++u) {
+        const int row = 8 * (wv * L::NAI + u) + lr;
         const int p = sl ^ ((row >> 1) & 7);
         asrc[u] = a.w + (int64_t)(co0 + row) * (2 * a.K) + ((p & 4) ? a.K : 0) + 8 * (p & 3);
     }
-    auto issue_weights = [&](int step, int slot) {
+    auto issue_weights = [&](int step, int slot) {  // step's weights into ring slot slot % 3
         const int cc = step / 9, tap = kPhaseTap[step - 9 * cc];
-        const int kc = tap * a.C + cc * kBK;
-        uint8_t *dst = abuf0 + (slot % 3) * AB;
-#pragma unroll
-        for (int u = 0; u < NAI; ++u) glds16(asrc[u] + kc, dst + (wv * NAI + u) * 8 * RB);
+        issue_weight_ring<L>(asrc, tap * a.C + cc * kBK, abuf0, slot, wv);
     };
     // phase g = 4 cc + p (p: 0 = (1,1), 1 = (1,0), 2 = (0,1), 3 = (0,0)) into buffer g & 1
     auto issue_halo = [&](int g) {
@@ -1211,7 +1035,7 @@ __global__ __launch_bounds__(64 * WCO * WPIX, 1) void k_conv3x3s2_phase(ConvArgs
     WaveAcc acc;
     zero_acc(acc);
     const int nc = a.C / kBK, T = 9 * nc;
-    if (tid < 2 * RB / 16) *reinterpret_cast<u32x4 *>(zrow + 16 * tid) = u32x4{0u, 0u, 0u, 0u};
+    zero_rows<L>(zrow, tid);
     issue_halo(0);
     issue_weights(0, 0);
     issue_weights(T > 1 ? 1 : 0, 1);
@@ -1279,6 +1103,7 @@ constexpr int kStemWinRow = 40;  // floats per window row: image column ix at ix
 // NTL > 1 (XT): a block walks NTL consecutive pixel tiles with its A fragments
 // loaded once, the next tile's input window loaded into registers while this
 // tile is gathered, multiplied and stored; the same arithmetic per tile.
+constexpr int kStemTiles = 2;  // NTL of the CIFAR stem's launch
 template <int WPIX, int CIN = 0, int KHW = 0, bool XT = false, int NTL = 1>
 __global__ __launch_bounds__(64 * WPIX) void k_conv_stem(ConvArgs a, const float *__restrict__ x) {
     constexpr int NT = 64 * WPIX, BNP = kWaveTile * WPIX;
@@ -1391,7 +1216,7 @@ __global__ __launch_bounds__(64 * WPIX) void k_conv_stem(ConvArgs a, const float
         mfma_frag(acc, f[s]);
     }
     __syncthreads();  // the epilogue reuses the operands' LDS
-    epilogue_lds<kWaveTile, BNP, NT, 2, WaveAcc, DLS_STEM_PIXSPLIT>(acc, smem, a, co0, pix0, 0, wp, tid);
+    epilogue_lds<kWaveTile, BNP, NT, 2, WaveAcc, true>(acc, smem, a, co0, pix0, 0, wp, tid);
     }
 }
 
@@ -1497,11 +1322,33 @@ __global__ __launch_bounds__(kPoolBlock) void k_pool_linear(const uint16_t *__re
 // the query (dls_conv_kernel_choice).  Each fit_* fills the ConvArgs tile fields
 // (TI / TR / NH / pix_tiles / co_tiles) and returns whether its kernel takes
 // the shape.
+// A pixel tile of BNP pixels as whole rows of the tiled rows x cols image (cols
+// divides BNP): TR rows of one image (TR divides rows), or TI whole images
+bool tile_rows(int rows, int cols, int BNP, int &TI, int &TR) {
+    TR = rows < BNP / cols ? rows : BNP / cols;
+    TI = 1;
+    if (TR == rows) {
+        if (BNP % (rows * cols)) return false;
+        TI = BNP / (rows * cols);
+    } else if (rows % TR) {
+        return false;
+    }
+    return true;
+}
+
+// The common tail: the tile fields, and whether a grid holds the blocks
+bool finish_fit(ConvArgs &a, int TI, int TR, int NH, int BNP, int BMC) {
+    a.TI = TI;
+    a.TR = TR;
+    a.NH = NH;
+    a.pix_tiles = (a.M + BNP - 1) / BNP;
+    a.co_tiles = a.Cout / BMC;
+    return (int64_t)a.pix_tiles * a.co_tiles <= INT32_MAX;
+}
+
 template <int WCO, int WPIX>
 bool fit_generic(ConvArgs &a) {
-    a.pix_tiles = (a.M + kWaveTile * WPIX - 1) / (kWaveTile * WPIX);
-    a.co_tiles = a.Cout / (kWaveTile * WCO);
-    return (int64_t)a.pix_tiles * a.co_tiles <= INT32_MAX;
+    return finish_fit(a, 0, 0, 0, kWaveTile * WPIX, kWaveTile * WCO);
 }
 
 // The halo kernel when the pixel tile can be whole output rows
@@ -1510,23 +1357,11 @@ bool fit_halo(ConvArgs &a) {
     constexpr int BNP = kWaveTile * WPIX;
     constexpr int RPP = 64 * WCO * WPIX / (kBK / 4);
     const int H = a.H, W = a.W;
-    if (W > BNP || BNP % W) return false;
-    const int TR = H < BNP / W ? H : BNP / W;
-    int TI = 1;
-    if (TR == H) {
-        if (BNP % (H * W)) return false;
-        TI = BNP / (H * W);
-    } else if (H % TR) {
-        return false;
-    }
+    int TI, TR;
+    if (W > BNP || BNP % W || !tile_rows(H, W, BNP, TI, TR)) return false;
     const int NH = TI * (TR + 2) * (W + 2);
     if (NH > RPP * NHMAX) return false;
-    a.TI = TI;
-    a.TR = TR;
-    a.NH = NH;
-    a.pix_tiles = (a.M + BNP - 1) / BNP;
-    a.co_tiles = a.Cout / (kWaveTile * WCO);
-    return (int64_t)a.pix_tiles * a.co_tiles <= INT32_MAX;
+    return finish_fit(a, TI, TR, NH, BNP, kWaveTile * WCO);
 }
 
 // The stride-2 phase pipeline (k_conv3x3s2_phase) when its phase halos fit NHI
@@ -1537,51 +1372,47 @@ bool fit_phase(ConvArgs &a) {
     const int H = a.H, W = a.W, Ho = a.Ho, Wo = a.Wo;
     if ((H | W) & 1 || 2 * Ho != H || 2 * Wo != W || 32 % Wo || a.Cout % (kWaveTile * WCO)) return false;
     if ((int64_t)a.B * H * W >= (1ll << 30)) return false;  // input pixel indices in 32 bits
-    const int TR = Ho < BNP / Wo ? Ho : BNP / Wo;
-    int TI = 1;
-    if (TR == Ho) {
-        if (BNP % (Ho * Wo)) return false;
-        TI = BNP / (Ho * Wo);
-    } else if (Ho % TR) {
-        return false;
-    }
+    int TI, TR;
+    if (!tile_rows(Ho, Wo, BNP, TI, TR)) return false;
     if (TR * Wo >= 32 ? (TR * Wo) % 64 : 32 % (TR * Wo)) return false;
     const int NH = TI * (TR + 1) * Wo;
     if (NH > 8 * WCO * WPIX * NHI) return false;
-    a.TI = TI;
-    a.TR = TR;
-    a.NH = NH;
-    a.pix_tiles = (a.M + BNP - 1) / BNP;
-    a.co_tiles = a.Cout / (kWaveTile * WCO);
-    return (int64_t)a.pix_tiles * a.co_tiles <= INT32_MAX;
+    return finish_fit(a, TI, TR, NH, BNP, kWaveTile * WCO);
 }
 
-// The LDS-DMA pipeline (k_conv3x3_pipe, or k_conv3x3_pipe16 with DLS_CONV_MF16)
-// when the halo tile fits NHI DMAs per wave
+// The LDS-DMA pipeline (k_conv3x3_pipe16) when the halo tile fits NHI DMAs per
+// wave
 template <int WCO, int WPIX, int NHI>
 bool fit_pipe(ConvArgs &a) {
     constexpr int BNP = kWaveTile * WPIX;
     const int H = a.H, W = a.W;
-    if (32 % W) return false;  // a wave's two 32-pixel tiles share their columns
+    if (32 % W) return false;  // a wave's pixel tiles 32 apart share their columns
     if ((int64_t)a.B * H * W >= (1ll << 28)) return false;  // halo sources: input pixel * 8 + piece in 32 bits
-    const int TR = H < BNP / W ? H : BNP / W;
-    int TI = 1;
-    if (TR == H) {
-        if (BNP % (H * W)) return false;
-        TI = BNP / (H * W);
-    } else if (H % TR) {
-        return false;
-    }
-    // pixel tile 1 = tile 0 + 32 pixels in the same image tile, or whole images on
+    int TI, TR;
+    if (!tile_rows(H, W, BNP, TI, TR)) return false;
+    // pixel p + 32 lies in the same image tile, or whole images on
     if (TR * W >= 32 ? (TR * W) % 64 : 32 % (TR * W)) return false;
     const int NH = TI * (TR + 2) * W;  // halo rows without the padding columns
     if (NH > 8 * WCO * WPIX * NHI || a.Cout % (kWaveTile * WCO)) return false;
-    a.TI = TI;
-    a.TR = TR;
-    a.NH = NH;
-    a.pix_tiles = (a.M + BNP - 1) / BNP;
-    a.co_tiles = a.Cout / (kWaveTile * WCO);
-    return (int64_t)a.pix_tiles * a.co_tiles <= INT32_MAX;
+    return finish_fit(a, TI, TR, NH, BNP, kWaveTile * WCO);
+}
+
+// The kernel arguments of a checked shape with M output pixels, the tile fields
+// and the walk direction still zero
+ConvArgs make_conv_args(const uint16_t *x, const uint16_t *w, const float *consts, const uint16_t *res,
+                        uint16_t *y, int64_t B, int H, int W, int C, int Cout, int KH, int KW, int stride,
+                        int pad, int64_t M, int relu) {
+    ConvArgs a{};
+    a.x = x, a.w = w, a.consts = consts, a.res = res, a.y = y;
+    a.H = H, a.W = W, a.C = C, a.Cout = Cout, a.KW = KW, a.stride = stride, a.pad = pad;
+    a.Ho = (H + 2 * pad - KH) / stride + 1;
+    a.Wo = (W + 2 * pad - KW) / stride + 1;
+    a.taps = KH * KW;
+    a.K = KH * KW * C;
+    a.M = (int)M;
+    a.relu = relu ? 1 : 0;
+    a.B = (int)B;
+    return a;
 }
 
 // The shape checks of dls_conv_bn_act_split and its query: the output pixels in
@@ -1607,39 +1438,36 @@ int conv_check_shape(int64_t B, int32_t H, int32_t W, int32_t C, int32_t Cout, i
 // M > 0, its tile fields filled in; DLS_EINVAL if no grid holds its blocks.
 // The choice is a function of the shape alone (never of the process's
 // environment): a coalition's utility must be the same bits on every rank.
-// DLS_CONV_GENERIC_ONLY=1 (compile-time probe knob, tools/build_variants.py):
-// the generic kernel for every shape.
 int conv_choose(ConvArgs &a, int KH) {
     const int W = a.W, KW = a.KW;
     const bool wide = a.Cout % 128 == 0;
-    if (!DLS_CONV_GENERIC_ONLY && KH == 3 && KW == 3 && a.stride == 1 && a.pad == 1) {
+    if (KH == 3 && KW == 3 && a.stride == 1 && a.pad == 1) {
         // the LDS-DMA pipelines (profiles/r06_conv_pipe_ab.txt): 128-channel
         // multiples 16 wide in 64-channel 4-wave blocks of one whole 16x16 image
         // (no halo rows re-read, half the weight bytes per MFMA), else in
         // 128-channel 4-wave one-halo-buffer blocks two per CU on images at least
         // 16 wide, else in 8-wave double-buffered ones (8x8, 4x4); 64 channels in
         // 4-wave one-halo-buffer blocks (32x32)
-        const bool narrow = (W == 16 && (DLS_PIPE_NARROW & 1)) || (W == 8 && (DLS_PIPE_NARROW & 2)) ||
-                            (W == 4 && (DLS_PIPE_NARROW & 4));
-        if (DLS_CONV_PIPE && narrow) {
+        // (16 wide: -0.9 % per forward; 8 wide: null; 4 wide: +0.6 %,
+        // profiles/r06_forward_narrow_ab.txt)
+        const bool narrow = W == 16;
+        if (narrow) {
             if (fit_pipe<1, 4, 10>(a)) return DLS_CONV_KERNEL_PIPE64_H10;
             if (fit_pipe<1, 4, 12>(a)) return DLS_CONV_KERNEL_PIPE64_H12;
         }
-        if (DLS_CONV_PIPE && wide) {
+        if (wide) {
             if (W >= 16 && fit_pipe<2, 2, 5>(a)) return DLS_CONV_KERNEL_PIPE128_W4;
             if (fit_pipe<2, 4, 5>(a)) return DLS_CONV_KERNEL_PIPE128_W8_H5;
             if (fit_pipe<2, 4, 6>(a)) return DLS_CONV_KERNEL_PIPE128_W8_H6;
         }
-        if (DLS_CONV_PIPE && !wide && fit_pipe<1, 4, 10>(a)) return DLS_CONV_KERNEL_PIPE64_H10;
+        if (!wide && fit_pipe<1, 4, 10>(a)) return DLS_CONV_KERNEL_PIPE64_H10;
         const bool skew = W <= 16;
         if (wide ? fit_halo<2, 2, 9>(a) : fit_halo<1, 4, 11>(a))
             return wide ? (skew ? DLS_CONV_KERNEL_HALO128_SKEW : DLS_CONV_KERNEL_HALO128)
                         : (skew ? DLS_CONV_KERNEL_HALO64_SKEW : DLS_CONV_KERNEL_HALO64);
     }
-    if (DLS_CONV_PHASE && !DLS_CONV_GENERIC_ONLY && KH == 3 && KW == 3 && a.stride == 2 && a.pad == 1 && wide &&
-        fit_phase<2, 4, 5>(a))
+    if (KH == 3 && KW == 3 && a.stride == 2 && a.pad == 1 && wide && fit_phase<2, 4, 5>(a))
         return DLS_CONV_KERNEL_PHASE;
-    a.TI = a.TR = a.NH = 0;
     if (!(wide ? fit_generic<2, 2>(a) : fit_generic<1, 4>(a))) {
         set_error("dls_conv_bn_act_split: %lld blocks", (long long)a.pix_tiles * a.co_tiles);
         return DLS_EINVAL;
@@ -1677,17 +1505,13 @@ void launch_phase(const ConvArgs &a, hipStream_t st) {
 
 template <int WCO, int WPIX, int NHI, int NHB = 2, int OCC = 1>
 void launch_pipe(const ConvArgs &a, hipStream_t st) {
-    if (DLS_CONV_MF16)
-        hipLaunchKernelGGL((k_conv3x3_pipe16<WCO, WPIX, NHI, NHB, OCC>), dim3(conv_blocks(a)),
-                           dim3(64 * WCO * WPIX), 0, st, a);
-    else
-        hipLaunchKernelGGL((k_conv3x3_pipe<WCO, WPIX, NHI, NHB, OCC>), dim3(conv_blocks(a)),
-                           dim3(64 * WCO * WPIX), 0, st, a);
+    hipLaunchKernelGGL((k_conv3x3_pipe16<WCO, WPIX, NHI, NHB, OCC>), dim3(conv_blocks(a)),
+                       dim3(64 * WCO * WPIX), 0, st, a);
 }
 
 // The stem's kernel (DLS_STEM_KERNEL_*) of a checked shape
 int stem_choose(int C, int H, int W, int KH, int KW, int stride, int pad) {
-    if (DLS_STEM_WINDOW && C == 3 && KH == 3 && KW == 3 && stride == 1 && pad == 1 && W == 32 && H % 8 == 0)
+    if (C == 3 && KH == 3 && KW == 3 && stride == 1 && pad == 1 && W == 32 && H % 8 == 0)
         return DLS_STEM_KERNEL_WINDOW;
     return C == 3 && KH == 3 && KW == 3 ? DLS_STEM_KERNEL_3X3 : DLS_STEM_KERNEL_GENERIC;
 }
@@ -1725,7 +1549,6 @@ struct WalkMemo {
 WalkMemo g_walk;
 
 int conv_walk_direction(const void *x) {
-    if (!DLS_CONV_SERPENTINE) return 0;
     std::lock_guard<std::mutex> g(g_walk.m);
     for (int i = 0; i < 16; ++i)
         if (g_walk.ptr[i] == x) return !g_walk.dir[i];
@@ -1733,7 +1556,6 @@ int conv_walk_direction(const void *x) {
 }
 
 void conv_record_walk(const void *y, int dir) {
-    if (!DLS_CONV_SERPENTINE) return;
     std::lock_guard<std::mutex> g(g_walk.m);
     for (int i = 0; i < 16; ++i)
         if (g_walk.ptr[i] == y) {
@@ -1821,10 +1643,7 @@ int dls_conv_bn_act_split(const uint16_t *x, int64_t B, int32_t H, int32_t W, in
                     (!residual || aligned16(residual)),
                 DLS_ELAYOUT, "dls_conv_bn_act_split: 16-byte alignment");
     if (M == 0) return DLS_OK;
-    const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
-    ConvArgs a{x, w, consts, residual, y, (int)H, (int)W, (int)C, Ho, Wo, (int)Cout, (int)KW,
-               (int)(KH * KW), (int)stride, (int)pad, (int)(KH * KW * C), (int)M, relu ? 1 : 0, 0, 0,
-               (int)B, 0, 0, 0};
+    ConvArgs a = make_conv_args(x, w, consts, residual, y, B, H, W, C, Cout, KH, KW, stride, pad, M, relu);
     const int id = conv_choose(a, KH);
     if (id < 0) return id;
     a.rev = conv_walk_direction(x);
@@ -1852,10 +1671,8 @@ int dls_conv_kernel_choice(int64_t B, int32_t H, int32_t W, int32_t C, int32_t C
     int64_t M = 0;
     if (const int rc = conv_check_shape(B, H, W, C, Cout, KH, KW, stride, pad, M)) return rc;
     if (M == 0) return DLS_CONV_KERNEL_NONE;
-    const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
-    ConvArgs a{nullptr, nullptr, nullptr, nullptr, nullptr, (int)H, (int)W, (int)C, Ho, Wo, (int)Cout,
-               (int)KW, (int)(KH * KW), (int)stride, (int)pad, (int)(KH * KW * C), (int)M, 0, 0, 0,
-               (int)B, 0, 0, 0};
+    ConvArgs a = make_conv_args(nullptr, nullptr, nullptr, nullptr, nullptr, B, H, W, C, Cout, KH, KW, stride,
+                                pad, M, 0);
     return conv_choose(a, KH);
 }
 
@@ -1869,18 +1686,17 @@ int dls_conv_stem_bn_act_f32(const float *x, int64_t B, int32_t C, int32_t H, in
     DLS_REQUIRE(aligned16(w) && aligned16(y) && (!consts || aligned16(consts)), DLS_ELAYOUT,
                 "dls_conv_stem_bn_act_f32: 16-byte alignment");
     if (M == 0) return DLS_OK;
-    const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
     constexpr int WPIX = 4;  // stem_check_shape's pixel tiles: 64 * WPIX pixels
-    ConvArgs a{nullptr, w, consts, nullptr, y, (int)H, (int)W, (int)C, Ho, Wo, (int)Cout, (int)KW,
-               (int)(KH * KW), (int)stride, (int)pad, kBK, (int)M, relu ? 1 : 0, 0, 0, (int)B, 0, 0, 0};
+    ConvArgs a = make_conv_args(nullptr, w, consts, nullptr, y, B, H, W, C, Cout, KH, KW, stride, pad, M, relu);
+    a.K = kBK;  // the im2col weights' row (dls_conv_pack_weights_im2col_f32 with Kp = kBK)
     conv_record_walk(y, 0);  // the stem walks forwards; the next layer backwards
     a.pix_tiles = pix_tiles;
     a.co_tiles = co_tiles;
     const int64_t blocks = (int64_t)a.pix_tiles * a.co_tiles;
     switch (stem_choose(C, H, W, KH, KW, stride, pad)) {
     case DLS_STEM_KERNEL_WINDOW: {
-        // the CIFAR ResNet stem, window staged in LDS, DLS_STEM_TILES pixel tiles per block
-        constexpr int NTL = DLS_STEM_TILES;
+        // the CIFAR ResNet stem, window staged in LDS, kStemTiles pixel tiles per block
+        constexpr int NTL = kStemTiles;
         const int64_t walks = (int64_t)((a.pix_tiles + NTL - 1) / NTL) * a.co_tiles;
         hipLaunchKernelGGL((k_conv_stem<WPIX, 3, 3, true, NTL>), dim3((unsigned)walks), dim3(64 * WPIX), 0,
                            as_stream(stream), a, x);

@@ -199,12 +199,6 @@ constexpr int kQuantPieceWps = DLS_QUANT_PIECE_WPS;
 #define DLS_QUANT_NTSTORE 0  // 1: non-temporal output stores in store_tile (A/B knob)
 #endif
 
-#ifndef DLS_QUANT_PROBE
-#define DLS_QUANT_PROBE 0  // 1: stream-only timing probe (loads + a xor per dword; wrong output)
-// 2: as 1, and lane_tile skips its per-chunk scale staging (no sz gathers, LDS table, ballot)
-// 3: as 2, and lane_tile addresses client j of a chunk as row base + j (no v_readlane)
-#endif
-
 template <int U, int GN>
 struct QBatch {
     u32x4 qv[U][GN];
@@ -636,18 +630,18 @@ __device__ __forceinline__ void lane_tile(const WaveTile &wt, const uint8_t *__r
     ChunkRows cr;
     cr.init(rows, w, K);
     f32x2 nsz[kSpanMax];
-    if (staged && DLS_QUANT_PROBE < 2) tab_load(cr.r0, nsz);
+    if (staged) tab_load(cr.r0, nsz);
     for (int base = 0; base < K; base += 64) {
         const int tr = cr.r0;
         const float tw = cr.w0;
         f32x2 tsz[kSpanMax];
 #pragma unroll
         for (int c = 0; c < kSpanMax; ++c) tsz[c] = nsz[c];
-        if (staged && DLS_QUANT_PROBE < 2) tab_load(cr.r1, nsz);  // next chunk (its rows landed a chunk ago)
+        if (staged) tab_load(cr.r1, nsz);  // next chunk (its rows landed a chunk ago)
         cr.advance(rows, w, K, base);
         const int n = min(64, K - base);
-        bool allfast = DLS_QUANT_PROBE >= 2;
-        if (staged && DLS_QUANT_PROBE < 2) {
+        bool allfast = false;
+        if (staged) {
             // every (client, channel) of the chunk on the common path: exact fl(z*s)
             // and the fast division range (always, for symmetric int8)
             int ok = d.fast;
@@ -662,25 +656,19 @@ __device__ __forceinline__ void lane_tile(const WaveTile &wt, const uint8_t *__r
         }
         if (allfast) {
             auto sfetch = [&](int j, SOne &b) {
-                const int64_t r = DLS_QUANT_PROBE >= 3 ? (int64_t)(base + j) : readlane_i(tr, j);
+                const int64_t r = readlane_i(tr, j);
                 const auto rs = __builtin_amdgcn_make_buffer_rsrc(
                     const_cast<uint8_t *>(Q + r * ldq), 0, (int)0xffffffffu, 0x00020000);  // 4 GiB
 #pragma unroll
                 for (int g = 0; g < G; ++g)
                     b.qv[g] = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)qoff[g], 0, 2 /* nt */);
-                b.wk = DLS_QUANT_PROBE >= 3 ? 1.f : readlane_f(tw, j);
+                b.wk = readlane_f(tw, j);
                 b.j = j;
             };
             auto sstep = [&](const SOne &b) {
                 // the lane's (s, -zs): a broadcast LDS read (<= kSpanMax addresses per wave)
 #pragma unroll
-                for (int g = 0; g < G; ++g) {
-                    if constexpr (DLS_QUANT_PROBE >= 1)
-                        acc[g][g] += __uint_as_float((b.qv[g].x ^ b.qv[g].y ^ b.qv[g].z ^ b.qv[g].w) &
-                                                     0x3fffffffu);
-                    else
-                        accum16_pk<SIGNED, TWO>(acc[g], b.qv[g], tab[0][toff[g] + b.j], b.wk, d);
-                }
+                for (int g = 0; g < G; ++g) accum16_pk<SIGNED, TWO>(acc[g], b.qv[g], tab[0][toff[g] + b.j], b.wk, d);
             };
             chunk_pipeline_1tail<US, SBatch>(
                 n,
@@ -989,13 +977,7 @@ __device__ __forceinline__ void fma_lane_tile(const WaveTile &wt, const uint8_t 
         };
         auto sstep = [&](const SOne &b) {
 #pragma unroll
-            for (int g = 0; g < G; ++g) {
-                if constexpr (DLS_QUANT_PROBE == 1)
-                    acc[g][g] += __uint_as_float((b.qv[g].x ^ b.qv[g].y ^ b.qv[g].z ^ b.qv[g].w) &
-                                                 0x3fffffffu);
-                else
-                    accum16_fmaz<SIGNED>(acc[g], b.qv[g], tab[0][toff[g] + b.j]);
-            }
+            for (int g = 0; g < G; ++g) accum16_fmaz<SIGNED>(acc[g], b.qv[g], tab[0][toff[g] + b.j]);
         };
         chunk_pipeline_1tail<US, SBatch>(
             n,

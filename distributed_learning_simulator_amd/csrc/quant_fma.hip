@@ -85,9 +85,6 @@ constexpr int kFmaWps = DLS_FMA_WPS;  // waves per SIMD per launch piece
 #ifndef DLS_FMA_F32U
 #define DLS_FMA_F32U 16  // clients per batch of the fp32 side walk (two batches in flight)
 #endif
-#ifndef DLS_FMA_PROBE
-#define DLS_FMA_PROBE 0  // 1: stream-only timing probe (loads + a xor per dword; wrong output)
-#endif
 
 // The tile order: segment s (widest tiles first: table groups 0, 4, 1, 5, 2, 6,
 // 3, 7) holds indices [cum[s], cum[s+1]), table indices start[s] + i.
@@ -288,13 +285,7 @@ __device__ __forceinline__ void fma_tile(const dls_qtile &t, const FmaCall &a, i
                     if ((kk & 63) == 0) chunk_start(kk);
                 const int j = kk & 63;
 #pragma unroll
-                for (int g = 0; g < G; ++g) {
-                    if constexpr (DLS_FMA_PROBE == 1)
-                        acc[g][g] += __uint_as_float(
-                            (slot[u][g].x ^ slot[u][g].y ^ slot[u][g].z ^ slot[u][g].w) & 0x3fffffffu);
-                    else
-                        fma16<SIGNED>(acc[g], slot[u][g], tab[0][toff[g] + j]);
-                }
+                for (int g = 0; g < G; ++g) fma16<SIGNED>(acc[g], slot[u][g], tab[0][toff[g] + j]);
                 const int f = kk + D, cb = kk & ~63;  // f < cb + 128: in chunk cb or the next
                 fetch(slot[u], f - cb < 64 ? readlane_i(r0, f & 63) : readlane_i(r1, f & 63));
             }

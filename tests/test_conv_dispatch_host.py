@@ -55,6 +55,21 @@ def test_reachability_sweep(sweep):
     assert not set(sweep) & UNREACHABLE
 
 
+def test_whole_dispatch_table_is_pinned():
+    """Every id of the sweep, in the sweep's order, one byte each: the table a
+    refactor of conv_choose / fit_* must reproduce (131,072 shapes; the digest is
+    of the table the library gave before the probe knobs were folded in)."""
+    import hashlib
+    f = _native.lib().dls_conv_kernel_choice
+    table = bytes(f(B, H, W, 32, co, 3, 3, s, 1) for s in (1, 2) for H in range(1, 129)
+                  for W in range(1, 129) for co in (64, 128) for B in (1, 3))
+    assert len(table) == 131072
+    counts = {i: table.count(i) for i in set(table)}
+    assert counts == {1: 65448, 2: 65188, 3: 104, 4: 4, 5: 14, 6: 68, 7: 8, 8: 160, 9: 16, 12: 62}
+    assert hashlib.sha256(table).hexdigest() == \
+        "78db64fde289234d8d1c1dd7e7fa8518bcf2c31f72f6ff24cf947c24a93031fa"
+
+
 def test_halo_forms_are_reached_where_the_fit_rules_say():
     assert choice(1, 64, 64, 32, 128) == HALO128        # 32 % 64: no pipeline
     assert choice(2, 12, 32, 32, 128) == HALO128        # the pipelines refuse H % TR or the halo's size
@@ -72,7 +87,8 @@ def test_choice_does_not_depend_on_history_or_environment():
     first = [choice(*t) for t in shapes]
     assert [choice(*t) for t in reversed(shapes)] == first[::-1]
     assert [choice(*t) for t in shapes for _ in range(2)] == [i for i in first for _ in range(2)]
-    # a fresh process with another environment (the library reads none)
+    # a fresh process with another environment (the library reads none; the
+    # variables carry the names of compile-time knobs the dispatch once had)
     code = ("from distributed_learning_simulator_amd import _native as n;"
             f"print([n.conv_kernel_choice(t[0],t[1],t[2],t[3],t[4],(t[5],t[5]),t[6],t[7]) for t in {shapes!r}])")
     env = dict(os.environ, DLS_CONV_GENERIC_ONLY="1", DLS_CONV_PIPE="0", DLS_PIPE_NARROW="7", HIP_VISIBLE_DEVICES="")
