@@ -67,6 +67,9 @@ SIGNATURES = {
     "dls_trimmed_mean_f32": ([_p, _i64, _p, _i32, _i32, _i64, _p, _p], _i32),
     "dls_pairwise_sqdist_workspace": ([_i32, _i64], _i64),
     "dls_pairwise_sqdist_f32": ([_p, _i64, _p, _i32, _i64, _p, _p, _p], _i32),
+    "dls_weiszfeld_workspace": ([_i32, _i64], _i64),
+    "dls_rows_sqdist_to_f32": ([_p, _i64, _p, _i32, _i64, _p, _p, _p, _p], _i32),
+    "dls_weiszfeld_step_f32": ([_p, _i64, _p, _i32, _p, _i64, _p, _p, _p, _p], _i32),
     "dls_subset_gemm_f32": ([_p, _i32, _i32, _p, _i64, _p, _i64, _p, _i64, _p], _i32),
     "dls_sign_pack_f32": ([_p, _i64, _i32, _i64, _p, _i64, _p, _p], _i32),
     "dls_sign_vote_count": ([_p, _i64, _p, _i32, _i64, _p, _p], _i32),
@@ -154,7 +157,7 @@ def _stream(stream=None, like=None):
 
 
 CSRC_HASHED = ["dls_runtime.hip", "fedavg.hip", "sign.hip", "quant.hip", "quant_fma.hip", "shapley.hip",
-               "infer.hip", "conv.hip", "lenet.hip", "loss.hip", "robust.hip", "pairdist.hip", "dls_common.h", "quant_common.h",
+               "infer.hip", "conv.hip", "lenet.hip", "loss.hip", "robust.hip", "pairdist.hip", "weiszfeld.hip", "dls_common.h", "quant_common.h",
                "loss_common.h", os.path.join("..", "..", "include", "dls_hip.h")]
 
 
@@ -275,6 +278,100 @@ def pairwise_sqdist(U, rows, P, out=None, stream=None):
     if stream is not None:
         work.record_stream(stream)
     return out
+
+
+def _rows_operands(fn, U, rows, P):
+    """The checks of pairwise_sqdist on (U, rows, P): returns (K, P, ldu)."""
+    if (not torch.is_tensor(U) or U.dtype != torch.float32 or U.dim() != 2
+            or (U.shape[1] > 1 and U.stride(1) != 1)):
+        raise RuntimeError(f"{fn}: U must be an fp32 [rows, ld] matrix with unit element stride")
+    if not torch.is_tensor(rows) or rows.dtype != torch.int32 or rows.dim() != 1 \
+            or not rows.is_contiguous():
+        raise RuntimeError(f"{fn}: rows must be a contiguous int32 [K] tensor")
+    K = rows.numel()
+    if not 1 <= K <= ROBUST_MAX_K:
+        raise RuntimeError(f"{fn}: K={K} rows (1..ROBUST_MAX_K={ROBUST_MAX_K})")
+    P = int(P)
+    if P < 0 or P % 4 != 0 or P > U.shape[1]:
+        raise RuntimeError(f"{fn}: P={P} must be a multiple of 4 and at most the row "
+                           f"length {U.shape[1]}")
+    ldu = U.stride(0) if U.shape[0] > 1 else U.shape[1]
+    if ldu % 4 != 0 or ldu < P:
+        raise RuntimeError(f"{fn}: row pitch {ldu} must be a multiple of 4, at least P")
+    return K, P, ldu
+
+
+def _point_operands(fn, U, K, P, z, dist2, name):
+    """z: an fp32 vector of at least P elements; dist2: None or a contiguous fp64 [K]
+    tensor (``name`` in messages).  Returns dist2 (a new tensor when None)."""
+    if (not torch.is_tensor(z) or z.dtype != torch.float32 or z.dim() != 1
+            or z.numel() < P or (z.numel() > 1 and z.stride(0) != 1)):
+        raise RuntimeError(f"{fn}: z must be an fp32 vector of at least P={P} elements "
+                           "with unit stride")
+    if dist2 is not None and (not torch.is_tensor(dist2) or dist2.dtype != torch.float64
+                              or tuple(dist2.shape) != (K,) or not dist2.is_contiguous()):
+        raise RuntimeError(f"{fn}: {name} must be a contiguous fp64 [K] = [{K}] tensor")
+    return dist2
+
+
+def _weiszfeld_work(K, P, device):
+    nbytes = int(lib().dls_weiszfeld_workspace(K, P))
+    if nbytes < 0:
+        _check(nbytes, "dls_weiszfeld_workspace")
+    return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+
+
+def rows_sqdist_to(U, rows, P, z, out=None, stream=None):
+    """Squared Euclidean distances of the K = rows.numel() selected rows of U to the
+    point z over their first P elements (dls_rows_sqdist_to_f32): an fp64 [K] device
+    tensor, each entry within 2^-17 relative of the exact squared distance of the fp32
+    operands; a row equal to z gives +0.0, rows of equal contents equal bits, a row
+    that holds inf or NaN +inf or NaN (the other rows are unaffected).  U, rows, P as
+    in pairwise_sqdist; z: fp32, at least P elements; out: a contiguous fp64 [K]
+    tensor (default: a new one)."""
+    fn = "rows_sqdist_to"
+    K, P, ldu = _rows_operands(fn, U, rows, P)
+    out = _point_operands(fn, U, K, P, z, out, "out")
+    _check_same_device(fn, U, rows=rows, z=z, out=out)
+    if U.data_ptr() % 16 != 0 or z.data_ptr() % 16 != 0:
+        raise RuntimeError(f"{fn}: U and z must be 16-byte aligned")
+    if out is None:
+        out = torch.empty((K,), dtype=torch.float64, device=U.device)
+    _ptr(U), _ptr(rows), _ptr(z), _ptr(out)  # no CPU path
+    work = _weiszfeld_work(K, P, U.device)
+    _check(lib().dls_rows_sqdist_to_f32(_ptr(U), ldu, _ptr(rows), K, P, _ptr(z), _ptr(out),
+                                        _ptr(work), _stream(stream, U)), "dls_rows_sqdist_to_f32")
+    if stream is not None:
+        work.record_stream(stream)
+    return out
+
+
+def weiszfeld_step(U, rows, w, P, z, dist2=None, stream=None):
+    """One fused Weiszfeld step (dls_weiszfeld_step_f32): z[:P] = sum_k fl32(w[k] *
+    U[rows[k]]) - multiply, then add in the order of ``rows``, every operation rounded
+    once, so z is defined bit for bit by the bits of w - and the squared distances of
+    the rows to that new z (as rows_sqdist_to) from the same read of the rows.  The
+    old contents of z are never read.  w: a contiguous fp32 [K] tensor; the rest as in
+    rows_sqdist_to.  Returns (z, dist2)."""
+    fn = "weiszfeld_step"
+    K, P, ldu = _rows_operands(fn, U, rows, P)
+    if (not torch.is_tensor(w) or w.dtype != torch.float32 or tuple(w.shape) != (K,)
+            or not w.is_contiguous()):
+        raise RuntimeError(f"{fn}: w must be a contiguous fp32 [K] = [{K}] tensor")
+    dist2 = _point_operands(fn, U, K, P, z, dist2, "dist2")
+    _check_same_device(fn, U, rows=rows, w=w, z=z, dist2=dist2)
+    if U.data_ptr() % 16 != 0 or z.data_ptr() % 16 != 0:
+        raise RuntimeError(f"{fn}: U and z must be 16-byte aligned")
+    if dist2 is None:
+        dist2 = torch.empty((K,), dtype=torch.float64, device=U.device)
+    _ptr(U), _ptr(rows), _ptr(w), _ptr(z), _ptr(dist2)  # no CPU path
+    work = _weiszfeld_work(K, P, U.device)
+    _check(lib().dls_weiszfeld_step_f32(_ptr(U), ldu, _ptr(rows), K, _ptr(w), P, _ptr(z),
+                                        _ptr(dist2), _ptr(work), _stream(stream, U)),
+           "dls_weiszfeld_step_f32")
+    if stream is not None:
+        work.record_stream(stream)
+    return z, dist2
 
 
 def subset_fedavg(U, sub_off, sub_rows, sub_weight, sub_total, P, out, stream=None):

@@ -113,6 +113,31 @@ def multi_krum_select(D, ids, byzantine, select):
     return [ids[i] for i in order[:m]], scores
 
 
+def weiszfeld_weights(dist2, nu):
+    """The weights of one smoothed Weiszfeld step (Pillutla et al., RFA) from the
+    squared distances of the clients to the current iterate, on the host in fp64:
+    (kept_indices, weights).
+
+    Indices whose ``dist2`` is non-finite or negative are dropped.  For the others
+    beta_i = 1 / max(nu, sqrt(dist2_i)), S = the sum of the beta_i in ascending index
+    order, and weights[j] = float32(beta_i / S) (a Python float holding the fp32
+    value) for the j-th kept index i.  ValueError: nothing is kept, or ``nu`` is not
+    a positive finite number."""
+    if isinstance(nu, bool) or not isinstance(nu, (int, float)) or not math.isfinite(nu) \
+            or nu <= 0:
+        raise ValueError(f"nu must be a positive finite number, not {nu!r}")
+    nu = float(nu)
+    d2 = [float(v) for v in dist2]
+    kept = [i for i, v in enumerate(d2) if math.isfinite(v) and v >= 0.0]
+    if not kept:
+        raise ValueError(f"no client has a finite distance (0 of {len(d2)})")
+    beta = [1.0 / max(nu, math.sqrt(d2[i])) for i in kept]
+    total = 0.0
+    for b in beta:
+        total += b
+    return kept, torch.tensor([b / total for b in beta], dtype=torch.float64).float().tolist()
+
+
 class ClientUpdateStore:
     """``acquire_range = (lo, hi)``: this process's own clients take rows [lo, hi)
     only (a fixed block; the sharded Shapley servers all-gather every rank's block
@@ -223,6 +248,68 @@ class ClientUpdateStore:
         row_of = dict(zip(ids, rows))
         flat = self.trimmed_mean([row_of[i] for i in selected], 0, out=out)
         return flat, selected, scores
+
+    def sqdist_to(self, rows, point, cols=None):
+        """Squared Euclidean distances of the given rows to ``point`` (an fp32 device
+        vector of the reduced length; dls_rows_sqdist_to_f32): an fp64 [K] device
+        tensor.  K <= _native.ROBUST_MAX_K; ``cols`` as in ``fedavg``."""
+        c0, c1 = cols if cols is not None else (0, self.layout.P)
+        r = rows if torch.is_tensor(rows) else _i32(rows, self.device)
+        return _native.rows_sqdist_to(self.U[:, c0:], r, c1 - c0, point)
+
+    def geometric_median(self, rows, ids, iters, nu, out=None, trace=False):
+        """The geometric median of the given rows (client ``ids[i]`` in ``rows[i]``) by
+        ``iters`` smoothed Weiszfeld steps (RFA, Pillutla et al.) from the coordinate-wise
+        median: the clients are taken in id order (distinct, sortable ids), so the
+        result is the same bits for any arrival order.  One distance pass against the
+        start, then per step ``weiszfeld_weights`` on the host, one fused
+        ``dls_weiszfeld_step_f32`` into ``out`` and one copy of K doubles to the host.  A
+        client whose distance is not finite after any pass is rejected for the rest of
+        the call; ValueError when none is left.  Returns (flat, info): ``distances``
+        {id: distance to the returned aggregate}, ``rejected`` (sorted ids),
+        ``objective`` (the sum of distances after the start and after each step, added
+        in id order) and, with ``trace``, per pass the (ids, fp32 weights or None,
+        dist2) the pass ran on and gave."""
+        iters = int(iters)
+        if iters < 1:
+            raise ValueError(f"iters={iters} must be at least 1")
+        ids = list(ids)
+        if len(set(ids)) != len(ids) or len(ids) != len(rows):
+            raise ValueError("geometric_median needs one distinct id per row")
+        active = sorted(zip(ids, (int(r) for r in rows)))
+        K, P = len(active), self.layout.P
+        flat = self.median([r for _, r in active], out=out)
+        info = {"distances": {}, "rejected": [], "objective": []}
+        passes = []
+
+        def settle(weights, d2):
+            """Book one pass's distances; the clients that go on."""
+            if trace:
+                passes.append(([i for i, _ in active], weights, list(d2)))
+            good = [k for k, v in enumerate(d2) if math.isfinite(v) and v >= 0.0]
+            info["rejected"] = sorted(info["rejected"]
+                                      + [active[k][0] for k in range(len(d2)) if k not in good])
+            if not good:
+                raise ValueError(f"geometric_median: no client is at a finite distance from the "
+                                 f"iterate after pass {len(info['objective'])} "
+                                 f"({K - len(info['rejected'])} of {K} finite)")
+            obj = 0.0
+            for k in good:
+                obj += math.sqrt(d2[k])
+            info["objective"].append(obj)
+            return [active[k] for k in good], [d2[k] for k in good]
+
+        d2 = self.sqdist_to([r for _, r in active], flat).cpu().tolist()
+        active, d2 = settle(None, d2)
+        for _ in range(iters):
+            _, weights = weiszfeld_weights(d2, nu)
+            _, dist2 = _native.weiszfeld_step(self.U, _i32([r for _, r in active], self.device),
+                                              _f32(weights, self.device), P, flat)
+            active, d2 = settle(weights, dist2.cpu().tolist())
+        info["distances"] = {i: math.sqrt(v) for (i, _), v in zip(active, d2)}
+        if trace:
+            info["trace"] = passes
+        return flat, info
 
     def subset_models(self, subsets, n_of_row, method="exact", out=None):
         """S subset models at once.  subsets: list of row lists (non-empty, in order)."""

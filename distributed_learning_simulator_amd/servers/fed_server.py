@@ -6,6 +6,7 @@ loop of K x (#tensors) torch ops, bit-exact with the reference's op order.
 """
 import copy
 import logging
+import math
 
 from .. import _native
 from ..aggregation import ClientParameters, ClientUpdateStore
@@ -17,7 +18,8 @@ from .server import Server
 log = logging.getLogger("distributed_learning_simulator_amd")
 
 _MODES = {"exact": _native.FEDAVG_EXACT, "fma": _native.FEDAVG_FMA}
-_RULES = ("mean", "median", "trimmed_mean", "multi_krum")
+_RULES = ("mean", "median", "trimmed_mean", "multi_krum", "geometric_median")
+_GM_ITERS, _GM_NU = 3, 1e-6  # the defaults of RFA (Pillutla et al.)
 
 
 class FedServer(Server):
@@ -34,7 +36,14 @@ class FedServer(Server):
       (dls_pairwise_sqdist_f32) and the ``krum_select`` best-scored ones (default
       K - ``byzantine``) are averaged unweighted (Blanchard et al. 2017);
       ``krum_select=1`` is classic Krum.  ``last_selection`` / ``last_scores``
-      hold the latest choice.
+      hold the latest choice;
+    * ``"geometric_median"``: the point that minimises the sum of Euclidean
+      distances to the updates, by ``gm_iters`` smoothed Weiszfeld steps
+      (smoothing ``gm_nu``, in the units of the parameters) from the coordinate-wise
+      median (RFA, Pillutla et al.; dls_weiszfeld_step_f32): an outlier is
+      down-weighted by 1 / distance instead of dropped, a client with a non-finite
+      update is rejected.  ``last_distances`` / ``last_rejected`` hold the latest
+      call's distances to the aggregate and rejected workers.
 
     The robust rules ignore the clients' sample counts n_i (every client counts
     once), take at most ``_native.ROBUST_MAX_K`` clients and are bit-identical for
@@ -45,11 +54,11 @@ class FedServer(Server):
     _robust_unsupported = None
 
     def __init__(self, aggregation_mode="exact", aggregation_rule="mean", trim=0, byzantine=0,
-                 krum_select=None, **kwargs):
+                 krum_select=None, gm_iters=_GM_ITERS, gm_nu=_GM_NU, **kwargs):
         if aggregation_mode not in _MODES:
             raise ValueError(f"aggregation_mode must be one of {sorted(_MODES)}, not {aggregation_mode!r}")
         self._check_rule(aggregation_rule, trim, aggregation_mode, kwargs.get("worker_number"),
-                         byzantine, krum_select)
+                         byzantine, krum_select, gm_iters, gm_nu)
         super().__init__(**kwargs)
         _native.require_gpu()
         self.round = 0
@@ -60,6 +69,10 @@ class FedServer(Server):
         self.krum_select = None if krum_select is None else int(krum_select)
         self.last_selection = ()
         self.last_scores = {}
+        self.gm_iters = gm_iters
+        self.gm_nu = float(gm_nu)
+        self.last_distances = {}
+        self.last_rejected = ()
         self.parameters: ClientParameters = ClientParameters(self._make_store)
         self.__prev_model = copy.deepcopy(
             ModelUtil(self.tester.model).get_parameter_dict()) if self.tester is not None else {}
@@ -67,7 +80,8 @@ class FedServer(Server):
             RepeatedResult(data=self.prev_model, num=self.clients_per_round))
 
     @classmethod
-    def _check_rule(cls, rule, trim, mode, worker_number, byzantine=0, krum_select=None):
+    def _check_rule(cls, rule, trim, mode, worker_number, byzantine=0, krum_select=None,
+                    gm_iters=_GM_ITERS, gm_nu=_GM_NU):
         if rule not in _RULES:
             raise ValueError(f"aggregation_rule must be one of {list(_RULES)}, not {rule!r}")
         if isinstance(trim, bool) or not isinstance(trim, int) or trim < 0:
@@ -82,6 +96,14 @@ class FedServer(Server):
         if rule != "multi_krum" and (byzantine != 0 or krum_select is not None):
             raise ValueError(f"byzantine={byzantine} / krum_select={krum_select} needs "
                              f"aggregation_rule='multi_krum', not {rule!r}")
+        if isinstance(gm_iters, bool) or not isinstance(gm_iters, int) or gm_iters < 1:
+            raise ValueError(f"gm_iters must be a positive integer, not {gm_iters!r}")
+        if (isinstance(gm_nu, bool) or not isinstance(gm_nu, (int, float))
+                or not math.isfinite(gm_nu) or gm_nu <= 0):
+            raise ValueError(f"gm_nu must be a positive finite number, not {gm_nu!r}")
+        if rule != "geometric_median" and (gm_iters != _GM_ITERS or gm_nu != _GM_NU):
+            raise ValueError(f"gm_iters={gm_iters} / gm_nu={gm_nu} needs "
+                             f"aggregation_rule='geometric_median', not {rule!r}")
         if rule == "mean":
             return
         if cls._robust_unsupported is not None:
@@ -159,9 +181,10 @@ class FedServer(Server):
             return self.__prev_model
         ids = list(client_subset)
         store = self.parameters.store
-        # multi-Krum reports and breaks ties by worker id (no subclass that overrides
-        # _aggregate runs that rule)
-        extra = {"ids": ids} if self.aggregation_rule == "multi_krum" else {}
+        # multi-Krum and the geometric median report, break ties and order by worker id
+        # (no subclass that overrides _aggregate runs those rules)
+        extra = {"ids": ids} if self.aggregation_rule in ("multi_krum",
+                                                          "geometric_median") else {}
         flat = self._aggregate(store, [self.parameters.row_of(i) for i in ids],
                                [self.parameters.n_of(i) for i in ids], **extra)
         return store.layout.views(flat)
@@ -177,6 +200,8 @@ class FedServer(Server):
             return store.median(rows)
         if self.aggregation_rule == "multi_krum":
             return self._multi_krum(store, rows, list(range(K)) if ids is None else ids)
+        if self.aggregation_rule == "geometric_median":
+            return self._geometric_median(store, rows, list(range(K)) if ids is None else ids)
         if 2 * self.trim >= K:
             raise ValueError(f"trim={self.trim} leaves nothing of a subset of {K} clients "
                              "(2*trim < len(subset) is needed)")
@@ -196,6 +221,15 @@ class FedServer(Server):
         chosen = set(selected)
         log.info("multi_krum: kept %s of %s clients, rejected workers %s", len(selected), K,
                  [i for i in ids if i not in chosen])
+        return flat
+
+    def _geometric_median(self, store, rows, ids):
+        flat, info = store.geometric_median(rows, ids, self.gm_iters, self.gm_nu)
+        self.last_distances = info["distances"]
+        self.last_rejected = tuple(info["rejected"])
+        log.info("geometric_median: %s of %s clients, rejected workers %s, objective %s -> %s",
+                 len(info["distances"]), len(rows), list(self.last_rejected),
+                 info["objective"][0], info["objective"][-1])
         return flat
 
     def _process_worker_data(self, data, __):

@@ -4,7 +4,8 @@
         --model_name LeNet5 --distributed_algorithm fed --worker_number 10 --round 5 \\
         --epoch 1 --learning_rate 0.01 --log_level INFO [--aggregation_mode fma]
         [--aggregation_rule median | --aggregation_rule trimmed_mean --trim 2 |
-         --aggregation_rule multi_krum --byzantine 2 [--krum_select 1]]
+         --aggregation_rule multi_krum --byzantine 2 [--krum_select 1] |
+         --aggregation_rule geometric_median [--gm_iters 3] [--gm_nu 1e-6]]
 
 Same flags and flow as the reference: IID split of the training set over the
 workers (:48-50), a tester on the test split (:51), ``factory.get_server``
@@ -68,10 +69,15 @@ def get_config(argv=None):
     # averages the --krum_select best-scored ones (default: all but --byzantine;
     # 1 is classic Krum).  The robust rules ignore the clients' sample counts.
     ap.add_argument("--aggregation_rule", type=str, default="mean",
-                    choices=("mean", "median", "trimmed_mean", "multi_krum"))
+                    choices=("mean", "median", "trimmed_mean", "multi_krum",
+                             "geometric_median"))
     ap.add_argument("--trim", type=int, default=0)
     ap.add_argument("--byzantine", type=int, default=0)
     ap.add_argument("--krum_select", type=int, default=None)
+    # geometric_median: --gm_iters smoothed Weiszfeld steps from the coordinate-wise
+    # median, smoothing --gm_nu in the units of the parameters (RFA's defaults)
+    ap.add_argument("--gm_iters", type=int, default=3)
+    ap.add_argument("--gm_nu", type=float, default=1e-6)
     config = ap.parse_args(argv)
     if config.distributed_algorithm == "sign_SGD" and config.aggregation_rule != "mean":
         ap.error("--aggregation_rule applies to the FedAvg-based servers; sign_SGD votes")
@@ -83,7 +89,8 @@ def server_kwargs(config):
     worker_number / multi_process: the aggregation mode for the FedAvg-based
     servers (sign_SGD votes; it has no FedAvg), the utility metric for the two
     Shapley servers, the aggregation rule and its trim count when the rule is not the
-    default mean, and multi-Krum's byzantine / krum_select for that rule alone."""
+    default mean, multi-Krum's byzantine / krum_select and the geometric median's
+    gm_iters / gm_nu for those rules alone."""
     if config.distributed_algorithm == "sign_SGD":
         return {}
     kwargs = {"aggregation_mode": config.aggregation_mode}
@@ -95,6 +102,9 @@ def server_kwargs(config):
         if config.aggregation_rule == "multi_krum":
             kwargs["byzantine"] = getattr(config, "byzantine", 0)
             kwargs["krum_select"] = getattr(config, "krum_select", None)
+        if config.aggregation_rule == "geometric_median":
+            kwargs["gm_iters"] = getattr(config, "gm_iters", 3)
+            kwargs["gm_nu"] = getattr(config, "gm_nu", 1e-6)
     return kwargs
 
 

@@ -170,6 +170,48 @@ int64_t dls_pairwise_sqdist_workspace(int32_t K, int64_t P);
 int dls_pairwise_sqdist_f32(const float *U, int64_t ldu, const int32_t *rows, int32_t K, int64_t P,
                             double *D, void *workspace, dls_stream_t stream);
 
+/* Fused Weiszfeld step and squared distances of K client rows to one point: the
+ * hot path of the geometric median (the smoothed Weiszfeld iteration of RFA,
+ * Pillutla, Kakade & Harchaoui) and of "how far is every client from the
+ * aggregate".  Operands and layout rules of dls_trimmed_mean_f32 (rows device
+ * int32 [K], 1 <= K <= DLS_ROBUST_MAX_K; P, ldu multiples of 4, ldu >= P; U and z
+ * 16-byte aligned); w is device fp32 [K]; dist2 is device fp64 [K] (8-byte
+ * aligned); workspace is device memory of dls_weiszfeld_workspace(K, P) bytes (a
+ * function of K and P alone; 16-byte aligned), scratch for this call only.  Every
+ * check, the null pointers included, runs before any device call.
+ *   dls_rows_sqdist_to_f32: z fp32 [P] is read;
+ *   dls_weiszfeld_step_f32: z is computed from the rows and written (the old
+ *     contents are never read), and dist2 is taken to that new z in the same
+ *     visit, so the K values of a coordinate are read from HBM once per step.
+ * The iterate of the step, per coordinate p, in the order of `rows`, every
+ * operation rounded once and never fused:
+ *   t_k = fl32(w[k] * U[rows[k]][p]);  acc = t_0;  acc = fl32(acc + t_k) for
+ *   k = 1 .. K-1;  z[p] = acc.
+ * Given the bits of w, z is defined bit for bit (numpy float32 reproduces it);
+ * K = 1 with w = 1.0 returns the row's own bits, -0.0 included.  z does not depend
+ * on ldu, on the rows' position in U, on the stream or on the CU count.
+ * The distances, dist2[k] ~ sum_p (U[rows[k]][p] - z[p])^2, use the arithmetic of
+ * dls_pairwise_sqdist_f32:
+ *   d = fl32(x - z); acc = fmaf(d, d, acc) in fp32 chains of at most 120 terms;
+ *   the chain results are converted to fp64 and added in fp64 in a fixed order
+ *   that is a function of P and K alone.
+ * All terms are non-negative, so for finite inputs whose terms neither overflow
+ * nor underflow dist2[k] is within (120 + 8) * 2^-24 = 2^-17 relative of the exact
+ * squared distance of the fp32 row to the fp32 z.
+ * Exact properties: rows of equal contents get the same bits; a row equal to z
+ * gets +0.0; coordinates past P contribute d = 0; repeated calls give the same
+ * bits on any stream.  No atomics: a second launch adds the per-wave partials of
+ * `workspace` in ascending order.  A row that holds an inf or NaN (or whose chain
+ * overflows) gets +inf or NaN; in dls_rows_sqdist_to_f32 the other rows are
+ * unaffected (in the step such a row with a non-zero weight poisons z).
+ * P == 0 writes zeros to dist2, writes nothing to z and launches nothing else. */
+int64_t dls_weiszfeld_workspace(int32_t K, int64_t P);
+int dls_rows_sqdist_to_f32(const float *U, int64_t ldu, const int32_t *rows, int32_t K, int64_t P,
+                           const float *z, double *dist2, void *workspace, dls_stream_t stream);
+int dls_weiszfeld_step_f32(const float *U, int64_t ldu, const int32_t *rows, int32_t K,
+                           const float *w, int64_t P, float *z, double *dist2,
+                           void *workspace, dls_stream_t stream);
+
 /* Subset aggregation as a dense fp32 MFMA contraction: out[S, P] = C[S, K] · U[rows, P]
  * (C row-major [S, K], c_si = n_i / N_S; rows[K] selects the K client rows of U).
  * fp32 in / fp32 accumulate (v_mfma_f32_32x32x2_f32): an fma chain in client
