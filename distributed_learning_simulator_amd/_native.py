@@ -70,6 +70,7 @@ SIGNATURES = {
     "dls_weiszfeld_workspace": ([_i32, _i64], _i64),
     "dls_rows_sqdist_to_f32": ([_p, _i64, _p, _i32, _i64, _p, _p, _p, _p], _i32),
     "dls_weiszfeld_step_f32": ([_p, _i64, _p, _i32, _p, _i64, _p, _p, _p, _p], _i32),
+    "dls_centered_clip_step_f32": ([_p, _i64, _p, _i32, _p, _i64, _p, _p, _p, _p], _i32),
     "dls_subset_gemm_f32": ([_p, _i32, _i32, _p, _i64, _p, _i64, _p, _i64, _p], _i32),
     "dls_sign_pack_f32": ([_p, _i64, _i32, _i64, _p, _i64, _p, _p], _i32),
     "dls_sign_vote_count": ([_p, _i64, _p, _i32, _i64, _p, _p], _i32),
@@ -369,6 +370,35 @@ def weiszfeld_step(U, rows, w, P, z, dist2=None, stream=None):
     _check(lib().dls_weiszfeld_step_f32(_ptr(U), ldu, _ptr(rows), K, _ptr(w), P, _ptr(z),
                                         _ptr(dist2), _ptr(work), _stream(stream, U)),
            "dls_weiszfeld_step_f32")
+    if stream is not None:
+        work.record_stream(stream)
+    return z, dist2
+
+
+def centered_clip_step(U, rows, c, P, z, dist2=None, stream=None):
+    """One fused centered-clipping step (dls_centered_clip_step_f32), in place: z[:P] =
+    fl32(z + sum_k fl32(c[k] * fl32(U[rows[k]] - z))) - subtract, multiply, add in the
+    order of ``rows``, then add to z, every operation rounded once, so the new z is
+    defined bit for bit by the bits of c and of the old z - and the squared distances
+    of the rows to that new z (as rows_sqdist_to) from the same read of the rows.  c: a
+    contiguous fp32 [K] tensor (the callers' min(1, tau / distance) / K); the rest as
+    in rows_sqdist_to.  Returns (z, dist2)."""
+    fn = "centered_clip_step"
+    K, P, ldu = _rows_operands(fn, U, rows, P)
+    if (not torch.is_tensor(c) or c.dtype != torch.float32 or tuple(c.shape) != (K,)
+            or not c.is_contiguous()):
+        raise RuntimeError(f"{fn}: c must be a contiguous fp32 [K] = [{K}] tensor")
+    dist2 = _point_operands(fn, U, K, P, z, dist2, "dist2")
+    _check_same_device(fn, U, rows=rows, c=c, z=z, dist2=dist2)
+    if U.data_ptr() % 16 != 0 or z.data_ptr() % 16 != 0:
+        raise RuntimeError(f"{fn}: U and z must be 16-byte aligned")
+    if dist2 is None:
+        dist2 = torch.empty((K,), dtype=torch.float64, device=U.device)
+    _ptr(U), _ptr(rows), _ptr(c), _ptr(z), _ptr(dist2)  # no CPU path
+    work = _weiszfeld_work(K, P, U.device)
+    _check(lib().dls_centered_clip_step_f32(_ptr(U), ldu, _ptr(rows), K, _ptr(c), P, _ptr(z),
+                                            _ptr(dist2), _ptr(work), _stream(stream, U)),
+           "dls_centered_clip_step_f32")
     if stream is not None:
         work.record_stream(stream)
     return z, dist2

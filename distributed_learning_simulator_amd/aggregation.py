@@ -138,6 +138,32 @@ def weiszfeld_weights(dist2, nu):
     return kept, torch.tensor([b / total for b in beta], dtype=torch.float64).float().tolist()
 
 
+def clip_scales(dist2, tau):
+    """The scales of one centered-clipping step (Karimireddy et al. 2021) from the
+    squared distances of the clients to the current iterate, on the host in fp64:
+    (kept_indices, scales, coeffs).
+
+    Indices whose ``dist2`` is non-finite or negative are dropped.  For the others
+    s_i = 1.0 if sqrt(dist2_i) <= tau, else tau / sqrt(dist2_i) (a client inside the
+    radius counts in full, one outside is pulled back onto it), and coeffs[j] =
+    float32(s_i / n_kept) (a Python float holding the fp32 value) for the j-th kept
+    index i: what dls_centered_clip_step_f32 multiplies the client's difference by.
+    ValueError: nothing is kept, or ``tau`` is not a positive finite number."""
+    if isinstance(tau, bool) or not isinstance(tau, (int, float)) or not math.isfinite(tau) \
+            or tau <= 0:
+        raise ValueError(f"tau must be a positive finite number, not {tau!r}")
+    tau = float(tau)
+    d2 = [float(v) for v in dist2]
+    kept = [i for i, v in enumerate(d2) if math.isfinite(v) and v >= 0.0]
+    if not kept:
+        raise ValueError(f"no client has a finite distance (0 of {len(d2)})")
+    dist = [math.sqrt(d2[i]) for i in kept]
+    scales = [1.0 if d <= tau else tau / d for d in dist]
+    n = float(len(kept))
+    return kept, scales, torch.tensor([s / n for s in scales],
+                                      dtype=torch.float64).float().tolist()
+
+
 class ClientUpdateStore:
     """``acquire_range = (lo, hi)``: this process's own clients take rows [lo, hi)
     only (a fixed block; the sharded Shapley servers all-gather every rank's block
@@ -307,6 +333,74 @@ class ClientUpdateStore:
                                               _f32(weights, self.device), P, flat)
             active, d2 = settle(weights, dist2.cpu().tolist())
         info["distances"] = {i: math.sqrt(v) for (i, _), v in zip(active, d2)}
+        if trace:
+            info["trace"] = passes
+        return flat, info
+
+    def centered_clip(self, rows, ids, start, tau, iters, out=None, trace=False):
+        """Centered clipping (Karimireddy, He & Jaggi 2021) of the given rows (client
+        ``ids[i]`` in ``rows[i]``) from ``start``: ``iters`` times v <- v + (1 / K) *
+        sum_k clip(x_k - v), where a difference longer than ``tau`` is shortened to
+        ``tau``, so no client moves a step by more than tau / K however far away it
+        sits; ``iters=1`` is norm clipping (Sun et al. 2019).  The clients are taken in
+        id order (distinct, sortable ids), so the result is the same bits for any arrival
+        order.  ``start`` is an fp32 device vector of ``layout.P`` elements and is never
+        modified: the iterate begins as its copy (in ``out`` if given).  One distance
+        pass against the start, then per step ``clip_scales`` on the host, one fused
+        ``dls_centered_clip_step_f32`` in place and one copy of K doubles to the host.
+        A client whose distance is not finite after any pass is rejected for the rest
+        of the call; ValueError when none is left.  Returns (flat, info):
+        ``distances`` {id: distance to the returned aggregate}, ``rejected`` (sorted
+        ids), ``scales`` {id: the scale s of the last step, 1.0 for a client inside the
+        radius}, ``moved`` (the Euclidean length of each step: the iterate before the
+        step is kept, and one device norm of the fp32 difference per step, summed in
+        fp64, is copied to the host once at the end) and, with ``trace``, per pass the
+        (ids, fp32 coefficients or None, dist2) the pass ran on and gave."""
+        iters = int(iters)
+        if iters < 1:
+            raise ValueError(f"iters={iters} must be at least 1")
+        ids = list(ids)
+        if len(set(ids)) != len(ids) or len(ids) != len(rows):
+            raise ValueError("centered_clip needs one distinct id per row")
+        active = sorted(zip(ids, (int(r) for r in rows)))
+        K, P = len(active), self.layout.P
+        if (not torch.is_tensor(start) or start.dtype != torch.float32 or start.dim() != 1
+                or start.numel() != P or start.device != self.U.device):
+            raise ValueError(f"start must be an fp32 vector of P={P} elements on {self.U.device}")
+        flat = torch.empty(P, dtype=torch.float32, device=self.device) if out is None else out
+        flat.copy_(start)
+        prev = torch.empty_like(flat)
+        moved = torch.zeros(iters, dtype=torch.float64, device=self.device)
+        info = {"distances": {}, "rejected": [], "scales": {}, "moved": []}
+        passes, n_pass = [], [0]
+
+        def settle(coeffs, d2):
+            """Book one pass's distances; the clients that go on."""
+            if trace:
+                passes.append(([i for i, _ in active], coeffs, list(d2)))
+            good = [k for k, v in enumerate(d2) if math.isfinite(v) and v >= 0.0]
+            info["rejected"] = sorted(info["rejected"]
+                                      + [active[k][0] for k in range(len(d2)) if k not in good])
+            if not good:
+                raise ValueError(f"centered_clip: no client is at a finite distance from the "
+                                 f"iterate after pass {n_pass[0]} "
+                                 f"({K - len(info['rejected'])} of {K} finite)")
+            n_pass[0] += 1
+            return [active[k] for k in good], [d2[k] for k in good]
+
+        d2 = self.sqdist_to([r for _, r in active], flat).cpu().tolist()
+        active, d2 = settle(None, d2)
+        for it in range(iters):
+            _, scales, coeffs = clip_scales(d2, tau)
+            info["scales"] = {i: s for (i, _), s in zip(active, scales)}
+            prev.copy_(flat)
+            _, dist2 = _native.centered_clip_step(
+                self.U, _i32([r for _, r in active], self.device), _f32(coeffs, self.device), P,
+                flat)
+            moved[it] = torch.linalg.vector_norm(flat - prev, dtype=torch.float64)
+            active, d2 = settle(coeffs, dist2.cpu().tolist())
+        info["distances"] = {i: math.sqrt(v) for (i, _), v in zip(active, d2)}
+        info["moved"] = moved.cpu().tolist()
         if trace:
             info["trace"] = passes
         return flat, info

@@ -1,13 +1,17 @@
-// Fused Weiszfeld step and row-to-point squared distances for gfx950: the hot path of
-// the geometric-median rule (RFA, Pillutla et al.; FedServer
-// aggregation_rule="geometric_median") and of "how far is every client from the
+// Fused Weiszfeld step, centered-clipping step and row-to-point squared distances for
+// gfx950: the hot path of the geometric-median rule (RFA, Pillutla et al.; FedServer
+// aggregation_rule="geometric_median"), of centered clipping (Karimireddy et al.;
+// aggregation_rule="centered_clip") and of "how far is every client from the
 // aggregate".
 //
 //   step:      z[p]     = sum_k fl32(w[k] * U[rows[k]][p])     (mul, then add, in row order)
+//   clip step: z[p]     = fl32(z[p] + sum_k fl32(c[k] * fl32(U[rows[k]][p] - z[p])))
 //   distances: dist2[k] ~ sum_p (U[rows[k]][p] - z[p])^2       (include/dls_hip.h)
-// One kernel template with a flag: z read (dls_rows_sqdist_to_f32), or z computed from
-// the K values the lane already holds and written (dls_weiszfeld_step_f32), so a step
-// reads the rows from HBM once: FedAvg's traffic.
+// One kernel template with a mode: z read (dls_rows_sqdist_to_f32), z computed from
+// the K values the lane already holds and written (dls_weiszfeld_step_f32), or z read,
+// moved by the clipped differences to those K values and written back
+// (dls_centered_clip_step_f32), so a step reads the rows from HBM once: FedAvg's
+// traffic (the clip step adds one read of z).
 //
 // Lanes run across coordinates as in k_trimmed_mean: a lane owns VW consecutive
 // coordinates of a tile of 64 VW (VW = 4, one 16-byte load per row, for K <= 32;
@@ -80,9 +84,11 @@ __device__ __forceinline__ double reduce_rows(const double (&v)[N], int lane) {
     }
 }
 
-// KP wires (a power of two >= K), VW coordinates per lane; STEP: z is computed from
-// the rows and written, else read.
-template <int KP, int VW, bool STEP>
+enum Mode { kRead, kStep, kClip };  // what happens to z before the distances
+
+// KP wires (a power of two >= K), VW coordinates per lane; kRead: z is read; kStep: z
+// is computed from the rows and written; kClip: z is read, stepped and written back.
+template <int KP, int VW, Mode MODE>
 __global__ __launch_bounds__(kBlock) void k_weiszfeld(const float *__restrict__ U, int64_t ldu,
                                                       const int32_t *__restrict__ rows, int K,
                                                       const float *__restrict__ w, int64_t P,
@@ -95,7 +101,7 @@ __global__ __launch_bounds__(kBlock) void k_weiszfeld(const float *__restrict__ 
     if (wv >= nW) return;  // the whole wave
     const int tr = rows[min(lane, K - 1)];
     int tw = 0;
-    if constexpr (STEP) tw = __float_as_int(w[min(lane, K - 1)]);
+    if constexpr (MODE != kRead) tw = __float_as_int(w[min(lane, K - 1)]);
     const int64_t PV = P / VW;
     vec *zv = reinterpret_cast<vec *>(z);
 
@@ -118,7 +124,7 @@ __global__ __launch_bounds__(kBlock) void k_weiszfeld(const float *__restrict__ 
             x[j] = __builtin_nontemporal_load(reinterpret_cast<const vec *>(U + r * ldu) + iq);
         }
         vec zq;
-        if constexpr (STEP) {
+        if constexpr (MODE == kStep) {
             // t_k = fl32(w_k * x_k); acc = t_0; acc = fl32(acc + t_k): -0 + t == t for
             // every t, so a wire past K adds -0
 #pragma unroll
@@ -132,6 +138,29 @@ __global__ __launch_bounds__(kBlock) void k_weiszfeld(const float *__restrict__ 
                     zq = zq + tk;
                 }
             }
+            if (in) zv[i0] = zq;
+        } else if constexpr (MODE == kClip) {
+            // The old z: an ordinary load (this lane stores z' to the same address and
+            // nobody else reads it).  A lane past P re-reads index PV - 1, which its
+            // owner in this wave may already have rewritten: whatever it gets is
+            // harmless, because such a lane stores nothing and its d below is forced
+            // to 0.
+            const vec zo = zv[iq];
+            // t_k = fl32(c_k * fl32(x_k - z)); acc = t_0; acc = fl32(acc + t_k);
+            // z' = fl32(z + acc): no fma (-ffp-contract=off), a wire past K adds -0
+            vec acc;
+#pragma unroll
+            for (int j = 0; j < KP; ++j) {
+                const float cj = __int_as_float(__builtin_amdgcn_readlane(tw, j));
+                vec tk = (x[j] - zo) * cj;
+                if (j == 0) {
+                    acc = tk;
+                } else {
+                    if (j >= K) tk = (vec)(-0.f);  // wave-uniform
+                    acc = acc + tk;
+                }
+            }
+            zq = zo + acc;
             if (in) zv[i0] = zq;
         } else {
             zq = reinterpret_cast<const vec *>(z)[iq];
@@ -185,33 +214,33 @@ __global__ __launch_bounds__(64 * kFinishPhases) void k_weiszfeld_finish(
     }
 }
 
-template <int KP, int VW, bool STEP>
+template <int KP, int VW, Mode MODE>
 void launch(const float *U, int64_t ldu, const int32_t *rows, int K, const float *w, int64_t P,
             float *z, double *dist2, double *part, hipStream_t st) {
     const StepPlan pl = make_plan(K, P);
     const unsigned blocks = (unsigned)((pl.nW + kBlock / 64 - 1) / (kBlock / 64));
-    hipLaunchKernelGGL((k_weiszfeld<KP, VW, STEP>), dim3(blocks), dim3(kBlock), 0, st, U, ldu, rows,
+    hipLaunchKernelGGL((k_weiszfeld<KP, VW, MODE>), dim3(blocks), dim3(kBlock), 0, st, U, ldu, rows,
                        K, w, P, pl.tiles, pl.tpw, pl.nW, z, part);
     hipLaunchKernelGGL(k_weiszfeld_finish, dim3(1), dim3(64 * kFinishPhases), 0, st,
                        (const double *)part, pl.nW, K, dist2);
 }
 
-template <bool STEP>
+template <Mode MODE>
 void dispatch(const float *U, int64_t ldu, const int32_t *rows, int K, const float *w, int64_t P,
               float *z, double *dist2, double *part, hipStream_t st) {
     if (K <= 4)
-        launch<4, 4, STEP>(U, ldu, rows, K, w, P, z, dist2, part, st);
+        launch<4, 4, MODE>(U, ldu, rows, K, w, P, z, dist2, part, st);
     else if (K <= 8)
-        launch<8, 4, STEP>(U, ldu, rows, K, w, P, z, dist2, part, st);
+        launch<8, 4, MODE>(U, ldu, rows, K, w, P, z, dist2, part, st);
     else if (K <= 16)
-        launch<16, 4, STEP>(U, ldu, rows, K, w, P, z, dist2, part, st);
+        launch<16, 4, MODE>(U, ldu, rows, K, w, P, z, dist2, part, st);
     else if (K <= 32)
-        launch<32, 4, STEP>(U, ldu, rows, K, w, P, z, dist2, part, st);
+        launch<32, 4, MODE>(U, ldu, rows, K, w, P, z, dist2, part, st);
     else
-        launch<64, 2, STEP>(U, ldu, rows, K, w, P, z, dist2, part, st);
+        launch<64, 2, MODE>(U, ldu, rows, K, w, P, z, dist2, part, st);
 }
 
-// The operand checks both entry points share; `fn` names the caller.
+// The operand checks the entry points share; `fn` names the caller.
 int check_operands(const char *fn, const float *U, int64_t ldu, const int32_t *rows, int32_t K,
                    int64_t P, const float *z, const double *dist2, const void *workspace,
                    const float *w, bool step) {
@@ -256,7 +285,7 @@ extern "C" int dls_rows_sqdist_to_f32(const float *U, int64_t ldu, const int32_t
     if (rc != DLS_OK) return rc;
     hipStream_t st = as_stream(stream);
     if (P == 0) return zero_dist2(fn, dist2, K, st);
-    dispatch<false>(U, ldu, rows, K, nullptr, P, const_cast<float *>(z), dist2,
+    dispatch<kRead>(U, ldu, rows, K, nullptr, P, const_cast<float *>(z), dist2,
                     static_cast<double *>(workspace), st);
     return check_launch(fn);
 }
@@ -269,6 +298,18 @@ extern "C" int dls_weiszfeld_step_f32(const float *U, int64_t ldu, const int32_t
     if (rc != DLS_OK) return rc;
     hipStream_t st = as_stream(stream);
     if (P == 0) return zero_dist2(fn, dist2, K, st);
-    dispatch<true>(U, ldu, rows, K, w, P, z, dist2, static_cast<double *>(workspace), st);
+    dispatch<kStep>(U, ldu, rows, K, w, P, z, dist2, static_cast<double *>(workspace), st);
+    return check_launch(fn);
+}
+
+extern "C" int dls_centered_clip_step_f32(const float *U, int64_t ldu, const int32_t *rows,
+                                          int32_t K, const float *c, int64_t P, float *z,
+                                          double *dist2, void *workspace, dls_stream_t stream) {
+    const char *fn = "dls_centered_clip_step_f32";
+    const int rc = check_operands(fn, U, ldu, rows, K, P, z, dist2, workspace, c, true);
+    if (rc != DLS_OK) return rc;
+    hipStream_t st = as_stream(stream);
+    if (P == 0) return zero_dist2(fn, dist2, K, st);
+    dispatch<kClip>(U, ldu, rows, K, c, P, z, dist2, static_cast<double *>(workspace), st);
     return check_launch(fn);
 }

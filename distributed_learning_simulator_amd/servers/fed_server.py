@@ -18,8 +18,9 @@ from .server import Server
 log = logging.getLogger("distributed_learning_simulator_amd")
 
 _MODES = {"exact": _native.FEDAVG_EXACT, "fma": _native.FEDAVG_FMA}
-_RULES = ("mean", "median", "trimmed_mean", "multi_krum", "geometric_median")
+_RULES = ("mean", "median", "trimmed_mean", "multi_krum", "geometric_median", "centered_clip")
 _GM_ITERS, _GM_NU = 3, 1e-6  # the defaults of RFA (Pillutla et al.)
+_CC_TAU, _CC_ITERS = 10.0, 3
 
 
 class FedServer(Server):
@@ -43,7 +44,21 @@ class FedServer(Server):
       median (RFA, Pillutla et al.; dls_weiszfeld_step_f32): an outlier is
       down-weighted by 1 / distance instead of dropped, a client with a non-finite
       update is rejected.  ``last_distances`` / ``last_rejected`` hold the latest
-      call's distances to the aggregate and rejected workers.
+      call's distances to the aggregate and rejected workers;
+    * ``"centered_clip"``: centered clipping (Karimireddy, He & Jaggi 2021;
+      dls_centered_clip_step_f32): ``cc_iters`` times the aggregate moves from where
+      it is by the mean of the clients' differences to it, every difference longer
+      than ``cc_tau`` shortened to ``cc_tau`` first, so a client pulls a step by at
+      most cc_tau / K however far away it sits and the clients inside the radius
+      count as in the plain mean.  It starts from the previous global model
+      (``prev_model``; from the coordinate-wise median while there is none, as in
+      round 1 of a server without a tester); ``cc_iters=1`` is norm clipping (Sun
+      et al. 2019).  ``cc_tau`` is in the units of the parameters:
+      ``last_distances`` of a trial round shows the scale to choose it from.  Like
+      the other robust rules it ignores the sample counts; a client with a
+      non-finite update is rejected.  ``last_clip_scales`` holds the last step's
+      scale per worker (1.0: not clipped) beside ``last_distances`` /
+      ``last_rejected``.
 
     The robust rules ignore the clients' sample counts n_i (every client counts
     once), take at most ``_native.ROBUST_MAX_K`` clients and are bit-identical for
@@ -54,11 +69,12 @@ class FedServer(Server):
     _robust_unsupported = None
 
     def __init__(self, aggregation_mode="exact", aggregation_rule="mean", trim=0, byzantine=0,
-                 krum_select=None, gm_iters=_GM_ITERS, gm_nu=_GM_NU, **kwargs):
+                 krum_select=None, gm_iters=_GM_ITERS, gm_nu=_GM_NU, cc_tau=_CC_TAU,
+                 cc_iters=_CC_ITERS, **kwargs):
         if aggregation_mode not in _MODES:
             raise ValueError(f"aggregation_mode must be one of {sorted(_MODES)}, not {aggregation_mode!r}")
         self._check_rule(aggregation_rule, trim, aggregation_mode, kwargs.get("worker_number"),
-                         byzantine, krum_select, gm_iters, gm_nu)
+                         byzantine, krum_select, gm_iters, gm_nu, cc_tau, cc_iters)
         super().__init__(**kwargs)
         _native.require_gpu()
         self.round = 0
@@ -73,6 +89,9 @@ class FedServer(Server):
         self.gm_nu = float(gm_nu)
         self.last_distances = {}
         self.last_rejected = ()
+        self.cc_tau = float(cc_tau)
+        self.cc_iters = cc_iters
+        self.last_clip_scales = {}
         self.parameters: ClientParameters = ClientParameters(self._make_store)
         self.__prev_model = copy.deepcopy(
             ModelUtil(self.tester.model).get_parameter_dict()) if self.tester is not None else {}
@@ -81,7 +100,7 @@ class FedServer(Server):
 
     @classmethod
     def _check_rule(cls, rule, trim, mode, worker_number, byzantine=0, krum_select=None,
-                    gm_iters=_GM_ITERS, gm_nu=_GM_NU):
+                    gm_iters=_GM_ITERS, gm_nu=_GM_NU, cc_tau=_CC_TAU, cc_iters=_CC_ITERS):
         if rule not in _RULES:
             raise ValueError(f"aggregation_rule must be one of {list(_RULES)}, not {rule!r}")
         if isinstance(trim, bool) or not isinstance(trim, int) or trim < 0:
@@ -104,6 +123,14 @@ class FedServer(Server):
         if rule != "geometric_median" and (gm_iters != _GM_ITERS or gm_nu != _GM_NU):
             raise ValueError(f"gm_iters={gm_iters} / gm_nu={gm_nu} needs "
                              f"aggregation_rule='geometric_median', not {rule!r}")
+        if isinstance(cc_iters, bool) or not isinstance(cc_iters, int) or cc_iters < 1:
+            raise ValueError(f"cc_iters must be a positive integer, not {cc_iters!r}")
+        if (isinstance(cc_tau, bool) or not isinstance(cc_tau, (int, float))
+                or not math.isfinite(cc_tau) or cc_tau <= 0):
+            raise ValueError(f"cc_tau must be a positive finite number, not {cc_tau!r}")
+        if rule != "centered_clip" and (cc_tau != _CC_TAU or cc_iters != _CC_ITERS):
+            raise ValueError(f"cc_tau={cc_tau} / cc_iters={cc_iters} needs "
+                             f"aggregation_rule='centered_clip', not {rule!r}")
         if rule == "mean":
             return
         if cls._robust_unsupported is not None:
@@ -181,10 +208,10 @@ class FedServer(Server):
             return self.__prev_model
         ids = list(client_subset)
         store = self.parameters.store
-        # multi-Krum and the geometric median report, break ties and order by worker id
-        # (no subclass that overrides _aggregate runs those rules)
-        extra = {"ids": ids} if self.aggregation_rule in ("multi_krum",
-                                                          "geometric_median") else {}
+        # multi-Krum, the geometric median and centered clipping report, break ties and
+        # order by worker id (no subclass that overrides _aggregate runs those rules)
+        extra = {"ids": ids} if self.aggregation_rule in ("multi_krum", "geometric_median",
+                                                          "centered_clip") else {}
         flat = self._aggregate(store, [self.parameters.row_of(i) for i in ids],
                                [self.parameters.n_of(i) for i in ids], **extra)
         return store.layout.views(flat)
@@ -202,6 +229,8 @@ class FedServer(Server):
             return self._multi_krum(store, rows, list(range(K)) if ids is None else ids)
         if self.aggregation_rule == "geometric_median":
             return self._geometric_median(store, rows, list(range(K)) if ids is None else ids)
+        if self.aggregation_rule == "centered_clip":
+            return self._centered_clip(store, rows, list(range(K)) if ids is None else ids)
         if 2 * self.trim >= K:
             raise ValueError(f"trim={self.trim} leaves nothing of a subset of {K} clients "
                              "(2*trim < len(subset) is needed)")
@@ -230,6 +259,25 @@ class FedServer(Server):
         log.info("geometric_median: %s of %s clients, rejected workers %s, objective %s -> %s",
                  len(info["distances"]), len(rows), list(self.last_rejected),
                  info["objective"][0], info["objective"][-1])
+        return flat
+
+    def _centered_clip(self, store, rows, ids):
+        # from the model the clients started from; the coordinate-wise median of the
+        # subset while there is none (round 1 of a server without a tester)
+        prev = self.__prev_model
+        if prev and store.accepts(prev):
+            start = store.layout.flatten(prev, device=store.U.device)
+        else:
+            start = store.median(rows)
+        flat, info = store.centered_clip(rows, ids, start, self.cc_tau, self.cc_iters)
+        self.last_distances = info["distances"]
+        self.last_rejected = tuple(info["rejected"])
+        self.last_clip_scales = info["scales"]
+        log.info("centered_clip: %s of %s clients, %s clipped in the last step (tau %s), "
+                 "rejected workers %s, steps of length %s",
+                 len(info["distances"]), len(rows),
+                 sum(1 for s in info["scales"].values() if s < 1.0), self.cc_tau,
+                 list(self.last_rejected), info["moved"])
         return flat
 
     def _process_worker_data(self, data, __):

@@ -5,7 +5,8 @@
         --epoch 1 --learning_rate 0.01 --log_level INFO [--aggregation_mode fma]
         [--aggregation_rule median | --aggregation_rule trimmed_mean --trim 2 |
          --aggregation_rule multi_krum --byzantine 2 [--krum_select 1] |
-         --aggregation_rule geometric_median [--gm_iters 3] [--gm_nu 1e-6]]
+         --aggregation_rule geometric_median [--gm_iters 3] [--gm_nu 1e-6] |
+         --aggregation_rule centered_clip [--cc_tau 10.0] [--cc_iters 3]]
 
 Same flags and flow as the reference: IID split of the training set over the
 workers (:48-50), a tester on the test split (:51), ``factory.get_server``
@@ -70,7 +71,7 @@ def get_config(argv=None):
     # 1 is classic Krum).  The robust rules ignore the clients' sample counts.
     ap.add_argument("--aggregation_rule", type=str, default="mean",
                     choices=("mean", "median", "trimmed_mean", "multi_krum",
-                             "geometric_median"))
+                             "geometric_median", "centered_clip"))
     ap.add_argument("--trim", type=int, default=0)
     ap.add_argument("--byzantine", type=int, default=0)
     ap.add_argument("--krum_select", type=int, default=None)
@@ -78,6 +79,11 @@ def get_config(argv=None):
     # median, smoothing --gm_nu in the units of the parameters (RFA's defaults)
     ap.add_argument("--gm_iters", type=int, default=3)
     ap.add_argument("--gm_nu", type=float, default=1e-6)
+    # centered_clip: --cc_iters clipped steps from the previous global model, each
+    # client's difference to the aggregate shortened to at most --cc_tau (in the units
+    # of the parameters); --cc_iters 1 is norm clipping
+    ap.add_argument("--cc_tau", type=float, default=10.0)
+    ap.add_argument("--cc_iters", type=int, default=3)
     config = ap.parse_args(argv)
     if config.distributed_algorithm == "sign_SGD" and config.aggregation_rule != "mean":
         ap.error("--aggregation_rule applies to the FedAvg-based servers; sign_SGD votes")
@@ -89,8 +95,8 @@ def server_kwargs(config):
     worker_number / multi_process: the aggregation mode for the FedAvg-based
     servers (sign_SGD votes; it has no FedAvg), the utility metric for the two
     Shapley servers, the aggregation rule and its trim count when the rule is not the
-    default mean, multi-Krum's byzantine / krum_select and the geometric median's
-    gm_iters / gm_nu for those rules alone."""
+    default mean, multi-Krum's byzantine / krum_select, the geometric median's
+    gm_iters / gm_nu and centered clipping's cc_tau / cc_iters for those rules alone."""
     if config.distributed_algorithm == "sign_SGD":
         return {}
     kwargs = {"aggregation_mode": config.aggregation_mode}
@@ -105,6 +111,9 @@ def server_kwargs(config):
         if config.aggregation_rule == "geometric_median":
             kwargs["gm_iters"] = getattr(config, "gm_iters", 3)
             kwargs["gm_nu"] = getattr(config, "gm_nu", 1e-6)
+        if config.aggregation_rule == "centered_clip":
+            kwargs["cc_tau"] = getattr(config, "cc_tau", 10.0)
+            kwargs["cc_iters"] = getattr(config, "cc_iters", 3)
     return kwargs
 
 

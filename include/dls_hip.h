@@ -212,6 +212,35 @@ int dls_weiszfeld_step_f32(const float *U, int64_t ldu, const int32_t *rows, int
                            const float *w, int64_t P, float *z, double *dist2,
                            void *workspace, dls_stream_t stream);
 
+/* Fused centered-clipping step (Karimireddy, He & Jaggi 2021): the iterate moves
+ * from where it is towards the K client rows by their clipped differences, and the
+ * squared distances to the new iterate come out of the same visit.  Operands, layout
+ * rules, workspace (dls_weiszfeld_workspace(K, P) bytes: the same plan) and checks of
+ * dls_weiszfeld_step_f32; c is device fp32 [K], the callers' c_k = min(1, tau /
+ * |x_k - z|) / K.  Every check, the null pointers included, runs before any device
+ * call.
+ * z fp32 [P] is read and overwritten in place.  Per coordinate p, in the order of
+ * `rows`, every operation rounded once and never fused:
+ *   d_k = fl32(U[rows[k]][p] - z[p]);  t_k = fl32(c[k] * d_k);  acc = t_0;
+ *   acc = fl32(acc + t_k) for k = 1 .. K-1;  z'[p] = fl32(z[p] + acc).
+ * Given the bits of c and of the old z, z' is defined bit for bit (numpy float32
+ * reproduces it) whenever the result is not NaN; where the arithmetic gives NaN the
+ * kernel gives some NaN, and the sign of a zero result is whatever IEEE gives the
+ * formula.  z' does not depend on ldu, on the rows' position in U, on the stream or
+ * on the CU count.
+ * dist2[k] ~ sum_p (U[rows[k]][p] - z'[p])^2 is taken to the new z, with the
+ * arithmetic and the 2^-17 relative bound of dls_weiszfeld_step_f32: d = fl32(x -
+ * z'), fma chains of at most 120 terms, an fp64 sum in a fixed order that is a
+ * function of P and K alone, no atomics.
+ * Exact properties: a row equal to z' gets +0.0; rows of equal contents get the same
+ * bits; coordinates past P contribute nothing; repeated calls from the same old z
+ * give the same bits on any stream.  A row that holds an inf or NaN poisons z' even
+ * with c[k] = 0 (0 * inf is NaN): callers leave such rows out.
+ * P == 0 writes zeros to dist2, touches nothing of z and launches nothing else. */
+int dls_centered_clip_step_f32(const float *U, int64_t ldu, const int32_t *rows, int32_t K,
+                               const float *c, int64_t P, float *z, double *dist2,
+                               void *workspace, dls_stream_t stream);
+
 /* Subset aggregation as a dense fp32 MFMA contraction: out[S, P] = C[S, K] · U[rows, P]
  * (C row-major [S, K], c_si = n_i / N_S; rows[K] selects the K client rows of U).
  * fp32 in / fp32 accumulate (v_mfma_f32_32x32x2_f32): an fma chain in client
