@@ -65,6 +65,7 @@ SIGNATURES = {
     "dls_subset_fedavg_union_f32": ([_p, _i64, _p, _p, _p, _i32, _p, _i32, _i64, _p, _i64, _p],
                                     _i32),
     "dls_trimmed_mean_f32": ([_p, _i64, _p, _i32, _i32, _i64, _p, _p], _i32),
+    "dls_mean_around_median_f32": ([_p, _i64, _p, _i32, _i32, _i64, _p, _p], _i32),
     "dls_pairwise_sqdist_workspace": ([_i32, _i64], _i64),
     "dls_pairwise_sqdist_f32": ([_p, _i64, _p, _i32, _i64, _p, _p, _p], _i32),
     "dls_weiszfeld_workspace": ([_i32, _i64], _i64),
@@ -300,6 +301,34 @@ def _rows_operands(fn, U, rows, P):
     if ldu % 4 != 0 or ldu < P:
         raise RuntimeError(f"{fn}: row pitch {ldu} must be a multiple of 4, at least P")
     return K, P, ldu
+
+
+def mean_around_median(U, rows, keep, P, out, stream=None):
+    """Coordinate-wise mean around the median of the K = rows.numel() selected rows of U
+    into out[:P] (dls_mean_around_median_f32): per coordinate the ``keep`` consecutive
+    sorted values closest to the median are averaged in ascending order (the window
+    slides to where the values cluster; a tie keeps the lower value).  keep = K is
+    ``trimmed_mean`` with trim 0, keep = 1 with an odd K the (finite, non-zero) median.  The client
+    weights play no part.  U: fp32 [*, ld] rows with unit element stride; rows: int32
+    [K], 1 <= K <= ROBUST_MAX_K; 1 <= keep <= K; P a multiple of 4, at most the row
+    length."""
+    fn = "mean_around_median"
+    K, P, ldu = _rows_operands(fn, U, rows, P)
+    keep = int(keep)
+    if not 1 <= keep <= K:
+        raise RuntimeError(f"{fn}: keep={keep} (1 <= keep <= K={K})")
+    if (not torch.is_tensor(out) or out.dtype != torch.float32 or out.dim() != 1
+            or out.numel() < P or (out.numel() > 1 and out.stride(0) != 1)):
+        raise RuntimeError(f"{fn}: out must be an fp32 vector of at least P={P} elements "
+                           "with unit stride")
+    _check_same_device(fn, U, rows=rows, out=out)
+    if U.data_ptr() % 16 != 0 or out.data_ptr() % 16 != 0:
+        raise RuntimeError(f"{fn}: U and out must be 16-byte aligned")
+    if P == 0:
+        return out
+    _check(lib().dls_mean_around_median_f32(_ptr(U), ldu, _ptr(rows), K, keep, P, _ptr(out),
+                                            _stream(stream, U)), "dls_mean_around_median_f32")
+    return out
 
 
 def _point_operands(fn, U, K, P, z, dist2, name):

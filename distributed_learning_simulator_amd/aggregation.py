@@ -113,6 +113,50 @@ def multi_krum_select(D, ids, byzantine, select):
     return [ids[i] for i in order[:m]], scores
 
 
+def bulyan_select(D, ids, byzantine):
+    """Stage 1 of Bulyan (El Mhamdi, Guerraoui & Rouault 2018), iterated Krum, from a
+    [K, K] matrix of squared distances, on the host: (selected_ids, scores).
+
+    ``D`` is any [K, K] array-like of float64 (row i belongs to client ``ids[i]``);
+    non-finite entries count as +inf.  theta = K - 2f clients are chosen (f =
+    ``byzantine``), one at a time from the remaining set R of r clients: client i's
+    score is the sum, ascending in fp64, of its max(r - f - 2, 1) smallest D[i][j]
+    over j in R, j != i, and the minimum by (score, id) is picked and leaves R (the
+    id breaks ties, the arrival order never does).  ``selected_ids`` is in pick
+    order, ``scores`` is {id: its score when it was picked}.  f == 0 selects
+    everybody: the sorted ids and no scores.  ValueError: D is not [K, K], f < 0,
+    K < 4f + 3, or a picked score is not finite."""
+    ids = list(ids)
+    K, f = len(ids), int(byzantine)
+    rows = [[float(v) for v in row] for row in D]
+    if len(rows) != K or any(len(r) != K for r in rows):
+        raise ValueError(f"D must be a [{K}, {K}] matrix for {K} ids")
+    if f < 0 or K < 4 * f + 3:
+        raise ValueError(f"Bulyan needs 4*byzantine + 3 <= K (byzantine={f}, K={K})")
+    if f == 0:
+        return sorted(ids), {}
+    rows = [[v if math.isfinite(v) else math.inf for v in row] for row in rows]
+    theta = K - 2 * f
+    remaining = list(range(K))
+    selected, scores = [], {}
+    while len(selected) < theta:
+        c = max(len(remaining) - f - 2, 1)
+        best = None
+        for i in remaining:
+            sc = 0.0
+            for v in sorted(rows[i][j] for j in remaining if j != i)[:c]:
+                sc += v
+            if best is None or (sc, ids[i]) < (best[0], ids[best[1]]):
+                best = (sc, i)
+        if not math.isfinite(best[0]):
+            raise ValueError(f"Bulyan could select only {len(selected)} of theta={theta} clients "
+                             f"with a finite score (K={K}, byzantine={f})")
+        scores[ids[best[1]]] = best[0]
+        selected.append(ids[best[1]])
+        remaining.remove(best[1])
+    return selected, scores
+
+
 def weiszfeld_weights(dist2, nu):
     """The weights of one smoothed Weiszfeld step (Pillutla et al., RFA) from the
     squared distances of the clients to the current iterate, on the host in fp64:
@@ -252,6 +296,20 @@ class ClientUpdateStore:
         K = rows.numel() if torch.is_tensor(rows) else len(rows)
         return self.trimmed_mean(rows, (K - 1) // 2, out=out, cols=cols)
 
+    def mean_around_median(self, rows, keep, out=None, cols=None):
+        """Coordinate-wise mean around the median of the given rows
+        (dls_mean_around_median_f32): per flat element the ``keep`` consecutive sorted
+        values closest to the median are averaged in ascending order (MeaMed, Xie et al.
+        2018; stage 2 of Bulyan).  The sample counts play no part, and the result is the
+        same bits for any order of ``rows``.  K <= _native.ROBUST_MAX_K, 1 <= keep <= K;
+        ``cols`` as in ``fedavg``."""
+        c0, c1 = cols if cols is not None else (0, self.layout.P)
+        if out is None:
+            out = torch.empty(c1 - c0, dtype=torch.float32, device=self.device)
+        r = rows if torch.is_tensor(rows) else _i32(rows, self.device)
+        _native.mean_around_median(self.U[:, c0:], r, keep, c1 - c0, out)
+        return out
+
     def pairwise_sqdist(self, rows, cols=None):
         """Squared Euclidean distances between the given rows (dls_pairwise_sqdist_f32):
         an fp64 [K, K] device tensor, symmetric in bits, +0.0 on the diagonal, the
@@ -273,6 +331,30 @@ class ClientUpdateStore:
         selected, scores = multi_krum_select(D, ids, byzantine, select)
         row_of = dict(zip(ids, rows))
         flat = self.trimmed_mean([row_of[i] for i in selected], 0, out=out)
+        return flat, selected, scores
+
+    def bulyan(self, rows, ids, byzantine, out=None):
+        """Bulyan over the given rows (client ``ids[i]`` in ``rows[i]``, distinct ids): one
+        distance launch, one copy of D to the host, ``bulyan_select`` (theta = K - 2f
+        clients by iterated Krum), then ``mean_around_median`` over the selected rows
+        with keep = theta - 2f = K - 4f.  Stage 2 depends only on the set of selected
+        rows, so the result is the same bits for any arrival order.  byzantine == 0
+        skips the distance launch: everybody is selected and the result is the ascending
+        mean.  Returns (flat, selected_ids, scores)."""
+        rows = [int(r) for r in rows]
+        ids = list(ids)
+        if len(set(ids)) != len(ids) or len(ids) != len(rows):
+            raise ValueError("bulyan needs one distinct id per row")
+        K, f = len(rows), int(byzantine)
+        if f < 0 or K < 4 * f + 3:
+            raise ValueError(f"Bulyan needs 4*byzantine + 3 <= K (byzantine={f}, K={K})")
+        if f == 0:
+            selected, scores = sorted(ids), {}
+        else:
+            D = self.pairwise_sqdist(rows).cpu().tolist()
+            selected, scores = bulyan_select(D, ids, f)
+        row_of = dict(zip(ids, rows))
+        flat = self.mean_around_median([row_of[i] for i in selected], K - 4 * f, out=out)
         return flat, selected, scores
 
     def sqdist_to(self, rows, point, cols=None):

@@ -1,5 +1,6 @@
-// Coordinate-wise trimmed mean / median over K client rows for gfx950: the robust
-// counterpart of the FedAvg hook (servers/fed_server.py:44-66).
+// Coordinate-wise trimmed mean / median, and the mean around the median (second
+// half of this file), over K client rows for gfx950: the robust counterparts of the
+// FedAvg hook (servers/fed_server.py:44-66).
 //
 // Per flat coordinate, independently (include/dls_hip.h has the contract):
 //   sort the K values ascending (-0 below +0, every NaN above +inf), drop the
@@ -195,6 +196,144 @@ void launch(const float *U, int64_t ldu, const int32_t *rows, int K, int trim, i
                        reinterpret_cast<f32x4 *>(out));
 }
 
+// ------------------------------------------- mean around the median (MeaMed)
+// dls_mean_around_median_f32: the `keep` consecutive sorted values closest to the
+// median, summed ascending.  Same loads, keys and network as k_trimmed_mean; after
+// the network, per coordinate:
+//   f[j]  = the sorted values (wires >= K decode to a NaN);
+//   med   = f[(K-1)/2], or fl(fl(f[K/2-1] + f[K/2]) / 2) for an even K, picked by
+//           wave-uniform selects over the wires that can hold it (j <= KP/2);
+//   h[i]  = f[i + keep], a NaN past the last wire: `keep` is wave-uniform, so the
+//           array is moved down by its set bits, one power of two per stage, every
+//           stage a select between two compile-time wires;
+//   s     = the number of wires with fl(med - f[i]) > fl(h[i] - med).  The true
+//           comparisons are a prefix of i = 0, 1, ... (both sides are monotone in
+//           i and the NaNs sit on top, where every comparison is false), so the
+//           count is the first false index, and a wire i >= K - keep compares
+//           with a NaN and never counts;
+//   sum   = the ascending sum of k_trimmed_mean with kept = s <= j < s + keep, a
+//           per-lane select (each of the lane's coordinates has its own s).
+template <int KP>
+constexpr int shift_stages() {
+    int n = 0;
+    while ((1 << n) <= KP) ++n;  // keep <= KP: bits 0 .. log2(KP)
+    return n;
+}
+
+template <int KP, int W, int C0>
+__device__ __forceinline__ void window_coords(const f32x4 (&x)[KP], int K, int keep, f32x4 &res) {
+    uint32_t v[W][KP];
+#pragma unroll
+    for (int j = 0; j < KP; ++j)
+#pragma unroll
+        for (int w = 0; w < W; ++w)
+            v[w][j] = j < K ? to_key(__float_as_uint(x[j][C0 + w])) : kTopKey;  // wave-uniform
+    net_sort<KP, W>(v);
+    float f[W][KP], h[W][KP];
+#pragma unroll
+    for (int j = 0; j < KP; ++j)
+#pragma unroll
+        for (int w = 0; w < W; ++w) h[w][j] = f[w][j] = from_key(v[w][j]);
+    // K > KP / 2 for KP >= 2, so the middle wires are among 0 .. KP/2
+    const int mlo = (K - 1) >> 1, mhi = K >> 1;
+    constexpr int kMid = KP > 1 ? KP / 2 : 0;
+    float med[W];
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+        float lo = f[w][0], hi = f[w][0];
+#pragma unroll
+        for (int j = 1; j <= kMid; ++j) {
+            lo = j == mlo ? f[w][j] : lo;  // wave-uniform
+            hi = j == mhi ? f[w][j] : hi;
+        }
+        med[w] = mlo == mhi ? lo : div_ieee(lo + hi, 2.f);
+    }
+    const float nan = __uint_as_float(0x7fc00000u);
+#pragma unroll
+    for (int b = 0; b < shift_stages<KP>(); ++b) {
+        const bool on = (keep >> b) & 1;  // wave-uniform
+#pragma unroll
+        for (int i = 0; i < KP; ++i)  // ascending: wire i + 2^b is still this stage's input
+#pragma unroll
+            for (int w = 0; w < W; ++w) {
+                const int src = i + (1 << b);
+                const float moved = src < KP ? h[w][src < KP ? src : i] : nan;
+                h[w][i] = on ? moved : h[w][i];
+            }
+    }
+    int s[W];
+#pragma unroll
+    for (int w = 0; w < W; ++w) s[w] = 0;
+#pragma unroll
+    for (int i = 0; i + 1 < KP; ++i)  // h[KP - 1] is a NaN for every keep >= 1
+#pragma unroll
+        for (int w = 0; w < W; ++w) s[w] += (med[w] - f[w][i]) > (h[w][i] - med[w]) ? 1 : 0;
+    float acc[W];
+#pragma unroll
+    for (int w = 0; w < W; ++w) acc[w] = -0.f;
+#pragma unroll
+    for (int j = 0; j < KP; ++j)
+#pragma unroll
+        for (int w = 0; w < W; ++w) {
+            const bool kept = (uint32_t)(j - s[w]) < (uint32_t)keep;  // s <= j < s + keep
+            acc[w] = acc[w] + (kept ? f[w][j] : -0.f);
+        }
+    if (keep > 1) {
+        const float fk = (float)keep;
+#pragma unroll
+        for (int w = 0; w < W; ++w) acc[w] = div_ieee(acc[w], fk);
+    }
+#pragma unroll
+    for (int w = 0; w < W; ++w) res[C0 + w] = quiet(acc[w]);
+}
+
+// The loads of k_trimmed_mean; W of the lane's 4 coordinates go through the network
+// and the window at a time.  KP = 64 takes one at a time: beside the parked loads a
+// pass holds the sorted values and their moved copy, and two coordinates per pass
+// spilled 60 bytes per lane to scratch.
+template <int KP, int W>
+__global__ __launch_bounds__(kRobustBlock) void k_mean_around_median(
+    const f32x4 *__restrict__ Uv, int64_t ldu4, const int32_t *__restrict__ rows, int K, int keep,
+    int64_t P4, f32x4 *__restrict__ out) {
+    const int lane = __lane_id();
+    const int64_t i0 = ((int64_t)blockIdx.x * (kRobustBlock / 64) + (threadIdx.x >> 6)) * 64 + lane;
+    const int64_t iq = i0 < P4 ? i0 : P4 - 1;  // every lane stays: the table needs all 64
+    const int tr = rows[min(lane, K - 1)];
+    f32x4 x[KP];
+#pragma unroll
+    for (int j = 0; j < KP; ++j) {
+        const int64_t r = __builtin_amdgcn_readlane(tr, j);
+        x[j] = __builtin_nontemporal_load(Uv + r * ldu4 + iq);
+    }
+    f32x4 res;
+    if constexpr (W == 4) {
+        window_coords<KP, 4, 0>(x, K, keep, res);
+    } else if constexpr (W == 2) {
+        window_coords<KP, 2, 0>(x, K, keep, res);
+        __builtin_amdgcn_sched_barrier(0);  // one pass's keys in registers at a time
+        window_coords<KP, 2, 2>(x, K, keep, res);
+    } else {
+        static_assert(W == 1, "coordinates per pass");
+        window_coords<KP, 1, 0>(x, K, keep, res);
+        __builtin_amdgcn_sched_barrier(0);
+        window_coords<KP, 1, 1>(x, K, keep, res);
+        __builtin_amdgcn_sched_barrier(0);
+        window_coords<KP, 1, 2>(x, K, keep, res);
+        __builtin_amdgcn_sched_barrier(0);
+        window_coords<KP, 1, 3>(x, K, keep, res);
+    }
+    if (i0 < P4) out[i0] = res;
+}
+
+template <int KP, int W = 4>
+void launch_window(const float *U, int64_t ldu, const int32_t *rows, int K, int keep, int64_t P4,
+                   float *out, hipStream_t st) {
+    const dim3 grid((unsigned)((P4 + kRobustBlock - 1) / kRobustBlock));
+    hipLaunchKernelGGL((k_mean_around_median<KP, W>), grid, dim3(kRobustBlock), 0, st,
+                       reinterpret_cast<const f32x4 *>(U), ldu / 4, rows, K, keep, P4,
+                       reinterpret_cast<f32x4 *>(out));
+}
+
 }  // namespace
 }  // namespace dls
 
@@ -233,4 +372,40 @@ extern "C" int dls_trimmed_mean_f32(const float *U, int64_t ldu, const int32_t *
     else
         launch<64, 2>(U, ldu, rows, K, trim, P4, out, st);
     return check_launch("dls_trimmed_mean_f32");
+}
+
+extern "C" int dls_mean_around_median_f32(const float *U, int64_t ldu, const int32_t *rows,
+                                          int32_t K, int32_t keep, int64_t P, float *out,
+                                          dls_stream_t stream) {
+    DLS_REQUIRE(U && rows && out, DLS_EINVAL, "dls_mean_around_median_f32: null pointer");
+    DLS_REQUIRE(K >= 1 && K <= DLS_ROBUST_MAX_K, DLS_EINVAL,
+                "dls_mean_around_median_f32: K=%d (1..DLS_ROBUST_MAX_K=%d)", K, DLS_ROBUST_MAX_K);
+    DLS_REQUIRE(keep >= 1 && keep <= K, DLS_EINVAL,
+                "dls_mean_around_median_f32: keep=%d (1 <= keep <= K=%d)", keep, K);
+    DLS_REQUIRE(P >= 0, DLS_EINVAL, "dls_mean_around_median_f32: P=%lld", (long long)P);
+    DLS_REQUIRE(P % 4 == 0 && ldu % 4 == 0 && ldu >= P, DLS_ELAYOUT,
+                "dls_mean_around_median_f32: P=%lld and ldu=%lld must be multiples of 4, ldu >= P",
+                (long long)P, (long long)ldu);
+    DLS_REQUIRE(aligned16(U) && aligned16(out), DLS_ELAYOUT,
+                "dls_mean_around_median_f32: 16-byte alignment");
+    if (P == 0) return DLS_OK;
+    const int64_t P4 = P / 4;
+    DLS_REQUIRE((P4 + kRobustBlock - 1) / kRobustBlock < (int64_t)1 << 31, DLS_EINVAL,
+                "dls_mean_around_median_f32: grid too large");
+    hipStream_t st = as_stream(stream);
+    if (K == 1)
+        launch_window<1>(U, ldu, rows, K, keep, P4, out, st);
+    else if (K == 2)
+        launch_window<2>(U, ldu, rows, K, keep, P4, out, st);
+    else if (K <= 4)
+        launch_window<4>(U, ldu, rows, K, keep, P4, out, st);
+    else if (K <= 8)
+        launch_window<8>(U, ldu, rows, K, keep, P4, out, st);
+    else if (K <= 16)
+        launch_window<16>(U, ldu, rows, K, keep, P4, out, st);
+    else if (K <= 32)
+        launch_window<32>(U, ldu, rows, K, keep, P4, out, st);
+    else
+        launch_window<64, 1>(U, ldu, rows, K, keep, P4, out, st);
+    return check_launch("dls_mean_around_median_f32");
 }

@@ -18,7 +18,9 @@ from .server import Server
 log = logging.getLogger("distributed_learning_simulator_amd")
 
 _MODES = {"exact": _native.FEDAVG_EXACT, "fma": _native.FEDAVG_FMA}
-_RULES = ("mean", "median", "trimmed_mean", "multi_krum", "geometric_median", "centered_clip")
+_RULES = ("mean", "median", "trimmed_mean", "multi_krum", "geometric_median", "centered_clip",
+          "mean_around_median", "bulyan")
+_BYZANTINE_RULES = ("multi_krum", "bulyan", "mean_around_median")
 _GM_ITERS, _GM_NU = 3, 1e-6  # the defaults of RFA (Pillutla et al.)
 _CC_TAU, _CC_ITERS = 10.0, 3
 
@@ -58,7 +60,18 @@ class FedServer(Server):
       the other robust rules it ignores the sample counts; a client with a
       non-finite update is rejected.  ``last_clip_scales`` holds the last step's
       scale per worker (1.0: not clipped) beside ``last_distances`` /
-      ``last_rejected``.
+      ``last_rejected``;
+    * ``"mean_around_median"``: per coordinate, the K - ``byzantine`` consecutive
+      sorted values closest to the median are averaged (MeaMed, Xie, Koyejo & Gupta
+      2018; dls_mean_around_median_f32): unlike the trimmed mean the kept window is
+      not centred, it slides to where the values cluster.  2*``byzantine`` < K;
+    * ``"bulyan"``: Bulyan (El Mhamdi, Guerraoui & Rouault 2018): K - 2*``byzantine``
+      whole updates are chosen by iterated Krum on the squared distances
+      (dls_pairwise_sqdist_f32), then every coordinate is the mean of the K -
+      4*``byzantine`` chosen values closest to their median
+      (dls_mean_around_median_f32), so a single poisoned coordinate cannot hide
+      inside a small Euclidean distance.  4*``byzantine`` + 3 <= K.
+      ``last_selection`` (in pick order) / ``last_scores`` hold the latest choice.
 
     The robust rules ignore the clients' sample counts n_i (every client counts
     once), take at most ``_native.ROBUST_MAX_K`` clients and are bit-identical for
@@ -112,7 +125,8 @@ class FedServer(Server):
         if krum_select is not None and (isinstance(krum_select, bool)
                                         or not isinstance(krum_select, int)):
             raise ValueError(f"krum_select must be an integer or None, not {krum_select!r}")
-        if rule != "multi_krum" and (byzantine != 0 or krum_select is not None):
+        if (rule not in _BYZANTINE_RULES and byzantine != 0) or (rule != "multi_krum"
+                                                                  and krum_select is not None):
             raise ValueError(f"byzantine={byzantine} / krum_select={krum_select} needs "
                              f"aggregation_rule='multi_krum', not {rule!r}")
         if isinstance(gm_iters, bool) or not isinstance(gm_iters, int) or gm_iters < 1:
@@ -156,6 +170,13 @@ class FedServer(Server):
                 if krum_select is not None and not 1 <= krum_select <= worker_number - byzantine:
                     raise ValueError(f"krum_select={krum_select} must be in 1..worker_number - "
                                      f"byzantine = {worker_number - byzantine}")
+            if rule == "mean_around_median" and 2 * byzantine >= worker_number:
+                raise ValueError(f"byzantine={byzantine} leaves no majority of worker_number="
+                                 f"{worker_number} clients (2*byzantine < worker_number is "
+                                 "needed)")
+            if rule == "bulyan" and 4 * byzantine + 3 > worker_number:
+                raise ValueError(f"byzantine={byzantine} is too many for worker_number="
+                                 f"{worker_number} (4*byzantine + 3 <= worker_number is needed)")
         elif rule == "multi_krum" and krum_select is not None and krum_select < 1:
             raise ValueError(f"krum_select={krum_select} must be at least 1")
 
@@ -208,10 +229,10 @@ class FedServer(Server):
             return self.__prev_model
         ids = list(client_subset)
         store = self.parameters.store
-        # multi-Krum, the geometric median and centered clipping report, break ties and
+        # multi-Krum, Bulyan, the geometric median and centered clipping report, break ties and
         # order by worker id (no subclass that overrides _aggregate runs those rules)
         extra = {"ids": ids} if self.aggregation_rule in ("multi_krum", "geometric_median",
-                                                          "centered_clip") else {}
+                                                          "centered_clip", "bulyan") else {}
         flat = self._aggregate(store, [self.parameters.row_of(i) for i in ids],
                                [self.parameters.n_of(i) for i in ids], **extra)
         return store.layout.views(flat)
@@ -231,6 +252,13 @@ class FedServer(Server):
             return self._geometric_median(store, rows, list(range(K)) if ids is None else ids)
         if self.aggregation_rule == "centered_clip":
             return self._centered_clip(store, rows, list(range(K)) if ids is None else ids)
+        if self.aggregation_rule == "bulyan":
+            return self._bulyan(store, rows, list(range(K)) if ids is None else ids)
+        if self.aggregation_rule == "mean_around_median":
+            if 2 * self.byzantine >= K:
+                raise ValueError(f"byzantine={self.byzantine} leaves no majority of a subset of "
+                                 f"{K} clients (2*byzantine < len(subset) is needed)")
+            return store.mean_around_median(rows, K - self.byzantine)
         if 2 * self.trim >= K:
             raise ValueError(f"trim={self.trim} leaves nothing of a subset of {K} clients "
                              "(2*trim < len(subset) is needed)")
@@ -249,6 +277,19 @@ class FedServer(Server):
         self.last_scores = dict(zip(ids, scores))
         chosen = set(selected)
         log.info("multi_krum: kept %s of %s clients, rejected workers %s", len(selected), K,
+                 [i for i in ids if i not in chosen])
+        return flat
+
+    def _bulyan(self, store, rows, ids):
+        K, f = len(rows), self.byzantine
+        if 4 * f + 3 > K:
+            raise ValueError(f"byzantine={f} is too many for a subset of {K} clients "
+                             "(4*byzantine + 3 <= len(subset) is needed)")
+        flat, selected, scores = store.bulyan(rows, ids, f)
+        self.last_selection = tuple(selected)
+        self.last_scores = scores
+        chosen = set(selected)
+        log.info("bulyan: kept %s of %s clients, rejected workers %s", len(selected), K,
                  [i for i in ids if i not in chosen])
         return flat
 

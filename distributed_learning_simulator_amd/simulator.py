@@ -6,7 +6,9 @@
         [--aggregation_rule median | --aggregation_rule trimmed_mean --trim 2 |
          --aggregation_rule multi_krum --byzantine 2 [--krum_select 1] |
          --aggregation_rule geometric_median [--gm_iters 3] [--gm_nu 1e-6] |
-         --aggregation_rule centered_clip [--cc_tau 10.0] [--cc_iters 3]]
+         --aggregation_rule centered_clip [--cc_tau 10.0] [--cc_iters 3] |
+         --aggregation_rule mean_around_median --byzantine 2 |
+         --aggregation_rule bulyan --byzantine 2]
 
 Same flags and flow as the reference: IID split of the training set over the
 workers (:48-50), a tester on the test split (:51), ``factory.get_server``
@@ -68,10 +70,15 @@ def get_config(argv=None):
     # coordinate, or multi-Krum, which scores whole updates by their squared
     # distances to their nearest neighbours, assuming --byzantine bad clients, and
     # averages the --krum_select best-scored ones (default: all but --byzantine;
-    # 1 is classic Krum).  The robust rules ignore the clients' sample counts.
+    # 1 is classic Krum), or the mean around the median, which averages per coordinate
+    # the all-but---byzantine values closest to the median, or Bulyan, which chooses all
+    # but 2 x --byzantine updates by iterated Krum and then averages per coordinate the
+    # chosen values closest to their median, all but another 2 x --byzantine (it needs
+    # 4 x --byzantine + 3 clients).  The robust rules ignore the clients' sample counts.
     ap.add_argument("--aggregation_rule", type=str, default="mean",
                     choices=("mean", "median", "trimmed_mean", "multi_krum",
-                             "geometric_median", "centered_clip"))
+                             "geometric_median", "centered_clip", "mean_around_median",
+                             "bulyan"))
     ap.add_argument("--trim", type=int, default=0)
     ap.add_argument("--byzantine", type=int, default=0)
     ap.add_argument("--krum_select", type=int, default=None)
@@ -95,7 +102,8 @@ def server_kwargs(config):
     worker_number / multi_process: the aggregation mode for the FedAvg-based
     servers (sign_SGD votes; it has no FedAvg), the utility metric for the two
     Shapley servers, the aggregation rule and its trim count when the rule is not the
-    default mean, multi-Krum's byzantine / krum_select, the geometric median's
+    default mean, multi-Krum's byzantine / krum_select, byzantine for Bulyan and the
+    mean around the median, the geometric median's
     gm_iters / gm_nu and centered clipping's cc_tau / cc_iters for those rules alone."""
     if config.distributed_algorithm == "sign_SGD":
         return {}
@@ -108,6 +116,8 @@ def server_kwargs(config):
         if config.aggregation_rule == "multi_krum":
             kwargs["byzantine"] = getattr(config, "byzantine", 0)
             kwargs["krum_select"] = getattr(config, "krum_select", None)
+        if config.aggregation_rule in ("bulyan", "mean_around_median"):
+            kwargs["byzantine"] = getattr(config, "byzantine", 0)
         if config.aggregation_rule == "geometric_median":
             kwargs["gm_iters"] = getattr(config, "gm_iters", 3)
             kwargs["gm_nu"] = getattr(config, "gm_nu", 1e-6)

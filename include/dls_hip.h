@@ -138,6 +138,40 @@ int dls_subset_fedavg_union_f32(const float *U, int64_t ldu, const int32_t *urow
 int dls_trimmed_mean_f32(const float *U, int64_t ldu, const int32_t *rows, int32_t K,
                          int32_t trim, int64_t P, float *out, dls_stream_t stream);
 
+/* Mean around the median (MeaMed, Xie, Koyejo & Gupta 2018), which is also stage 2
+ * of Bulyan (El Mhamdi, Guerraoui & Rouault 2018): per coordinate the mean of the
+ * `keep` values closest to the median.  Unlike the trimmed mean the kept window
+ * is not centred in the sorted order: it slides, per coordinate, to where the
+ * values cluster.  Operands, layout rules and checks of dls_trimmed_mean_f32 (rows
+ * device int32 [K], 1 <= K <= DLS_ROBUST_MAX_K; P, ldu multiples of 4, ldu >= P; U
+ * and out 16-byte aligned; every check, the null pointers included, before any
+ * device call; P == 0 returns 0 without a launch), with 1 <= keep <= K in place of
+ * trim.  Per flat coordinate, independently:
+ *   1. order the K values ascending in the total order of dls_trimmed_mean_f32
+ *      (-0.0 below +0.0, every NaN above +inf): v[0] .. v[K-1];
+ *   2. the median: med = v[(K-1)/2]'s own bits for an odd K,
+ *      med = fl32(fl32(v[K/2-1] + v[K/2]) / 2) for an even K;
+ *   3. the window start s: the first i in 0 .. K-keep-1 for which
+ *      fl32(med - v[i]) > fl32(v[i+keep] - med) is false, s = K-keep if there is
+ *      none; a comparison with a NaN is false.  In words: a window of `keep`
+ *      consecutive sorted values slides upwards while the value leaving at the
+ *      bottom is strictly farther from the median than the value entering at the
+ *      top; an exact tie keeps the lower value.  (The true comparisons always form
+ *      a prefix of i = 0, 1, ..., so s is also their count.)
+ *   4. acc = v[s]; acc = fl32(acc + v[i]) for i = s+1 .. s+keep-1 ascending (one
+ *      rounding each); out = fl32(acc / fl32(keep)), correctly rounded.
+ *      keep == 1: out is v[s]'s own bits.  A NaN result is 0x7fc00000.
+ * Consequences: the result depends only on the multiset of each column (the same
+ * bits for any permutation of `rows`); keep == K gives the bits of
+ * dls_trimmed_mean_f32 with trim 0; as long as at most K-keep values of a column
+ * are NaN and its median is not NaN, no NaN is kept; keep == 1 with an odd K gives
+ * the bits of the median whenever the median is finite and not a zero (the steps
+ * decide elsewhere: {-0, +0, +0} gives -0, the tie keeps the lower value; with an
+ * infinite or NaN median the comparisons against it are false where they would
+ * meet inf - inf or the NaN, e.g. {1, inf, inf} gives 1). */
+int dls_mean_around_median_f32(const float *U, int64_t ldu, const int32_t *rows, int32_t K,
+                               int32_t keep, int64_t P, float *out, dls_stream_t stream);
+
 /* Pairwise squared distances between K client rows: the hot path of the
  * distance-based robust rules (Krum / multi-Krum, Blanchard et al. 2017) and of
  * client similarity.  Operands and layout rules of dls_trimmed_mean_f32 (rows
