@@ -64,9 +64,18 @@ inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 
 // range.  Floating-point ops are scale-invariant there, so checking every fp32
 // mantissa of a in [1,2) proves it for one b; tests/test_oracle_golden.py does
 // that exhaustively for adversarial divisors (and 6,000+ more were checked while
-// building).  The kernels take the fast path for 2^-60 <= |a| <= 2^60 and
-// 1 <= b <= 2^31 (host side: `fast`) and fall back to IEEE `/` otherwise
-// (zeros incl. -0, denormals, inf, nan, huge values).
+// building).  The kernels take the fast path for 2^-60 <= |a| < 2^61 (biased
+// exponent 67..187, in_fast_range below) and 1 <= b <= 2^31 (host side: `fast`)
+// and fall back to IEEE `/` otherwise (zeros incl. -0, denormals, inf, nan, huge
+// values).  The guard is a two-op exponent test placed well inside the range
+// where q0 = a*y and r stay normal for every b <= 2^31, not the edge of
+// exactness.  tests/test_gpu_division.py runs every mantissa of the binades
+// [2^-60, 2^-59) and [2^60, 2^61) and the values one ulp either side of both
+// bounds through the kernels.  No test can observe the upper bound itself:
+// Markstein's quotient is still RN(a/b) for 2^61 <= |a| < 2^62 (and well beyond)
+// with b in [1, 2^31], so moving the bound up a binade changes no bit.  What the
+// guard must keep out, and the tests do observe, is zeros (Markstein turns -0
+// into +0), denormals, inf and nan.
 //
 // Two-constant variant (Brisebarre, Muller & Raina, IEEE TC 2004): with
 // yh = RN(1/b), yl = RN(1/b - yh),  q = fma(a, yh, RN(a*yl))  is RN(a/b) for
@@ -119,7 +128,8 @@ __device__ __forceinline__ float markstein(float a, float b, float y) {
     return __builtin_fmaf(r, y, q0);
 }
 
-// 1 if 2^-60 <= |a| <= 2^60 (fast path valid), else 0.  Two VALU ops.
+// 1 if 2^-60 <= |a| < 2^61 (biased exponent 67..187: the fast path), else 0
+// (zeros, denormals, inf and nan included).  Two VALU ops.
 __device__ __forceinline__ bool in_fast_range(float a) {
     const uint32_t e = (__float_as_uint(a) >> 23) & 0xffu;  // biased exponent
     return (e - (127u - 60u)) <= 120u;

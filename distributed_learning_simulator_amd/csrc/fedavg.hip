@@ -227,8 +227,9 @@ __global__ __launch_bounds__(kBlock) void k_subset_exact(const f32x4 *__restrict
 // membership the quotient (2 ops two-constant / 3 Markstein) + the add.
 constexpr int kUnionChunk = 64;  // clients per launch (the host splits larger unions)
 
-// in_fast_range (dls_common.h) of all four: 2^-60 <= |t| < 2^61 on the bit
-// patterns (min / max of |bits|: zeros, denormals, inf and nan all fail)
+// in_fast_range (dls_common.h) of all four, the same bound 2^-60 <= |t| < 2^61
+// (biased exponent 67..187) taken on the bit patterns: min / max of |bits|, so
+// zeros, denormals, inf and nan all fail
 __device__ __forceinline__ bool all_in_fast_range(f32x4 t) {
     const uint32_t a = __float_as_uint(t.x) & 0x7fffffffu, b = __float_as_uint(t.y) & 0x7fffffffu;
     const uint32_t c = __float_as_uint(t.z) & 0x7fffffffu, d = __float_as_uint(t.w) & 0x7fffffffu;

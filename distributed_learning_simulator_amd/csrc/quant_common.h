@@ -10,7 +10,9 @@ namespace dls {
 namespace quant {
 
 __device__ __forceinline__ bool scale_fast(float sw) {
-    // |q - zp| in [1, 383]: fl(deq*n) then lies in [2^-60, 2^60] (dls_common.h)
+    // |q - zp| in [1, 383]: fl(deq*n) then lies in [2^-60, 2^60), inside the fast
+    // range 2^-60 <= |a| < 2^61 of dls_common.h; q == zp gives +0, which Markstein
+    // returns as +0 like IEEE division (sw > 0 here, so never -0)
     return sw >= 0x1p-59f && sw <= 0x1p50f;
 }
 

@@ -199,7 +199,9 @@ def test_gtg_shapley_golden():
 
 
 @pytest.mark.parametrize("b", [1.0, 3.0, 7.0, 550.0, 55000.0, 16777215.0, 33554432.0, 123457.0,
-                               2147483648.0])
+                               2147483648.0,
+                               # test_two_constant_division_check_without_gpu's divisors
+                               55123.0, 49972.0, 1024.0, 100.0])
 def test_kernel_fast_division_exhaustive(b):
     """The kernels' guarded fp32 division equals IEEE a/b for every mantissa."""
     assert _c.fastdiv_check(b) == 0
