@@ -7,6 +7,7 @@ CPU or PyTorch fallback: if the library cannot be loaded, or a tensor is not on
 the GPU, the call fails loudly.
 """
 import ctypes
+import math
 import os
 import threading
 
@@ -66,6 +67,7 @@ SIGNATURES = {
                                     _i32),
     "dls_trimmed_mean_f32": ([_p, _i64, _p, _i32, _i32, _i64, _p, _p], _i32),
     "dls_mean_around_median_f32": ([_p, _i64, _p, _i32, _i32, _i64, _p, _p], _i32),
+    "dls_craft_rows_f32": ([_p, _i64, _p, _i32, _p, _i32, _f32, _f32, _p, _i64, _p], _i32),
     "dls_pairwise_sqdist_workspace": ([_i32, _i64], _i64),
     "dls_pairwise_sqdist_f32": ([_p, _i64, _p, _i32, _i64, _p, _p, _p], _i32),
     "dls_weiszfeld_workspace": ([_i32, _i64], _i64),
@@ -329,6 +331,40 @@ def mean_around_median(U, rows, keep, P, out, stream=None):
     _check(lib().dls_mean_around_median_f32(_ptr(U), ldu, _ptr(rows), K, keep, P, _ptr(out),
                                             _stream(stream, U)), "dls_mean_around_median_f32")
     return out
+
+
+def craft_rows(U, hrows, arows, a, b, P, base=None, stream=None):
+    """Byzantine rows crafted in place from the honest rows of U (dls_craft_rows_f32):
+    per coordinate out = base + a * (mu - base) + b * sigma, mu the ascending mean and
+    sigma the population standard deviation of the Kh = hrows.numel() honest values
+    (sigma only when b != 0; without ``base``, out = a * mu + b * sigma), written into
+    each of the Ka = arows.numel() attacker rows.  Multiply, then add, every operation
+    rounded once: the bits are those of the header's contract, the same for any order
+    of ``hrows``.  hrows and arows: int32 [1..ROBUST_MAX_K] device tables that must not
+    share a row (not checked here: the tables live on the device;
+    ``ClientUpdateStore.craft`` checks its host lists); a, b finite; base: None or an
+    fp32 vector of at least P elements; U, P as in pairwise_sqdist.  Returns U."""
+    fn = "craft_rows"
+    Kh, P, ldu = _rows_operands(fn, U, hrows, P)
+    _rows_operands(fn, U, arows, P)
+    a, b = float(a), float(b)
+    if not (math.isfinite(a) and math.isfinite(b)):
+        raise RuntimeError(f"{fn}: a={a} and b={b} must be finite")
+    if base is not None and (not torch.is_tensor(base) or base.dtype != torch.float32
+                             or base.dim() != 1 or base.numel() < P
+                             or (base.numel() > 1 and base.stride(0) != 1)):
+        raise RuntimeError(f"{fn}: base must be an fp32 vector of at least P={P} elements "
+                           "with unit stride")
+    _check_same_device(fn, U, hrows=hrows, arows=arows, base=base)
+    if U.data_ptr() % 16 != 0 or (base is not None and base.data_ptr() % 16 != 0):
+        raise RuntimeError(f"{fn}: U and base must be 16-byte aligned")
+    _ptr(U), _ptr(hrows), _ptr(arows), _ptr(base)  # no CPU path
+    if P == 0:
+        return U
+    _check(lib().dls_craft_rows_f32(_ptr(U), ldu, _ptr(hrows), Kh, _ptr(arows), arows.numel(),
+                                    a, b, _ptr(base), P, _stream(stream, U)),
+           "dls_craft_rows_f32")
+    return U
 
 
 def _point_operands(fn, U, K, P, z, dist2, name):

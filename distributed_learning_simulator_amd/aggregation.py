@@ -13,6 +13,7 @@ HBM layout:
 """
 import heapq
 import math
+import statistics
 import threading
 
 import torch
@@ -208,6 +209,48 @@ def clip_scales(dist2, tau):
                                       dtype=torch.float64).float().tolist()
 
 
+ATTACKS = ("alie", "ipm", "sign_flip")
+
+
+def alie_z(n, f):
+    """The z of "a little is enough" (Baruch, Baruch & Goldberg 2019) for ``n`` clients of
+    which ``f`` are Byzantine, as the authors' code computes it: s = n // 2 + 1 - f
+    honest clients must be won over for a majority, p = (n - f - s) / (n - f), and z is
+    the standard normal quantile of p, so that mean - z * std still lies among the
+    honest values of the s clients farthest out on that side.  The result is negative
+    for a small f (p < 1/2: (n, f) = (10, 1) gives about -0.14) and is passed through
+    as it is, like the authors' code does.  ValueError unless 1 <= f < n and
+    0 < p < 1."""
+    if any(isinstance(v, bool) or not isinstance(v, int) for v in (n, f)) or not 1 <= f < n:
+        raise ValueError(f"alie_z needs integers 1 <= f < n, not n={n!r}, f={f!r}")
+    s = n // 2 + 1 - f
+    p = (n - f - s) / (n - f)
+    if not 0.0 < p < 1.0:
+        raise ValueError(f"alie_z: p = (n - f - s) / (n - f) = {p} with s = n // 2 + 1 - f = {s} "
+                         f"is not inside (0, 1) (n={n}, f={f})")
+    return statistics.NormalDist().inv_cdf(p)
+
+
+def attack_coefficients(attack, n, f, z=None, eps=0.1):
+    """(a, b, uses_base) of ``ClientUpdateStore.craft`` for the crafted attacks, ``n``
+    clients of which ``f`` are Byzantine: "alie" sends mean - z * std of the honest
+    updates, (1.0, -z, False), z = ``alie_z(n, f)`` unless given; "ipm" (inner product
+    manipulation, Xie, Koyejo & Gupta 2019) sends -eps times the honest mean update
+    relative to the previous global model, (-eps, 0.0, True).  ValueError: another
+    attack name, or a z / eps that is not a finite number."""
+    def finite(name, v):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+            raise ValueError(f"{name} must be a finite number, not {v!r}")
+        return float(v)
+
+    if attack == "alie":
+        z = alie_z(n, f) if z is None else finite("z", z)
+        return 1.0, -z, False
+    if attack == "ipm":
+        return -finite("eps", eps), 0.0, True
+    raise ValueError(f"attack_coefficients: attack must be 'alie' or 'ipm', not {attack!r}")
+
+
 class ClientUpdateStore:
     """``acquire_range = (lo, hi)``: this process's own clients take rows [lo, hi)
     only (a fixed block; the sharded Shapley servers all-gather every rank's block
@@ -309,6 +352,57 @@ class ClientUpdateStore:
         r = rows if torch.is_tensor(rows) else _i32(rows, self.device)
         _native.mean_around_median(self.U[:, c0:], r, keep, c1 - c0, out)
         return out
+
+    def craft(self, honest_rows, attacker_rows, a, b, base=None, cols=None):
+        """Rewrite the attacker rows in place from the honest rows (dls_craft_rows_f32):
+        per flat element base + a * (mu - base) + b * sigma, mu the ascending mean and
+        sigma the population standard deviation of the honest values (a * mu + b *
+        sigma without ``base``; ``attack_coefficients`` has the a, b of ALIE and IPM).
+        The sample counts play no part, and the result is the same bits for any order
+        of ``honest_rows``.  Both are host lists of row indices, 1..
+        _native.ROBUST_MAX_K each; ValueError if one is empty or too long, holds a
+        duplicate, or the two share a row.  ``base``: an fp32 device vector of the
+        reduced length; ``cols`` as in ``fedavg``.  Returns nothing."""
+        honest = [int(r) for r in honest_rows]
+        bad = [int(r) for r in attacker_rows]
+        for name, rows in (("honest_rows", honest), ("attacker_rows", bad)):
+            if not 1 <= len(rows) <= _native.ROBUST_MAX_K:
+                raise ValueError(f"craft: {name} holds {len(rows)} rows "
+                                 f"(1..ROBUST_MAX_K={_native.ROBUST_MAX_K})")
+            if len(set(rows)) != len(rows):
+                raise ValueError(f"craft: {name} holds a row twice: {rows}")
+            if min(rows) < 0 or max(rows) >= self.U.shape[0]:
+                raise ValueError(f"craft: {name} {rows} outside the store's "
+                                 f"{self.U.shape[0]} rows")
+        both = sorted(set(honest) & set(bad))
+        if both:
+            raise ValueError(f"craft: rows {both} are both honest and attacker rows")
+        c0, c1 = cols if cols is not None else (0, self.layout.P)
+        _native.craft_rows(self.U[:, c0:], _i32(honest, self.device), _i32(bad, self.device),
+                           a, b, c1 - c0, base=base)
+
+    def sign_flip(self, rows, scale, base=None):
+        """Rewrite each listed row in place as x <- base - scale * (x - base), the
+        sign-flipping attack on the update relative to ``base`` (an fp32 device vector
+        of ``layout.P`` elements, the previous global model); without ``base``, x <-
+        -(scale * x).  Three elementwise fp32 operations in this order, each rounded
+        once: d = x - base; d *= fl32(scale); x = base - d."""
+        if isinstance(scale, bool) or not isinstance(scale, (int, float)) \
+                or not math.isfinite(scale):
+            raise ValueError(f"scale must be a finite number, not {scale!r}")
+        rows = [int(r) for r in rows]
+        if len(set(rows)) != len(rows):
+            raise ValueError(f"sign_flip: a row is listed twice: {rows}")
+        scale = torch.tensor(float(scale), dtype=torch.float32).item()  # its fp32 value
+        for r in rows:
+            x = self.U[r]
+            if base is None:
+                d = x * scale
+                torch.neg(d, out=x)
+            else:
+                d = x - base
+                d *= scale
+                torch.sub(base, d, out=x)
 
     def pairwise_sqdist(self, rows, cols=None):
         """Squared Euclidean distances between the given rows (dls_pairwise_sqdist_f32):

@@ -145,6 +145,10 @@ __device__ __forceinline__ float div_ieee(float a, float b) {
     return a / b;  // hipcc default: correctly rounded fp32 division
 }
 
+__device__ __forceinline__ float sqrt_ieee(float a) {
+    return __builtin_sqrtf(a);  // hipcc default: correctly rounded fp32 square root, denormals kept
+}
+
 // Guarded exact division (one element).
 __device__ __forceinline__ float div_exact(float a, const FastDiv &d) {
     if (d.fast && in_fast_range(a)) return markstein(a, d.b, d.y);

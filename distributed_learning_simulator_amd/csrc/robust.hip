@@ -1,6 +1,7 @@
-// Coordinate-wise trimmed mean / median, and the mean around the median (second
-// half of this file), over K client rows for gfx950: the robust counterparts of the
-// FedAvg hook (servers/fed_server.py:44-66).
+// Coordinate-wise trimmed mean / median, the mean around the median (second part of
+// this file) and the crafted Byzantine rows they are measured against (third part),
+// over K client rows for gfx950: the robust counterparts of the FedAvg hook
+// (servers/fed_server.py:44-66).
 //
 // Per flat coordinate, independently (include/dls_hip.h has the contract):
 //   sort the K values ascending (-0 below +0, every NaN above +inf), drop the
@@ -17,6 +18,7 @@
 // instantiated for KP = 1, 2, 4, ..., 64 wires; wires K..KP-1 hold the top key.
 // Every register index is a compile-time constant (no scratch, no LDS), and one
 // lane produces each output (no atomics, no split reduction).
+#include <cmath>
 #include <utility>
 
 #include "dls_common.h"
@@ -334,6 +336,127 @@ void launch_window(const float *U, int64_t ldu, const int32_t *rows, int K, int 
                        reinterpret_cast<f32x4 *>(out));
 }
 
+// ------------------------------------------- crafted Byzantine rows (ALIE, IPM)
+// dls_craft_rows_f32: out = base + a * (mu - base) + b * sigma per coordinate, mu and
+// sigma the ascending mean and the population standard deviation of the Kh honest
+// values, written into every attacker row.  Same loads, keys and network as
+// k_trimmed_mean.  The sorted keys stay in registers and are decoded twice: once for
+// the ascending sum, and, when b != 0 (wave-uniform), once more for the deviations
+//   d = fl(v[j] - mu); s = fmaf(d, d, s),
+// where a wire >= Kh (a NaN) is masked out by a wave-uniform select.  Nothing beside
+// that fmaf is contracted (the library is built with -ffp-contract=off).
+template <int KP, int W, int C0>
+__device__ __forceinline__ void craft_coords(const f32x4 (&x)[KP], int K, float a, float b,
+                                             bool has_base, const f32x4 &bs, f32x4 &res) {
+    uint32_t v[W][KP];
+#pragma unroll
+    for (int j = 0; j < KP; ++j)
+#pragma unroll
+        for (int w = 0; w < W; ++w)
+            v[w][j] = j < K ? to_key(__float_as_uint(x[j][C0 + w])) : kTopKey;  // wave-uniform
+    net_sort<KP, W>(v);
+    // the sum of reduce_coords with trim 0: from -0, so that v[0] keeps its own bits
+    float mu[W], sg[W];
+#pragma unroll
+    for (int w = 0; w < W; ++w) mu[w] = -0.f;
+#pragma unroll
+    for (int j = 0; j < KP; ++j) {
+        const bool kept = j < K;  // wave-uniform; t + -0 == t
+#pragma unroll
+        for (int w = 0; w < W; ++w) mu[w] = mu[w] + (kept ? from_key(v[w][j]) : -0.f);
+    }
+    const float fk = (float)K;
+    if (K > 1) {
+#pragma unroll
+        for (int w = 0; w < W; ++w) mu[w] = div_ieee(mu[w], fk);
+    }
+    const bool use_b = b != 0.f;  // wave-uniform
+#pragma unroll
+    for (int w = 0; w < W; ++w) sg[w] = 0.f;
+    if (use_b) {
+        float s[W];
+#pragma unroll
+        for (int w = 0; w < W; ++w) s[w] = 0.f;
+#pragma unroll
+        for (int j = 0; j < KP; ++j) {
+            const bool kept = j < K;
+#pragma unroll
+            for (int w = 0; w < W; ++w) {
+                const float d = from_key(v[w][j]) - mu[w];
+                const float q = __builtin_fmaf(d, d, s[w]);
+                s[w] = kept ? q : s[w];
+            }
+        }
+        if (K > 1) {
+#pragma unroll
+            for (int w = 0; w < W; ++w) s[w] = div_ieee(s[w], fk);
+        }
+#pragma unroll
+        for (int w = 0; w < W; ++w) sg[w] = sqrt_ieee(s[w]);
+    }
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+        const float z = bs[C0 + w];
+        const float t = has_base ? mu[w] - z : mu[w];
+        float r = a * t;
+        const float e = b * sg[w];
+        r = use_b ? r + e : r;
+        res[C0 + w] = quiet(has_base ? z + r : r);
+    }
+}
+
+// The loads of k_trimmed_mean over the honest rows; the attacker rows reach the wave
+// the same way (a per-lane table and v_readlane) and take one 16-byte store each.
+template <int KP, int W>
+__global__ __launch_bounds__(kRobustBlock) void k_craft_rows(
+    f32x4 *Uv, int64_t ldu4, const int32_t *__restrict__ hrows, int K,
+    const int32_t *__restrict__ arows, int Ka, float a, float b, const f32x4 *base, int64_t P4) {
+    const int lane = __lane_id();
+    const int64_t i0 = ((int64_t)blockIdx.x * (kRobustBlock / 64) + (threadIdx.x >> 6)) * 64 + lane;
+    const int64_t iq = i0 < P4 ? i0 : P4 - 1;  // every lane stays: the tables need all 64
+    const int tr = hrows[min(lane, K - 1)];
+    const int ta = arows[min(lane, Ka - 1)];
+    f32x4 x[KP];
+#pragma unroll
+    for (int j = 0; j < KP; ++j) {
+        const int64_t r = __builtin_amdgcn_readlane(tr, j);
+        x[j] = __builtin_nontemporal_load(Uv + r * ldu4 + iq);
+    }
+    const bool has_base = base != nullptr;  // wave-uniform
+    f32x4 bs = {0.f, 0.f, 0.f, 0.f};
+    if (has_base) bs = base[iq];
+    f32x4 res;
+    if constexpr (W == 4) {
+        craft_coords<KP, 4, 0>(x, K, a, b, has_base, bs, res);
+    } else if constexpr (W == 2) {
+        craft_coords<KP, 2, 0>(x, K, a, b, has_base, bs, res);
+        __builtin_amdgcn_sched_barrier(0);  // one pass's keys in registers at a time
+        craft_coords<KP, 2, 2>(x, K, a, b, has_base, bs, res);
+    } else {
+        static_assert(W == 1, "coordinates per pass");
+        craft_coords<KP, 1, 0>(x, K, a, b, has_base, bs, res);
+        __builtin_amdgcn_sched_barrier(0);
+        craft_coords<KP, 1, 1>(x, K, a, b, has_base, bs, res);
+        __builtin_amdgcn_sched_barrier(0);
+        craft_coords<KP, 1, 2>(x, K, a, b, has_base, bs, res);
+        __builtin_amdgcn_sched_barrier(0);
+        craft_coords<KP, 1, 3>(x, K, a, b, has_base, bs, res);
+    }
+    for (int j = 0; j < Ka; ++j) {  // wave-uniform trip count and row
+        const int64_t r = __builtin_amdgcn_readlane(ta, j);
+        if (i0 < P4) Uv[r * ldu4 + i0] = res;
+    }
+}
+
+template <int KP, int W = 4>
+void launch_craft(float *U, int64_t ldu, const int32_t *hrows, int K, const int32_t *arows, int Ka,
+                  float a, float b, const float *base, int64_t P4, hipStream_t st) {
+    const dim3 grid((unsigned)((P4 + kRobustBlock - 1) / kRobustBlock));
+    hipLaunchKernelGGL((k_craft_rows<KP, W>), grid, dim3(kRobustBlock), 0, st,
+                       reinterpret_cast<f32x4 *>(U), ldu / 4, hrows, K, arows, Ka, a, b,
+                       reinterpret_cast<const f32x4 *>(base), P4);
+}
+
 }  // namespace
 }  // namespace dls
 
@@ -408,4 +531,42 @@ extern "C" int dls_mean_around_median_f32(const float *U, int64_t ldu, const int
     else
         launch_window<64, 1>(U, ldu, rows, K, keep, P4, out, st);
     return check_launch("dls_mean_around_median_f32");
+}
+
+extern "C" int dls_craft_rows_f32(float *U, int64_t ldu, const int32_t *hrows, int32_t Kh,
+                                  const int32_t *arows, int32_t Ka, float a, float b,
+                                  const float *base, int64_t P, dls_stream_t stream) {
+    DLS_REQUIRE(U && hrows && arows, DLS_EINVAL, "dls_craft_rows_f32: null pointer");
+    DLS_REQUIRE(Kh >= 1 && Kh <= DLS_ROBUST_MAX_K, DLS_EINVAL,
+                "dls_craft_rows_f32: Kh=%d (1..DLS_ROBUST_MAX_K=%d)", Kh, DLS_ROBUST_MAX_K);
+    DLS_REQUIRE(Ka >= 1 && Ka <= DLS_ROBUST_MAX_K, DLS_EINVAL,
+                "dls_craft_rows_f32: Ka=%d (1..DLS_ROBUST_MAX_K=%d)", Ka, DLS_ROBUST_MAX_K);
+    DLS_REQUIRE(std::isfinite(a) && std::isfinite(b), DLS_EINVAL,
+                "dls_craft_rows_f32: a=%g and b=%g must be finite", (double)a, (double)b);
+    DLS_REQUIRE(P >= 0, DLS_EINVAL, "dls_craft_rows_f32: P=%lld", (long long)P);
+    DLS_REQUIRE(P % 4 == 0 && ldu % 4 == 0 && ldu >= P, DLS_ELAYOUT,
+                "dls_craft_rows_f32: P=%lld and ldu=%lld must be multiples of 4, ldu >= P",
+                (long long)P, (long long)ldu);
+    DLS_REQUIRE(aligned16(U) && aligned16(base), DLS_ELAYOUT,
+                "dls_craft_rows_f32: 16-byte alignment");
+    if (P == 0) return DLS_OK;
+    const int64_t P4 = P / 4;
+    DLS_REQUIRE((P4 + kRobustBlock - 1) / kRobustBlock < (int64_t)1 << 31, DLS_EINVAL,
+                "dls_craft_rows_f32: grid too large");
+    hipStream_t st = as_stream(stream);
+    if (Kh == 1)
+        launch_craft<1>(U, ldu, hrows, Kh, arows, Ka, a, b, base, P4, st);
+    else if (Kh == 2)
+        launch_craft<2>(U, ldu, hrows, Kh, arows, Ka, a, b, base, P4, st);
+    else if (Kh <= 4)
+        launch_craft<4>(U, ldu, hrows, Kh, arows, Ka, a, b, base, P4, st);
+    else if (Kh <= 8)
+        launch_craft<8>(U, ldu, hrows, Kh, arows, Ka, a, b, base, P4, st);
+    else if (Kh <= 16)
+        launch_craft<16>(U, ldu, hrows, Kh, arows, Ka, a, b, base, P4, st);
+    else if (Kh <= 32)
+        launch_craft<32>(U, ldu, hrows, Kh, arows, Ka, a, b, base, P4, st);
+    else
+        launch_craft<64, 2>(U, ldu, hrows, Kh, arows, Ka, a, b, base, P4, st);
+    return check_launch("dls_craft_rows_f32");
 }

@@ -95,6 +95,9 @@ def allreduce_chunked(flat, chunks=3, group=None, produce=None):
 
 
 class _ShardedMixin:
+    _attack_unsupported = ("a rank of the sharded servers holds only its own clients' rows, "
+                           "not every honest update the attackers craft from")
+
     def _init_shard(self, worker_number, group, chunks):
         # before FedServer.__init__, which publishes the initial broadcast to
         # clients_per_round consumers
@@ -145,7 +148,9 @@ class ShardedFedServer(_ShardedMixin, FedServer):
     ``"worker_id"`` sorts by id: the same bits on every run.
 
     ``aggregation_rule`` other than "mean" raises ``ValueError``: a rank holds only
-    its own clients' rows, and a coordinate's median is not a sum over ranks."""
+    its own clients' rows, and a coordinate's median is not a sum over ranks.  For the
+    same reason ``attack`` raises on every sharded server: the attackers' updates are
+    crafted from all honest rows."""
 
     _robust_unsupported = ("the sharded servers reduce each rank's own clients and sum over "
                            "ranks, which a coordinate-wise order statistic is not")

@@ -49,9 +49,11 @@ class FedQuantServer(FedServer):
     bit-exact with the reference's dequant-then-average.
 
     ``aggregation_rule`` other than "mean" raises ``ValueError``: the weighted mean is
-    fused with the dequantization here."""
+    fused with the dequantization here.  So does ``attack``: the store holds the
+    clients' int payloads, not fp32 rows to rewrite."""
 
     _robust_unsupported = "its weighted mean is fused with the dequantization of the int payloads"
+    _attack_unsupported = "its store holds the clients' int payloads, not fp32 rows to rewrite"
 
     def __init__(self, quantization_level=256, stochastic=False, seed=0, granularity="model",
                  **kwargs):

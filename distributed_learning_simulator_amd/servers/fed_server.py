@@ -9,7 +9,7 @@ import logging
 import math
 
 from .. import _native
-from ..aggregation import ClientParameters, ClientUpdateStore
+from ..aggregation import ATTACKS, ClientParameters, ClientUpdateStore, attack_coefficients
 from ..layout import ParameterLayout
 from ..model_util import ModelUtil
 from ..task_queue import RepeatedResult
@@ -23,6 +23,7 @@ _RULES = ("mean", "median", "trimmed_mean", "multi_krum", "geometric_median", "c
 _BYZANTINE_RULES = ("multi_krum", "bulyan", "mean_around_median")
 _GM_ITERS, _GM_NU = 3, 1e-6  # the defaults of RFA (Pillutla et al.)
 _CC_TAU, _CC_ITERS = 10.0, 3
+_ATTACK_EPS, _ATTACK_SCALE = 0.1, 1.0
 
 
 class FedServer(Server):
@@ -73,6 +74,23 @@ class FedServer(Server):
       inside a small Euclidean distance.  4*``byzantine`` + 3 <= K.
       ``last_selection`` (in pick order) / ``last_scores`` hold the latest choice.
 
+    ``attack`` makes the workers listed in ``attackers`` Byzantine: once a round's
+    updates have all arrived, their rows are rewritten in place before anything reads
+    them, so hooks, ``self.parameters[w]``, Shapley coalitions and every rule above see
+    the attacker exactly as if the worker had sent the crafted update.
+
+    * ``"alie"``: "a little is enough" (Baruch, Baruch & Goldberg 2019): every attacker
+      sends, per coordinate, mean - z * std of the honest updates
+      (dls_craft_rows_f32); z = ``attack_z``, by default ``aggregation.alie_z`` of the
+      worker and attacker counts;
+    * ``"ipm"``: inner product manipulation (Xie, Koyejo & Gupta 2019): every attacker
+      sends -``attack_eps`` times the honest mean update, taken relative to the
+      previous global model (relative to zero while there is none);
+    * ``"sign_flip"``: every attacker sends its own update mirrored at the previous
+      global model and scaled by ``attack_scale``.
+
+    ``last_attack`` holds the latest round's attack, attackers and coefficients.
+
     The robust rules ignore the clients' sample counts n_i (every client counts
     once), take at most ``_native.ROBUST_MAX_K`` clients and are bit-identical for
     any arrival order.  Hooks, ``prev_model``, ``get_metric`` and the round protocol
@@ -80,14 +98,19 @@ class FedServer(Server):
 
     # why a subclass cannot run the robust rules (None: it can)
     _robust_unsupported = None
+    # why a subclass cannot run the Byzantine client attacks (None: it can)
+    _attack_unsupported = None
 
     def __init__(self, aggregation_mode="exact", aggregation_rule="mean", trim=0, byzantine=0,
                  krum_select=None, gm_iters=_GM_ITERS, gm_nu=_GM_NU, cc_tau=_CC_TAU,
-                 cc_iters=_CC_ITERS, **kwargs):
+                 cc_iters=_CC_ITERS, attack=None, attackers=(), attack_z=None,
+                 attack_eps=_ATTACK_EPS, attack_scale=_ATTACK_SCALE, **kwargs):
         if aggregation_mode not in _MODES:
             raise ValueError(f"aggregation_mode must be one of {sorted(_MODES)}, not {aggregation_mode!r}")
         self._check_rule(aggregation_rule, trim, aggregation_mode, kwargs.get("worker_number"),
                          byzantine, krum_select, gm_iters, gm_nu, cc_tau, cc_iters)
+        attackers = self._check_attack(attack, attackers, attack_z, attack_eps, attack_scale,
+                                       kwargs.get("worker_number"))
         super().__init__(**kwargs)
         _native.require_gpu()
         self.round = 0
@@ -105,6 +128,12 @@ class FedServer(Server):
         self.cc_tau = float(cc_tau)
         self.cc_iters = cc_iters
         self.last_clip_scales = {}
+        self.attack = attack
+        self.attackers = attackers
+        self.attack_z = None if attack_z is None else float(attack_z)
+        self.attack_eps = float(attack_eps)
+        self.attack_scale = float(attack_scale)
+        self.last_attack = {}
         self.parameters: ClientParameters = ClientParameters(self._make_store)
         self.__prev_model = copy.deepcopy(
             ModelUtil(self.tester.model).get_parameter_dict()) if self.tester is not None else {}
@@ -179,6 +208,65 @@ class FedServer(Server):
                                  f"{worker_number} (4*byzantine + 3 <= worker_number is needed)")
         elif rule == "multi_krum" and krum_select is not None and krum_select < 1:
             raise ValueError(f"krum_select={krum_select} must be at least 1")
+
+    @classmethod
+    def _check_attack(cls, attack, attackers, attack_z=None, attack_eps=_ATTACK_EPS,
+                      attack_scale=_ATTACK_SCALE, worker_number=None):
+        """The sorted tuple of attacker ids; ValueError for what no round could run."""
+        if attack is not None and attack not in ATTACKS:
+            raise ValueError(f"attack must be None or one of {list(ATTACKS)}, not {attack!r}")
+        try:
+            ids = list(attackers)
+        except TypeError:
+            raise ValueError(f"attackers must be a collection of worker ids, not {attackers!r}")
+        if any(isinstance(w, bool) or not isinstance(w, int) or w < 0 for w in ids):
+            raise ValueError(f"attackers must be non-negative integer worker ids, not {ids!r}")
+        if len(set(ids)) != len(ids):
+            raise ValueError(f"attackers must be distinct worker ids, not {ids!r}")
+        for name, v in (("attack_z", attack_z), ("attack_eps", attack_eps),
+                        ("attack_scale", attack_scale)):
+            if v is not None and (isinstance(v, bool) or not isinstance(v, (int, float))
+                                  or not math.isfinite(v)):
+                raise ValueError(f"{name} must be a finite number, not {v!r}")
+        if attack is None and ids:
+            raise ValueError(f"attackers={ids} needs an attack, one of {list(ATTACKS)}")
+        if attack != "alie" and attack_z is not None:
+            raise ValueError(f"attack_z={attack_z} needs attack='alie', not {attack!r}")
+        if attack != "ipm" and attack_eps != _ATTACK_EPS:
+            raise ValueError(f"attack_eps={attack_eps} needs attack='ipm', not {attack!r}")
+        if attack != "sign_flip" and attack_scale != _ATTACK_SCALE:
+            raise ValueError(f"attack_scale={attack_scale} needs attack='sign_flip', not "
+                             f"{attack!r}")
+        if attack is None:
+            return ()
+        if cls._attack_unsupported is not None:
+            raise ValueError(
+                f"{cls.__name__} does not support attack={attack!r} "
+                f"({cls._attack_unsupported}); the one-process FedServer "
+                "(factory.get_server('fed', ...)) and the one-process Shapley servers are the "
+                "servers that run the Byzantine client attacks")
+        if not ids:
+            raise ValueError(f"attack={attack!r} needs attackers, a non-empty collection of "
+                             "worker ids")
+        if len(ids) > _native.ROBUST_MAX_K:
+            raise ValueError(f"attack={attack!r} takes at most ROBUST_MAX_K="
+                             f"{_native.ROBUST_MAX_K} attackers, not {len(ids)}")
+        if worker_number is not None:
+            if max(ids) >= worker_number:
+                raise ValueError(f"attackers={ids} must be worker ids in 0..worker_number - 1 = "
+                                 f"{worker_number - 1}")
+            if attack != "sign_flip":
+                honest = worker_number - len(ids)
+                if honest < 1:
+                    raise ValueError(f"attack={attack!r} needs at least one honest worker, "
+                                     f"attackers={ids} leaves none of worker_number="
+                                     f"{worker_number}")
+                if honest > _native.ROBUST_MAX_K:
+                    raise ValueError(f"attack={attack!r} takes at most ROBUST_MAX_K="
+                                     f"{_native.ROBUST_MAX_K} honest workers, not {honest}")
+                if attack == "alie" and attack_z is None:
+                    attack_coefficients("alie", worker_number, len(ids))  # alie_z's ValueError
+        return tuple(sorted(ids))
 
     @property
     def clients_per_round(self):
@@ -321,6 +409,45 @@ class FedServer(Server):
                  list(self.last_rejected), info["moved"])
         return flat
 
+    def _apply_attack(self):
+        """Rewrite the attackers' rows of the round in place (all clients have arrived)."""
+        if self.attack is None:
+            return
+        store = self.parameters.store
+        bad = [w for w in self.attackers if w in self.parameters]
+        honest = [w for w in self.parameters.keys() if w not in set(self.attackers)]
+        if len(bad) != len(self.attackers):
+            raise ValueError(f"attack={self.attack!r}: attackers "
+                             f"{[w for w in self.attackers if w not in self.parameters]} sent no "
+                             "update this round")
+        # relative to the model the clients started from, flattened as _centered_clip
+        # does it; while there is none (round 1 of a server without a tester), to zero
+        prev = self.__prev_model
+        base = None
+        if self.attack != "alie" and prev and store.accepts(prev):
+            base = store.layout.flatten(prev, device=store.U.device)
+        info = {"attack": self.attack, "attackers": self.attackers}
+        if self.attack == "sign_flip":
+            store.sign_flip([self.parameters.row_of(w) for w in bad], self.attack_scale,
+                            base=base)
+            info.update(a=-self.attack_scale, b=0.0, scale=self.attack_scale)
+        else:
+            if not honest:
+                raise ValueError(f"attack={self.attack!r} needs at least one honest worker")
+            a, b, _ = attack_coefficients(self.attack, len(self.parameters), len(bad),
+                                          z=self.attack_z, eps=self.attack_eps)
+            store.craft([self.parameters.row_of(w) for w in honest],
+                        [self.parameters.row_of(w) for w in bad], a, b, base=base)
+            info.update(a=a, b=b)
+            if self.attack == "alie":
+                info["z"] = -b
+            else:
+                info["eps"] = self.attack_eps
+        self.last_attack = info
+        log.info("attack %s: workers %s rewritten from %s honest ones (a %s, b %s, %s)",
+                 self.attack, list(self.attackers), len(honest), info["a"], info["b"],
+                 "relative to the previous model" if base is not None else "no base")
+
     def _process_worker_data(self, data, __):
         worker_id, training_dataset_size, parameter_dict = data
         self.parameters[worker_id] = (
@@ -332,6 +459,7 @@ class FedServer(Server):
             return None
         self._before_aggregate()
         self.round += 1
+        self._apply_attack()
         log.info("begin aggregating")
         avg_parameter = self.get_subset_model(self.parameters.keys())
         data = self._process_aggregated_parameter(avg_parameter)

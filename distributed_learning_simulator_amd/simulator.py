@@ -9,6 +9,9 @@
          --aggregation_rule centered_clip [--cc_tau 10.0] [--cc_iters 3] |
          --aggregation_rule mean_around_median --byzantine 2 |
          --aggregation_rule bulyan --byzantine 2]
+        [--attack alie --attackers 3,7 [--attack_z 1.0] |
+         --attack ipm --attackers 3,7 [--attack_eps 0.1] |
+         --attack sign_flip --attackers 3,7 [--attack_scale 1.0]]
 
 Same flags and flow as the reference: IID split of the training set over the
 workers (:48-50), a tester on the test split (:51), ``factory.get_server``
@@ -91,10 +94,32 @@ def get_config(argv=None):
     # of the parameters); --cc_iters 1 is norm clipping
     ap.add_argument("--cc_tau", type=float, default=10.0)
     ap.add_argument("--cc_iters", type=int, default=3)
+    # Byzantine clients: the workers listed in --attackers (comma-separated ids) have
+    # their update of every round rewritten on the server before anything reads it:
+    # "alie" (a little is enough) sends mean - z * std of the honest updates per
+    # coordinate, z = --attack_z (default: from the worker and attacker counts), "ipm"
+    # (inner product manipulation) -(--attack_eps) times the honest mean update,
+    # "sign_flip" the attacker's own update mirrored and scaled by --attack_scale
+    ap.add_argument("--attack", type=str, default=None, choices=("alie", "ipm", "sign_flip"))
+    ap.add_argument("--attackers", type=_worker_ids, default=())
+    ap.add_argument("--attack_z", type=float, default=None)
+    ap.add_argument("--attack_eps", type=float, default=0.1)
+    ap.add_argument("--attack_scale", type=float, default=1.0)
     config = ap.parse_args(argv)
     if config.distributed_algorithm == "sign_SGD" and config.aggregation_rule != "mean":
         ap.error("--aggregation_rule applies to the FedAvg-based servers; sign_SGD votes")
+    if config.distributed_algorithm == "sign_SGD" and config.attack is not None:
+        ap.error("--attack applies to the servers that hold fp32 client rows; sign_SGD holds "
+                 "sign planes")
     return config
+
+
+def _worker_ids(text):
+    """"3,7" -> (3, 7)."""
+    try:
+        return tuple(int(t) for t in text.split(",") if t.strip())
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"comma-separated worker ids expected, not {text!r}")
 
 
 def server_kwargs(config):
@@ -104,7 +129,9 @@ def server_kwargs(config):
     Shapley servers, the aggregation rule and its trim count when the rule is not the
     default mean, multi-Krum's byzantine / krum_select, byzantine for Bulyan and the
     mean around the median, the geometric median's
-    gm_iters / gm_nu and centered clipping's cc_tau / cc_iters for those rules alone."""
+    gm_iters / gm_nu and centered clipping's cc_tau / cc_iters for those rules alone, and
+    the attack with its attackers and parameters when --attack is given (the server
+    rejects a parameter that belongs to another attack)."""
     if config.distributed_algorithm == "sign_SGD":
         return {}
     kwargs = {"aggregation_mode": config.aggregation_mode}
@@ -124,6 +151,12 @@ def server_kwargs(config):
         if config.aggregation_rule == "centered_clip":
             kwargs["cc_tau"] = getattr(config, "cc_tau", 10.0)
             kwargs["cc_iters"] = getattr(config, "cc_iters", 3)
+    if getattr(config, "attack", None) is not None:
+        kwargs["attack"] = config.attack
+        kwargs["attackers"] = tuple(getattr(config, "attackers", ()))
+        kwargs["attack_z"] = getattr(config, "attack_z", None)
+        kwargs["attack_eps"] = getattr(config, "attack_eps", 0.1)
+        kwargs["attack_scale"] = getattr(config, "attack_scale", 1.0)
     return kwargs
 
 

@@ -172,6 +172,40 @@ int dls_trimmed_mean_f32(const float *U, int64_t ldu, const int32_t *rows, int32
 int dls_mean_around_median_f32(const float *U, int64_t ldu, const int32_t *rows, int32_t K,
                                int32_t keep, int64_t P, float *out, dls_stream_t stream);
 
+/* Byzantine client updates crafted from the honest clients' rows, in place: the
+ * omniscient coordinate-wise attacks the robust rules above are measured against.
+ * Per coordinate out = base + a * (mean - base) + b * sigma over the Kh honest rows,
+ * written into each of the Ka attacker rows of the same store.  "A little is enough"
+ * (Baruch, Baruch & Goldberg 2019) is a = 1, b = -z, no base (mean - z * std); inner
+ * product manipulation (Xie, Koyejo & Gupta 2019) is a = -eps, b = 0 with the
+ * previous global model as base (-eps times the honest mean update).
+ * hrows / arows are device int32 [Kh] / [Ka] tables of row indices of U, 1 <= Kh, Ka <=
+ * DLS_ROBUST_MAX_K; they must not share a row (a precondition: the tables live on
+ * the device and are not checked; rows in neither table are not touched).  a and b
+ * are finite; base is NULL or P device floats (16-byte aligned); P, ldu multiples of
+ * 4, ldu >= P; U 16-byte aligned.  Every check, the null pointers included, runs
+ * before any device call; P == 0 returns 0 without a launch.
+ * Per flat coordinate p, independently, with v[0] .. v[Kh-1] the honest values
+ * U[hrows[k]][p] ascending in the total order of dls_trimmed_mean_f32 (-0.0 below
+ * +0.0, every NaN above +inf):
+ *   1. acc = v[0]; acc = fl32(acc + v[i]) ascending; mu = fl32(acc / fl32(Kh)),
+ *      correctly rounded (Kh == 1: mu = v[0]'s own bits): the bits of
+ *      dls_trimmed_mean_f32 with trim 0 on the same rows;
+ *   2. only when b != 0: s = +0; ascending d = fl32(v[i] - mu), s = fmaf(d, d, s);
+ *      var = fl32(s / fl32(Kh)) (Kh == 1: var = s), the population variance; sigma
+ *      = the correctly rounded fp32 square root of var (denormals included);
+ *   3. t = base ? fl32(mu - base[p]) : mu; r = fl32(a * t); if b != 0, r = fl32(r +
+ *      fl32(b * sigma)); out = base ? fl32(base[p] + r) : r.  Multiply, then add:
+ *      nothing is contracted but the one fmaf of step 2.  A NaN result is 0x7fc00000;
+ *   4. U[arows[j]][p] = out for every j < Ka.
+ * The result depends only on the multiset of each column: the same bits for any
+ * order of hrows.  b == 0 (either sign) skips step 2, so a variance that overflows
+ * cannot turn a pure a * mu into a NaN.  Columns P .. ldu-1 of every row are
+ * untouched. */
+int dls_craft_rows_f32(float *U, int64_t ldu, const int32_t *hrows, int32_t Kh,
+                       const int32_t *arows, int32_t Ka, float a, float b, const float *base,
+                       int64_t P, dls_stream_t stream);
+
 /* Pairwise squared distances between K client rows: the hot path of the
  * distance-based robust rules (Krum / multi-Krum, Blanchard et al. 2017) and of
  * client similarity.  Operands and layout rules of dls_trimmed_mean_f32 (rows
