@@ -70,6 +70,9 @@ SIGNATURES = {
     "dls_craft_rows_f32": ([_p, _i64, _p, _i32, _p, _i32, _f32, _f32, _p, _i64, _p], _i32),
     "dls_pairwise_sqdist_workspace": ([_i32, _i64], _i64),
     "dls_pairwise_sqdist_f32": ([_p, _i64, _p, _i32, _i64, _p, _p, _p], _i32),
+    "dls_rows_gram_workspace": ([_i32, _i64], _i64),
+    "dls_rows_gram_f32": ([_p, _i64, _p, _i32, _i64, _p, _p, _p, _p], _i32),
+    "dls_history_gram_f32": ([_p, _i64, _p, _p, _i64, _p, _i32, _i64, _p, _p, _p, _p], _i32),
     "dls_weiszfeld_workspace": ([_i32, _i64], _i64),
     "dls_rows_sqdist_to_f32": ([_p, _i64, _p, _i32, _i64, _p, _p, _p, _p], _i32),
     "dls_weiszfeld_step_f32": ([_p, _i64, _p, _i32, _p, _i64, _p, _p, _p, _p], _i32),
@@ -161,7 +164,7 @@ def _stream(stream=None, like=None):
 
 
 CSRC_HASHED = ["dls_runtime.hip", "fedavg.hip", "sign.hip", "quant.hip", "quant_fma.hip", "shapley.hip",
-               "infer.hip", "conv.hip", "lenet.hip", "loss.hip", "robust.hip", "pairdist.hip", "weiszfeld.hip", "dls_common.h", "quant_common.h",
+               "infer.hip", "conv.hip", "lenet.hip", "loss.hip", "robust.hip", "pairdist.hip", "weiszfeld.hip", "gram.hip", "dls_common.h", "quant_common.h",
                "loss_common.h", os.path.join("..", "..", "include", "dls_hip.h")]
 
 
@@ -303,6 +306,97 @@ def _rows_operands(fn, U, rows, P):
     if ldu % 4 != 0 or ldu < P:
         raise RuntimeError(f"{fn}: row pitch {ldu} must be a multiple of 4, at least P")
     return K, P, ldu
+
+
+def _gram_operands(fn, U, P, base, out, K):
+    """base: None or an fp32 vector of at least P elements; out: None or a contiguous
+    fp64 [K, K] tensor."""
+    if base is not None and (not torch.is_tensor(base) or base.dtype != torch.float32
+                             or base.dim() != 1 or base.numel() < P
+                             or (base.numel() > 1 and base.stride(0) != 1)):
+        raise RuntimeError(f"{fn}: base must be an fp32 vector of at least P={P} elements "
+                           "with unit stride")
+    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.float64
+                            or tuple(out.shape) != (K, K) or not out.is_contiguous()):
+        raise RuntimeError(f"{fn}: out must be a contiguous fp64 [K, K] = [{K}, {K}] tensor")
+
+
+def _gram_work(K, P, device):
+    nbytes = int(lib().dls_rows_gram_workspace(K, P))
+    if nbytes < 0:
+        _check(nbytes, "dls_rows_gram_workspace")
+    return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+
+
+def rows_gram(U, rows, P, base=None, out=None, stream=None):
+    """Inner products of the K = rows.numel() selected rows of U over their first P
+    elements (dls_rows_gram_f32): an fp64 [K, K] device tensor G[a][b] ~ sum_p h_a h_b,
+    h_k = U[rows[k]] - base (one fp32 rounding) or the row itself without ``base``.
+    Symmetric in bits; |G[a][b] - exact| <= 2^-17 * sum_p |h_a h_b|, so a cosine
+    G[a][b] / sqrt(G[a][a] G[b][b]) is within 2^-17 absolute; rows of equal contents
+    give G[a][b] == G[a][a] == G[b][b] bit for bit; a row that holds inf or NaN makes its
+    own row and column non-finite.  U, rows, P as in pairwise_sqdist; base: None or an
+    fp32 vector of at least P elements; out: a contiguous fp64 [K, K] tensor (default:
+    a new one)."""
+    fn = "rows_gram"
+    K, P, ldu = _rows_operands(fn, U, rows, P)
+    _gram_operands(fn, U, P, base, out, K)
+    _check_same_device(fn, U, rows=rows, base=base, out=out)
+    if U.data_ptr() % 16 != 0 or (base is not None and base.data_ptr() % 16 != 0):
+        raise RuntimeError(f"{fn}: U and base must be 16-byte aligned")
+    if out is None:
+        out = torch.empty((K, K), dtype=torch.float64, device=U.device)
+    _ptr(U), _ptr(rows), _ptr(base), _ptr(out)  # no CPU path
+    work = _gram_work(K, P, U.device)
+    _check(lib().dls_rows_gram_f32(_ptr(U), ldu, _ptr(rows), K, P, _ptr(base), _ptr(out),
+                                   _ptr(work), _stream(stream, U)), "dls_rows_gram_f32")
+    if stream is not None:
+        work.record_stream(stream)
+    return out
+
+
+def history_gram(U, rows, H, hrows, P, base=None, out=None, stream=None):
+    """The fused FoolsGold step (dls_history_gram_f32): H[hrows[k]][:P] += U[rows[k]][:P]
+    - base in place (the subtraction and the addition each rounded once to fp32, so
+    numpy float32 reproduces the new H bit for bit; without ``base`` the row itself is
+    added) and the Gram matrix of the new history rows, as ``rows_gram`` would give it,
+    from the same visit: U, H and base are each read once and H is written once.
+    Columns P.. of H and the rows not listed in ``hrows`` are untouched.  H: fp32
+    [*, ldh] like U, not overlapping U or base; hrows: int32 [K] like rows.  The row
+    tables are copied to the host once and checked: every index inside its matrix and
+    ``hrows`` distinct (two lanes folding into one row would race).  Returns (H, G)."""
+    fn = "history_gram"
+    K, P, ldu = _rows_operands(fn, U, rows, P)
+    try:
+        Kh, _, ldh = _rows_operands(fn, H, hrows, P)
+    except RuntimeError as e:
+        raise RuntimeError(str(e).replace("U must be", "H must be")
+                           .replace("rows must be", "hrows must be")) from None
+    if Kh != K:
+        raise RuntimeError(f"{fn}: hrows holds {Kh} rows, rows holds {K}")
+    _gram_operands(fn, U, P, base, out, K)
+    _check_same_device(fn, U, rows=rows, H=H, hrows=hrows, base=base, out=out)
+    if U.data_ptr() % 16 != 0 or H.data_ptr() % 16 != 0 \
+            or (base is not None and base.data_ptr() % 16 != 0):
+        raise RuntimeError(f"{fn}: U, H and base must be 16-byte aligned")
+    if _overlaps(H, U) or (base is not None and _overlaps(H, base)):
+        raise RuntimeError(f"{fn}: H must not overlap U or base")
+    _ptr(U), _ptr(rows), _ptr(H), _ptr(hrows), _ptr(base)  # no CPU path
+    for name, table, n in (("rows", rows, U.shape[0]), ("hrows", hrows, H.shape[0])):
+        idx = table.cpu().tolist()
+        if min(idx) < 0 or max(idx) >= n:
+            raise RuntimeError(f"{fn}: {name} {idx} outside the matrix's {n} rows")
+        if name == "hrows" and len(set(idx)) != K:
+            raise RuntimeError(f"{fn}: hrows must be distinct, not {idx}")
+    if out is None:
+        out = torch.empty((K, K), dtype=torch.float64, device=U.device)
+    work = _gram_work(K, P, U.device)
+    _check(lib().dls_history_gram_f32(_ptr(U), ldu, _ptr(rows), _ptr(H), ldh, _ptr(hrows), K, P,
+                                      _ptr(base), _ptr(out), _ptr(work), _stream(stream, U)),
+           "dls_history_gram_f32")
+    if stream is not None:
+        work.record_stream(stream)
+    return H, out
 
 
 def mean_around_median(U, rows, keep, P, out, stream=None):

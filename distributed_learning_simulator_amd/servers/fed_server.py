@@ -19,10 +19,11 @@ log = logging.getLogger("distributed_learning_simulator_amd")
 
 _MODES = {"exact": _native.FEDAVG_EXACT, "fma": _native.FEDAVG_FMA}
 _RULES = ("mean", "median", "trimmed_mean", "multi_krum", "geometric_median", "centered_clip",
-          "mean_around_median", "bulyan")
+          "mean_around_median", "bulyan", "foolsgold")
 _BYZANTINE_RULES = ("multi_krum", "bulyan", "mean_around_median")
 _GM_ITERS, _GM_NU = 3, 1e-6  # the defaults of RFA (Pillutla et al.)
 _CC_TAU, _CC_ITERS = 10.0, 3
+_FG_KAPPA = 1.0  # the paper's confidence parameter
 _ATTACK_EPS, _ATTACK_SCALE = 0.1, 1.0
 
 
@@ -72,7 +73,23 @@ class FedServer(Server):
       4*``byzantine`` chosen values closest to their median
       (dls_mean_around_median_f32), so a single poisoned coordinate cannot hide
       inside a small Euclidean distance.  4*``byzantine`` + 3 <= K.
-      ``last_selection`` (in pick order) / ``last_scores`` hold the latest choice.
+      ``last_selection`` (in pick order) / ``last_scores`` hold the latest choice;
+    * ``"foolsgold"``: FoolsGold (Fung, Yoon & Beschastnikh 2020), the defence against
+      sybils: clients whose accumulated updates keep pointing the same way are
+      down-weighted, whatever their number; no count of bad clients is needed.  Every
+      round each client's update, taken from the previous global model (from the
+      coordinate-wise median of the round's rows while there is none, as in round 1 of
+      a server without a tester), is added to that worker's history row and the cosines
+      of the histories come out of the same visit (dls_history_gram_f32), exactly once
+      per round, when all updates have arrived and after the attack;
+      ``aggregation.foolsgold_weights`` turns them into a weight alpha in [0, 1] per
+      client (``fg_kappa`` is the paper's confidence: larger pushes the weights towards
+      0 and 1) and the aggregate is the alpha-weighted mean of the updates (one
+      dls_centered_clip_step_f32).  ``get_subset_model`` weights a subset from the
+      round's cached similarities and folds nothing.  ``last_weights`` /
+      ``last_similarity`` hold each worker's alpha and maximum cosine after pardoning,
+      ``last_rejected`` the workers whose history is not finite; ``reset_history``
+      forgets one worker's history or all.
 
     ``attack`` makes the workers listed in ``attackers`` Byzantine: once a round's
     updates have all arrived, their rows are rewritten in place before anything reads
@@ -104,11 +121,12 @@ class FedServer(Server):
     def __init__(self, aggregation_mode="exact", aggregation_rule="mean", trim=0, byzantine=0,
                  krum_select=None, gm_iters=_GM_ITERS, gm_nu=_GM_NU, cc_tau=_CC_TAU,
                  cc_iters=_CC_ITERS, attack=None, attackers=(), attack_z=None,
-                 attack_eps=_ATTACK_EPS, attack_scale=_ATTACK_SCALE, **kwargs):
+                 attack_eps=_ATTACK_EPS, attack_scale=_ATTACK_SCALE, fg_kappa=_FG_KAPPA, **kwargs):
         if aggregation_mode not in _MODES:
             raise ValueError(f"aggregation_mode must be one of {sorted(_MODES)}, not {aggregation_mode!r}")
         self._check_rule(aggregation_rule, trim, aggregation_mode, kwargs.get("worker_number"),
-                         byzantine, krum_select, gm_iters, gm_nu, cc_tau, cc_iters)
+                         byzantine, krum_select, gm_iters, gm_nu, cc_tau, cc_iters,
+                         fg_kappa=fg_kappa)
         attackers = self._check_attack(attack, attackers, attack_z, attack_eps, attack_scale,
                                        kwargs.get("worker_number"))
         super().__init__(**kwargs)
@@ -128,6 +146,10 @@ class FedServer(Server):
         self.cc_tau = float(cc_tau)
         self.cc_iters = cc_iters
         self.last_clip_scales = {}
+        self.fg_kappa = float(fg_kappa)
+        self.last_weights = {}
+        self.last_similarity = {}
+        self._fg_round = None  # the folded round: its worker ids, their G and the base
         self.attack = attack
         self.attackers = attackers
         self.attack_z = None if attack_z is None else float(attack_z)
@@ -142,7 +164,8 @@ class FedServer(Server):
 
     @classmethod
     def _check_rule(cls, rule, trim, mode, worker_number, byzantine=0, krum_select=None,
-                    gm_iters=_GM_ITERS, gm_nu=_GM_NU, cc_tau=_CC_TAU, cc_iters=_CC_ITERS):
+                    gm_iters=_GM_ITERS, gm_nu=_GM_NU, cc_tau=_CC_TAU, cc_iters=_CC_ITERS,
+                    fg_kappa=_FG_KAPPA):
         if rule not in _RULES:
             raise ValueError(f"aggregation_rule must be one of {list(_RULES)}, not {rule!r}")
         if isinstance(trim, bool) or not isinstance(trim, int) or trim < 0:
@@ -174,6 +197,12 @@ class FedServer(Server):
         if rule != "centered_clip" and (cc_tau != _CC_TAU or cc_iters != _CC_ITERS):
             raise ValueError(f"cc_tau={cc_tau} / cc_iters={cc_iters} needs "
                              f"aggregation_rule='centered_clip', not {rule!r}")
+        if (isinstance(fg_kappa, bool) or not isinstance(fg_kappa, (int, float))
+                or not math.isfinite(fg_kappa) or fg_kappa <= 0):
+            raise ValueError(f"fg_kappa must be a positive finite number, not {fg_kappa!r}")
+        if rule != "foolsgold" and fg_kappa != _FG_KAPPA:
+            raise ValueError(f"fg_kappa={fg_kappa} needs aggregation_rule='foolsgold', not "
+                             f"{rule!r}")
         if rule == "mean":
             return
         if cls._robust_unsupported is not None:
@@ -317,10 +346,12 @@ class FedServer(Server):
             return self.__prev_model
         ids = list(client_subset)
         store = self.parameters.store
-        # multi-Krum, Bulyan, the geometric median and centered clipping report, break ties and
-        # order by worker id (no subclass that overrides _aggregate runs those rules)
+        # multi-Krum, Bulyan, the geometric median, centered clipping and FoolsGold report,
+        # break ties and order by worker id (no subclass that overrides _aggregate runs
+        # those rules)
         extra = {"ids": ids} if self.aggregation_rule in ("multi_krum", "geometric_median",
-                                                          "centered_clip", "bulyan") else {}
+                                                          "centered_clip", "bulyan",
+                                                          "foolsgold") else {}
         flat = self._aggregate(store, [self.parameters.row_of(i) for i in ids],
                                [self.parameters.n_of(i) for i in ids], **extra)
         return store.layout.views(flat)
@@ -342,6 +373,8 @@ class FedServer(Server):
             return self._centered_clip(store, rows, list(range(K)) if ids is None else ids)
         if self.aggregation_rule == "bulyan":
             return self._bulyan(store, rows, list(range(K)) if ids is None else ids)
+        if self.aggregation_rule == "foolsgold":
+            return self._foolsgold(store, rows, list(range(K)) if ids is None else ids)
         if self.aggregation_rule == "mean_around_median":
             if 2 * self.byzantine >= K:
                 raise ValueError(f"byzantine={self.byzantine} leaves no majority of a subset of "
@@ -409,6 +442,57 @@ class FedServer(Server):
                  list(self.last_rejected), info["moved"])
         return flat
 
+    def _fold_round(self):
+        """FoolsGold: add the round's updates to the workers' histories, once (all
+        clients have arrived, the attack has run), and cache what the round's
+        ``get_subset_model`` calls share: the Gram matrix of the histories and the base."""
+        store = self.parameters.store
+        ids = list(self.parameters.keys())
+        if len(ids) > _native.ROBUST_MAX_K:
+            raise ValueError(f"aggregation_rule='foolsgold' takes at most ROBUST_MAX_K="
+                             f"{_native.ROBUST_MAX_K} clients, not {len(ids)}")
+        if any(isinstance(w, bool) or not isinstance(w, int) or w < 0 for w in ids):
+            raise ValueError("aggregation_rule='foolsgold' keeps one history row per worker id: "
+                             f"the ids must be non-negative integers, not {ids!r}")
+        rows = [self.parameters.row_of(w) for w in ids]
+        # updates are taken from the model the clients started from, flattened as
+        # _centered_clip does it; from the round's coordinate-wise median while there is none
+        prev = self.__prev_model
+        if prev and store.accepts(prev):
+            base = store.layout.flatten(prev, device=store.U.device)
+        else:
+            base = store.median(rows)
+            log.info("foolsgold: no previous model in round %s, updates are taken from the "
+                     "coordinate-wise median of the round's %s rows", self.round, len(rows))
+        G = store.fold_history(rows, ids, base).cpu().tolist()
+        self._fg_round = {"ids": ids, "G": G, "base": base}
+
+    def _foolsgold(self, store, rows, ids):
+        fr = self._fg_round
+        if fr is None:
+            raise ValueError("aggregation_rule='foolsgold': no folded round: the histories are "
+                             "folded once per round when all of its updates have arrived, and "
+                             "get_subset_model weights subsets of that round only")
+        pos = {w: i for i, w in enumerate(fr["ids"])}
+        missing = [w for w in ids if w not in pos]
+        if missing:
+            raise ValueError(f"aggregation_rule='foolsgold': workers {missing} are not part of "
+                             "the folded round")
+        sub = [[fr["G"][pos[a]][pos[b]] for b in ids] for a in ids]
+        flat, info = store.foolsgold(rows, ids, sub, fr["base"], self.fg_kappa)
+        self.last_weights = info["weights"]
+        self.last_similarity = info["similarity"]
+        self.last_rejected = tuple(info["rejected"])
+        log.info("foolsgold: %s of %s clients weighted above 0 (kappa %s), weights %s, rejected "
+                 "workers %s", sum(1 for a in info["weights"].values() if a > 0.0), len(rows),
+                 self.fg_kappa, info["weights"], list(self.last_rejected))
+        return flat
+
+    def reset_history(self, worker_id=None):
+        """Forget the FoolsGold history of one worker, or of all (None)."""
+        if self.parameters.store is not None:
+            self.parameters.store.reset_history(worker_id)
+
     def _apply_attack(self):
         """Rewrite the attackers' rows of the round in place (all clients have arrived)."""
         if self.attack is None:
@@ -460,6 +544,8 @@ class FedServer(Server):
         self._before_aggregate()
         self.round += 1
         self._apply_attack()
+        if self.aggregation_rule == "foolsgold":
+            self._fold_round()
         log.info("begin aggregating")
         avg_parameter = self.get_subset_model(self.parameters.keys())
         data = self._process_aggregated_parameter(avg_parameter)
@@ -467,5 +553,6 @@ class FedServer(Server):
         acc = self.get_metric(self.prev_model)
         log.info("end aggregating, test accuracy is %s", acc)
         self.parameters.clear()
+        self._fg_round = None
         # one copy per client that feeds this process (its local clients when sharded)
         return RepeatedResult(data=data, num=self.clients_per_round)

@@ -8,7 +8,8 @@
          --aggregation_rule geometric_median [--gm_iters 3] [--gm_nu 1e-6] |
          --aggregation_rule centered_clip [--cc_tau 10.0] [--cc_iters 3] |
          --aggregation_rule mean_around_median --byzantine 2 |
-         --aggregation_rule bulyan --byzantine 2]
+         --aggregation_rule bulyan --byzantine 2 |
+         --aggregation_rule foolsgold [--fg_kappa 1.0]]
         [--attack alie --attackers 3,7 [--attack_z 1.0] |
          --attack ipm --attackers 3,7 [--attack_eps 0.1] |
          --attack sign_flip --attackers 3,7 [--attack_scale 1.0]]
@@ -81,7 +82,7 @@ def get_config(argv=None):
     ap.add_argument("--aggregation_rule", type=str, default="mean",
                     choices=("mean", "median", "trimmed_mean", "multi_krum",
                              "geometric_median", "centered_clip", "mean_around_median",
-                             "bulyan"))
+                             "bulyan", "foolsgold"))
     ap.add_argument("--trim", type=int, default=0)
     ap.add_argument("--byzantine", type=int, default=0)
     ap.add_argument("--krum_select", type=int, default=None)
@@ -94,6 +95,10 @@ def get_config(argv=None):
     # of the parameters); --cc_iters 1 is norm clipping
     ap.add_argument("--cc_tau", type=float, default=10.0)
     ap.add_argument("--cc_iters", type=int, default=3)
+    # foolsgold: clients whose accumulated updates keep pointing the same way (sybils,
+    # e.g. --attack alie --attackers 3,7) are down-weighted; --fg_kappa is the paper's
+    # confidence parameter (larger pushes the weights towards 0 and 1)
+    ap.add_argument("--fg_kappa", type=float, default=1.0)
     # Byzantine clients: the workers listed in --attackers (comma-separated ids) have
     # their update of every round rewritten on the server before anything reads it:
     # "alie" (a little is enough) sends mean - z * std of the honest updates per
@@ -129,7 +134,8 @@ def server_kwargs(config):
     Shapley servers, the aggregation rule and its trim count when the rule is not the
     default mean, multi-Krum's byzantine / krum_select, byzantine for Bulyan and the
     mean around the median, the geometric median's
-    gm_iters / gm_nu and centered clipping's cc_tau / cc_iters for those rules alone, and
+    gm_iters / gm_nu, centered clipping's cc_tau / cc_iters and FoolsGold's fg_kappa for
+    those rules alone, and
     the attack with its attackers and parameters when --attack is given (the server
     rejects a parameter that belongs to another attack)."""
     if config.distributed_algorithm == "sign_SGD":
@@ -151,6 +157,8 @@ def server_kwargs(config):
         if config.aggregation_rule == "centered_clip":
             kwargs["cc_tau"] = getattr(config, "cc_tau", 10.0)
             kwargs["cc_iters"] = getattr(config, "cc_iters", 3)
+        if config.aggregation_rule == "foolsgold":
+            kwargs["fg_kappa"] = getattr(config, "fg_kappa", 1.0)
     if getattr(config, "attack", None) is not None:
         kwargs["attack"] = config.attack
         kwargs["attackers"] = tuple(getattr(config, "attackers", ()))

@@ -238,6 +238,50 @@ int64_t dls_pairwise_sqdist_workspace(int32_t K, int64_t P);
 int dls_pairwise_sqdist_f32(const float *U, int64_t ldu, const int32_t *rows, int32_t K, int64_t P,
                             double *D, void *workspace, dls_stream_t stream);
 
+/* Gram matrix (inner products) of K client rows, read-only and fused with the
+ * in-place fold of the rows into a per-client history: the hot path of the
+ * direction-based robust rules (FoolsGold, Fung, Yoon & Beschastnikh 2020) and the
+ * base of cosine similarity, trust scores and spectral filtering.  Operands, layout
+ * rules and checks of dls_pairwise_sqdist_f32: rows (and hrows) device int32 [K],
+ * 1 <= K <= DLS_ROBUST_MAX_K; P, ldu and ldh multiples of 4 and >= P; U, H, base and
+ * workspace 16-byte aligned; G is device fp64 [K*K] row-major (8-byte aligned);
+ * workspace is device memory of dls_rows_gram_workspace(K, P) bytes (a function of K
+ * and P alone, the same for both calls), scratch for this call only; base is NULL or
+ * P device floats.  Every check, the null pointers included, runs before any device
+ * call; P == 0 writes an all-zero G and touches nothing else.
+ * Per coordinate p,  h_k = base ? fl32(U[rows[k]][p] - base[p]) : U[rows[k]][p].
+ *   dls_rows_gram_f32:  G[a][b] ~ sum_p h_a * h_b for every pair and the diagonal;
+ *     nothing but G and the workspace is written.
+ *   dls_history_gram_f32, the fused per-round step: H'[hrows[k]][p] = fl32(H[hrows[k]][p]
+ *     + h_k), stored in place, and G is the Gram matrix of the rows of H'.  The
+ *     addition is rounded once and never contracted with the subtraction: given the
+ *     bits of U, base and H, H' is defined bit for bit (numpy float32 reproduces it).
+ *     U, H and base are each read once and H is written once.  Columns P .. ldh-1 of
+ *     H and the rows not listed in hrows are untouched.  hrows must be distinct and H
+ *     must not overlap U or base (preconditions: the tables live on the device and are
+ *     not checked here).
+ * The Gram arithmetic is that of dls_pairwise_sqdist_f32 with the subtraction removed:
+ *   acc = fmaf(h_a, h_b, acc) in fp32 chains of at most 120 terms; the chain results
+ *   are converted to fp64 and added in fp64 in a fixed order that is a function of P
+ *   and K alone.
+ * The terms are signed, so the bound is not relative to the result: for finite inputs
+ * whose terms neither overflow nor underflow
+ *   |G[a][b] - exact| <= (120 + 8) * 2^-24 * sum_p |h_a h_b| <= 2^-17 * |h_a| |h_b|,
+ * an absolute error of at most 2^-17 of the cosine G[a][b] / (|h_a| |h_b|).
+ * Exact properties: G[a][b] has the bits of G[b][a]; permuting rows (together with
+ * hrows) permutes G without changing a bit; rows of equal contents give G[a][b] ==
+ * G[a][a] == G[b][b] bit for bit (the same chain of the same operands); repeated
+ * read-only calls give the same bits on any stream, at any ldu and for any position
+ * of the rows in U.  No atomics: a second launch adds the per-wave partials of
+ * `workspace` in ascending order.  A row that holds an inf or NaN makes its own row
+ * and column of G non-finite and leaves the other entries alone. */
+int64_t dls_rows_gram_workspace(int32_t K, int64_t P);
+int dls_rows_gram_f32(const float *U, int64_t ldu, const int32_t *rows, int32_t K, int64_t P,
+                      const float *base, double *G, void *workspace, dls_stream_t stream);
+int dls_history_gram_f32(const float *U, int64_t ldu, const int32_t *rows, float *H, int64_t ldh,
+                         const int32_t *hrows, int32_t K, int64_t P, const float *base, double *G,
+                         void *workspace, dls_stream_t stream);
+
 /* Fused Weiszfeld step and squared distances of K client rows to one point: the
  * hot path of the geometric median (the smoothed Weiszfeld iteration of RFA,
  * Pillutla, Kakade & Harchaoui) and of "how far is every client from the
