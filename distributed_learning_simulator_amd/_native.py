@@ -621,9 +621,40 @@ def sign_vote(planes, rows, K, P, sign_out, counts=None, vote_planes=None, strea
     return sign_out
 
 
+def _require_logical_f32(fn, **tensors):
+    """The worker kernels walk memory from data_ptr() for numel() elements: every
+    tensor must be fp32 with its memory in logical (row-major) order."""
+    for name, t in tensors.items():
+        if t is None:
+            continue
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise RuntimeError(f"{fn}: {name} must be a contiguous fp32 tensor (memory in logical "
+                               f"order), not {t.dtype} with shape {tuple(t.shape)} and strides "
+                               f"{tuple(t.stride())}")
+
+
+def _require_plane_words(fn, planes, P):
+    """planes: int64 words with unit stride, at least the 2 * ceil(P / 64) the kernel touches."""
+    need = 2 * ((P + 63) // 64)
+    if planes.dtype != torch.int64 or planes.dim() != 1 or not planes.is_contiguous() \
+            or planes.numel() < need:
+        raise RuntimeError(f"{fn}: planes must be a contiguous int64 vector of at least {need} "
+                           f"words for {P} parameters, not {planes.dtype} "
+                           f"{tuple(planes.shape)}")
+
+
 def sign_sgd_direction(grad, buf, momentum, one_minus_dampening, nesterov, first, planes,
                        sign_out=None, stream=None):
+    """workers/sign_sgd_worker.py:32-44 on one tensor (dls_sign_sgd_direction): updates
+    ``buf`` in place and writes the 2 * ceil(P / 64) plane words of the signs to
+    ``planes``.  grad, buf and sign_out hold P elements each in logical order."""
+    fn = "sign_sgd_direction"
     P = grad.numel()
+    _require_logical_f32(fn, grad=grad, buf=buf, sign_out=sign_out)
+    for name, t in (("buf", buf), ("sign_out", sign_out)):
+        if t is not None and t.numel() != P:
+            raise RuntimeError(f"{fn}: {name} holds {t.numel()} elements, grad {P}")
+    _require_plane_words(fn, planes, P)
     _check(lib().dls_sign_sgd_direction(_ptr(grad), _ptr(buf), P, float(momentum),
                                         float(one_minus_dampening), int(bool(nesterov)),
                                         int(bool(first)), _ptr(planes), _ptr(sign_out),
@@ -631,6 +662,13 @@ def sign_sgd_direction(grad, buf, momentum, one_minus_dampening, nesterov, first
 
 
 def sign_sgd_apply(param, vote_planes, neg_lr, weight_decay, stream=None):
+    """workers/sign_sgd_worker.py:48-57 on one tensor, in place (dls_sign_sgd_apply).
+    Bit j of the vote's group g is the parameter's element 64 g + j in memory, so
+    ``param`` must have its memory in logical order: a tensor that has not (a
+    channels_last weight) is rejected, not stepped with a permuted vote."""
+    fn = "sign_sgd_apply"
+    _require_logical_f32(fn, param=param)
+    _require_plane_words(fn, vote_planes, param.numel())
     _check(lib().dls_sign_sgd_apply(_ptr(param), _ptr(vote_planes), param.numel(), float(neg_lr),
                                     float(weight_decay), _stream(stream, param)), "dls_sign_sgd_apply")
 

@@ -47,16 +47,25 @@ class SignSGDServer(Server):
         self._bad = None
 
     def _ensure(self, shapes):
-        if self._layout is None:
-            self._layout = ParameterLayout((str(i), s) for i, s in enumerate(shapes))
-            P = self._layout.P
-            # rows of sign_words(P) words at a 128-byte pitch (sign_row_pitch)
-            self._planes = torch.zeros((self.worker_number, _native.sign_row_pitch(P)),
-                                       dtype=torch.int64, device=self.device)
-            self._X = torch.zeros((1, P), dtype=torch.float32, device=self.device)
-            self._bad = torch.zeros(1, dtype=torch.int32, device=self.device)
-        elif [tuple(s) for s in shapes] != self._layout.shapes:
+        """Layout, plane rows and staging row for this vote's tensor list.  The
+        reference keeps no layout: its workers skip tensors without a gradient
+        (workers/sign_sgd_worker.py:29), so the list may change from one vote to the
+        next and only has to agree within a vote.  The first client of a vote that
+        brings other shapes rebuilds; a later one that disagrees ends the vote."""
+        shapes = [tuple(s) for s in shapes]
+        if self._layout is not None and shapes == self._layout.shapes:
+            return
+        if self.sign_gradients:
+            self.sign_gradients = []
+            self._bad.zero_()
             raise ValueError("sign gradient shapes differ between clients")
+        self._layout = ParameterLayout((str(i), s) for i, s in enumerate(shapes))
+        P = self._layout.P
+        # rows of sign_words(P) words at a 128-byte pitch (sign_row_pitch)
+        self._planes = torch.zeros((self.worker_number, _native.sign_row_pitch(P)),
+                                   dtype=torch.int64, device=self.device)
+        self._X = torch.zeros((1, P), dtype=torch.float32, device=self.device)
+        self._bad = torch.zeros(1, dtype=torch.int32, device=self.device)
 
     def _store_client(self, slot, sign_gradient):
         if isinstance(sign_gradient, PackedSigns):

@@ -8,7 +8,16 @@ tensor (``dls_sign_sgd_direction``) updates the momentum buffer in the
 optimizer state, takes the sign and packs it straight into the tensor's slice
 of one 2-bit plane row that stays on the GPU; the vote comes back packed and
 ``dls_sign_sgd_apply`` applies it in place.  Arithmetic is bit-identical to the
-reference's torch ops (golden vectors, tests/test_gpu_sign.py).
+reference's torch ops (golden vectors, tests/test_gpu_sign.py,
+tests/test_gpu_sign_worker.py).
+
+The planes and the vote index a tensor's elements in logical (row-major) order
+and the kernels walk memory, so everything a kernel sees has its memory in that
+order: the gradient goes in through ``contiguous()``, the momentum buffer is
+allocated contiguous whatever the parameter's memory format (its values equal
+the reference's buffer element for element), and a parameter whose memory is
+not in logical order (a ``channels_last`` conv weight) is stepped on a
+contiguous copy that is written back, so it keeps its format.
 """
 import torch
 from torch.optim.sgd import SGD
@@ -51,8 +60,11 @@ class SignSGDWorker(Worker):
             state = optimizer.state[p]
             first = momentum != 0 and "momentum_buffer" not in state
             if momentum != 0 and first:
-                state["momentum_buffer"] = torch.empty_like(p)
+                state["momentum_buffer"] = torch.empty_like(
+                    p, memory_format=torch.contiguous_format)
             buf = state.get("momentum_buffer") if momentum != 0 else None
+            if buf is not None and not buf.is_contiguous():  # e.g. left by torch's own step
+                buf = state["momentum_buffer"] = buf.contiguous()
             off = layout.offsets[i] // 64 * 2
             _native.sign_sgd_direction(p.grad.contiguous(), buf, momentum,
                                        1 - group["dampening"], group["nesterov"], first,
@@ -64,4 +76,9 @@ class SignSGDWorker(Worker):
         vote = result.vote_planes.to(params[0].device)
         for i, (p, group) in enumerate(zip(params, hyper)):
             off = layout.offsets[i] // 64 * 2
-            _native.sign_sgd_apply(p.data, vote[off:], -group["lr"], group["weight_decay"])
+            if p.data.is_contiguous():
+                _native.sign_sgd_apply(p.data, vote[off:], -group["lr"], group["weight_decay"])
+            else:
+                stepped = p.data.contiguous()
+                _native.sign_sgd_apply(stepped, vote[off:], -group["lr"], group["weight_decay"])
+                p.data.copy_(stepped)

@@ -76,23 +76,161 @@ def test_vote_golden_bit_exact():
                               osign.pack_planes(np.pad(vote, (0, Pp - P))))
 
 
-@pytest.mark.parametrize("K", [1, 2, 15, 16, 255, 256, 1023, 1024, 4100])
+def gpu_vote_reference(planes, rows, P):
+    """(#pos, #neg, any NaN code) per parameter from the plane words themselves: a bit
+    unpack with torch ops on the GPU, no loop over the clients.  planes: int64
+    [*, >= 2 * ceil(P / 64)]; rows: row indices (repeats count twice) or None."""
+    ng = (P + 63) // 64
+    sel = planes if rows is None else planes[rows.long()]
+    pos, neg = sel[:, 0:2 * ng:2], sel[:, 1:2 * ng:2]  # [K, ng]
+    both = pos & neg
+    cp = torch.empty((ng, 64), dtype=torch.int32, device=planes.device)
+    cn = torch.empty_like(cp)
+    nan = torch.empty((ng, 64), dtype=torch.bool, device=planes.device)
+    for j in range(64):
+        cp[:, j] = ((pos >> j) & 1).sum(0, dtype=torch.int32)
+        cn[:, j] = ((neg >> j) & 1).sum(0, dtype=torch.int32)
+        nan[:, j] = ((both >> j) & 1).any(0)
+    return cp.reshape(-1)[:P], cn.reshape(-1)[:P], nan.reshape(-1)[:P]
+
+
+def gpu_pack_reference(sign, W):
+    """int64 [W] wire planes of a ternary fp32 vote [P] (torch ops, zero padded)."""
+    P = sign.numel()
+    s = torch.zeros(W * 32, device=sign.device)
+    s[:P] = sign
+    sh = torch.arange(64, device=sign.device)
+    out = torch.empty(W, dtype=torch.int64, device=sign.device)
+    out[0::2] = ((s > 0).reshape(-1, 64).long() << sh).sum(1)  # wraps into bit 63
+    out[1::2] = ((s < 0).reshape(-1, 64).long() << sh).sum(1)
+    return out
+
+
+def check_vote_against_planes(planes, rows, K, P):
+    """dls_sign_vote_count and the fused dls_sign_vote (signs + counts + packed vote)
+    against gpu_vote_reference, on every parameter."""
+    from distributed_learning_simulator_amd import _native
+    cp, cn, nan = gpu_vote_reference(planes, rows, P)
+    ref_counts = cp - cn + nan.int() * _native.SIGN_NAN_MARK
+    ref_sign = torch.where(nan, torch.zeros((), device=dev), torch.sign((cp - cn).float()))
+    W = _native.sign_words(P)
+    counts = torch.full((P,), -7, dtype=torch.int32, device=dev)
+    _native.sign_vote_count(planes, rows, K, P, counts)
+    assert torch.equal(counts, ref_counts)
+    c2 = torch.full((P,), -7, dtype=torch.int32, device=dev)
+    sign = torch.full((P,), 7.0, device=dev)
+    vote = torch.full((W,), 0x55, dtype=torch.int64, device=dev)
+    _native.sign_vote(planes, rows, K, P, sign, counts=c2, vote_planes=vote)
+    assert torch.equal(c2, ref_counts)
+    assert torch.equal(sign.view(torch.int32), ref_sign.view(torch.int32))
+    assert torch.equal(vote, gpu_pack_reference(ref_sign, W))
+    s3 = torch.full((P,), 7.0, device=dev)  # the server's instance: no counts
+    v3 = torch.full((W,), 0x55, dtype=torch.int64, device=dev)
+    _native.sign_vote(planes, rows, K, P, s3, vote_planes=v3)
+    assert torch.equal(s3.view(torch.int32), ref_sign.view(torch.int32))
+    assert torch.equal(v3, vote)
+    return cp, cn
+
+
+def one_sided_planes(K, W, seed, nan_row):
+    """Random planes without NaN codes; group 0 all-positive and group 1 all-negative in
+    every row, so that the counts reach +K and -K (the only inputs that drive the
+    eights counter to its top value); NaN codes in group 2 of one row."""
+    g = torch.Generator(device=dev).manual_seed(seed)
+    planes = torch.randint(-2**62, 2**62, (K, W), generator=g, device=dev)
+    planes[:, 1::2] &= ~planes[:, 0::2]  # no NaN codes
+    planes[:, 0], planes[:, 1] = -1, 0
+    planes[:, 2], planes[:, 3] = 0, -1
+    planes[nan_row, 5] |= planes[nan_row, 4]
+    return planes
+
+
+# vote_dispatch picks the counter width CB from (K + 7) / 8 < 2^CB: the widths change
+# between K = 24|25, 120|121, 504|505, 2040|2041 and 32760|32761 (CB = 16 from there)
+@pytest.mark.parametrize("K", [1, 2, 15, 16, 255, 256, 1023, 1024, 4100,
+                               24, 25, 120, 121, 504, 505, 2040, 2041, 32760, 32761])
 def test_vote_counter_widths(K):
-    """Every bit-sliced counter width, including K at each 2^B boundary."""
+    """Every bit-sliced counter width on both sides of each width boundary, with all
+    K clients on one side of a parameter."""
     from distributed_learning_simulator_amd import _native
     P = 1024
-    g = torch.Generator(device=dev).manual_seed(K)
-    planes = torch.randint(-2**62, 2**62, (K, _native.sign_words(P)), generator=g, device=dev)
-    planes[:, 1::2] &= ~planes[:, 0::2]  # no NaN codes
-    planes[: K // 2 + 1, 0::2] |= -1  # a majority positive on every parameter...
-    planes[: K // 2 + 1, 1::2] = 0
-    counts = torch.empty(P, dtype=torch.int32, device=dev)
-    _native.sign_vote_count(planes, None, K, P, counts)
-    w = planes.cpu().numpy().view(np.uint64)
-    ref = np.zeros(P, np.int64)
+    planes = one_sided_planes(K, _native.sign_words(P), K, K // 2)
+    planes[: K // 2 + 1, 6::2] |= -1  # a majority positive on every other parameter...
+    planes[: K // 2 + 1, 7::2] = 0
+    cp, cn = check_vote_against_planes(planes, None, K, P)
+    assert int((cp - cn)[:64].min()) == K and int((cp - cn)[64:128].max()) == -K
+    if K <= 4100:  # the oracle's unpack, client by client
+        w = planes.cpu().numpy().view(np.uint64)
+        ref = np.zeros(P, np.int64)
+        for k in range(K):
+            ref += np.nan_to_num(osign.unpack_planes(w[k], P)).astype(np.int64)
+        assert np.array_equal((cp - cn).cpu().numpy(), ref)
+
+
+@pytest.mark.parametrize("K,CB,subset", [(40, 4, True), (130, 6, False), (2048, 12, False)])
+def test_vote_wide_layout_counter_widths(K, CB, subset):
+    """The wide per-wave layout (G > 1 groups per lane) with the counter widths it had
+    never run with: signs, counts and packed vote on every parameter."""
+    from distributed_learning_simulator_amd import _native
+    P = 4_000_000
+    W = _native.sign_words(P)
+    # the host's condition for G > 1 (launch_vote), restated so that the case cannot
+    # fall back to one group per lane on a part with more CUs
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    vote_groups = W // 2
+    assert -(-vote_groups // (4 * cus)) + 7 > 64, cus
+    c_max = (K + 7) // 8
+    assert c_max < (1 << CB) and c_max >= (1 << {4: 2, 6: 4, 12: 8}[CB])
+    rows = None
+    nrows = K
+    if subset:  # K of K + 10 rows, out of order, one of them twice
+        nrows = K + 10
+        idx = torch.randperm(nrows, generator=torch.Generator().manual_seed(K))[:K]
+        idx[7] = idx[3]
+        rows = idx.to(torch.int32).to(dev)
+    planes = one_sided_planes(nrows, W, K, nrows // 2 if rows is None else int(rows[0]))
+    planes[:, 2 * ((P + 63) // 64):] = 0  # past P: zero, as the packer leaves it
+    cp, cn = check_vote_against_planes(planes, rows, K, P)
+    assert int((cp - cn)[:64].min()) == K and int((cp - cn)[64:128].max()) == -K
+
+
+@pytest.mark.parametrize("P", [1000, 4096, 4097, 4352 - 3])
+def test_pack_server_geometry(P):
+    """dls_sign_pack_f32 as SignSGDServer calls it: padded X rows, plane rows at the
+    128-byte pitch, one-row launches into planes[slot:slot + 1], and a nonternary
+    counter that the kernel only ever adds to.  16 tiles of 256 make a block: 4096 is
+    the last size of one block, 4097 and 4349 have 17 tiles."""
+    from distributed_learning_simulator_amd import _native
+    K = 5
+    ldx = (P + 3) // 4 * 4 + 12  # P + 12 where the library accepts it (ldx % 4 == 0)
+    W, pitch = _native.sign_words(P), _native.sign_row_pitch(P)
+    g = np.random.default_rng(P)
+    S = g.integers(-1, 2, (K, P)).astype(np.float32)
+    S[:, ::13] = -0.0
+    S[1, P // 2] = S[4, P - 1] = np.nan
+    S[2, 0], S[2, P - 1], S[3, P // 3] = 0.5, np.inf, -2.0  # 3 nonternary values
+    X = torch.full((K, ldx), 7.0, device=dev)  # the pitch padding is nonternary: never read
+    X[:, :P] = torch.from_numpy(S)
+    fill = 0xABABABABABABABAB - (1 << 64)
+    want = np.stack([osign.pack_planes(S[k]) for k in range(K)])
+    bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    planes = torch.full((K, pitch), fill, dtype=torch.int64, device=dev)
+    _native.sign_pack(X, P, planes, bad)
+    got = planes.cpu().numpy().view(np.uint64)
+    assert np.array_equal(got[:, :W], want)
+    assert np.all(got[:, W:] == np.uint64(0xABABABABABABABAB))  # pitch words untouched
+    assert int(bad.item()) == 3
+    # the server's form: one row per launch; the counter accumulates over launches
+    planes2 = torch.full((K, pitch), fill, dtype=torch.int64, device=dev)
     for k in range(K):
-        ref += osign.unpack_planes(w[k], P).astype(np.int64)
-    assert np.array_equal(counts.cpu().numpy(), ref)
+        _native.sign_pack(X[k:k + 1], P, planes2[k:k + 1], bad)
+    assert torch.equal(planes2, planes)
+    assert int(bad.item()) == 6
+    if P % 4:  # a row pitch of P + 12 that is no multiple of 4 is rejected before any launch
+        Xo = torch.zeros((K, P + 12), device=dev)
+        with pytest.raises(RuntimeError):
+            _native.sign_pack(Xo, P, planes2, bad)
+        assert int(bad.item()) == 6
 
 
 def test_vote_rows_subset_order_free():

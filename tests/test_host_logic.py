@@ -243,6 +243,35 @@ def test_sign_server_vote_and_nonternary(doubles):
         bad.worker_data_queue.add_task([torch.tensor([0.5, 1.0, -1.0])])
 
 
+def test_sign_server_tensor_list_may_change_between_votes(doubles):
+    """The reference keeps no layout (its workers skip tensors without a gradient), so
+    the tensor list may differ from one vote to the next; within a vote it may not."""
+    from distributed_learning_simulator_amd.servers.sign_sgd_server import SignSGDServer
+    from oracle import sign as osign
+    rng = np.random.default_rng(2)
+    server = SignSGDServer(tester=None, worker_number=2, synchronous=True, device=CPU)
+    q = server.worker_data_queue
+
+    def vote(shapes):
+        S = [[rng.integers(-1, 2, s).astype(np.float32) for s in shapes] for _ in range(2)]
+        for k in range(2):
+            q.add_task([torch.from_numpy(t) for t in S[k]])
+        res = q.get_result(consumer=0)
+        assert [tuple(t.shape) for t in res] == list(shapes)
+        for i, t in enumerate(res):
+            want = osign.majority_vote(np.stack([S[k][i].reshape(-1) for k in range(2)]))
+            assert same_bits(t.reshape(-1).numpy(), want)
+
+    full = [(4, 3), (7,), (70,)]
+    vote(full)
+    vote([full[0], full[2]])
+    vote(full)
+    q.add_task([torch.zeros(s) for s in full])
+    with pytest.raises(ValueError, match="differ"):
+        q.add_task([torch.zeros(s) for s in full[:2]])
+    vote(full)  # the broken vote was dropped
+
+
 def test_fastdiv_random_divisors():
     rng = np.random.default_rng(1)
     for b in rng.integers(1, 2**31, size=3):
