@@ -764,7 +764,16 @@ class ClientUpdateStore:
         return flat, info
 
     def subset_models(self, subsets, n_of_row, method="exact", out=None):
-        """S subset models at once.  subsets: list of row lists (non-empty, in order)."""
+        """S subset models at once.  subsets: list of row lists (non-empty, in order).
+
+        ``method="exact"``: the reference's operation order, bit for bit; only a
+        coalition's own rows are read.  ``method="gemm"``: one dls_subset_gemm_f32
+        call over the sorted union of the subsets' rows (rows in no subset are not
+        read) with c_sr = fl32(n_r / N_s) computed in fp64, whatever the order inside
+        a subset; each element within (K+1) 2^-24 of the magnitude sum of its terms.
+        It is a dense product: an inf or NaN in one client's row makes that parameter
+        non-finite in every subset of the call, the ones without that client included
+        (0 * inf is NaN)."""
         S = len(subsets)
         P = self.layout.P
         if out is None:

@@ -10,6 +10,14 @@ model is scored with ``get_metric`` (servers/fed_server.py:26-32).  Under
 over the ranks and the utilities are summed with one all-reduce (each rank
 fills only its own entries), so every rank ends with the full table.
 
+``subset_method="gemm"`` is a dense product over the union of a batch's clients:
+every element of a subset model is within (K+1) 2^-24 of the magnitude sum of its
+terms (K clients in the batch; ``include/dls_hip.h``), but a client row that holds an
+inf or NaN (a diverged or attacking client) makes those parameters non-finite in
+EVERY coalition of the batch, the ones without that client included, because 0 * inf
+is NaN.  The exact kernels read only a coalition's members: with clients that may
+diverge, keep the default.
+
 ``utility_metric="loss"`` makes the utility the tester's mean cross-entropy
 (``get_metric(model, "loss")``, unnegated: the sign convention is the caller's)
 instead of the top-1 accuracy, on the same fast paths: every image's loss is

@@ -355,8 +355,29 @@ int dls_centered_clip_step_f32(const float *U, int64_t ldu, const int32_t *rows,
 
 /* Subset aggregation as a dense fp32 MFMA contraction: out[S, P] = C[S, K] · U[rows, P]
  * (C row-major [S, K], c_si = n_i / N_S; rows[K] selects the K client rows of U).
- * fp32 in / fp32 accumulate (v_mfma_f32_32x32x2_f32): an fma chain in client
- * order, normwise ~1e-7 from the exact weighted mean. */
+ * fp32 in / fp32 accumulate (v_mfma_f32_32x32x2_f32): per element one fma chain in
+ * the order of `rows`, started from +0.0; S is cut into chunks of 64 and K into chunks
+ * of 256 clients, a later client chunk continuing the chain from the fp32 value the
+ * chunk before it stored.
+ * Accuracy, elementwise: |out[s][p] - sum_k c_sk U[rows[k]][p]| <= g * sum_k |c_sk|
+ * |U[rows[k]][p]| with g = (K+1)u / (1 - (K+1)u), u = 2^-24 (every term: at most one
+ * product rounding and K additions), while products and sums stay in the normal
+ * range; subnormals are kept, not flushed.  Where every product and every partial sum
+ * is exactly representable (small integers times dyadic coefficients) the result is
+ * exact, bit for bit, for any S, K, P and pitch.
+ * Layout: P, ldu and ldo are multiples of 4, U and out 16-byte aligned
+ * (DLS_ELAYOUT otherwise); S, K, P > 0 (DLS_EINVAL otherwise); a failed check writes
+ * nothing.  Exactly out[s][0 .. P) for s < S is written: out[s][P .. ldo) and rows of
+ * out past S are left alone.  Only U[rows[k]][0 .. P) is read: rows of U that `rows`
+ * does not name and U[..][P .. ldu) may hold anything.  A row may be listed more than
+ * once in `rows`: each listing is a term of its own.
+ * Non-finite rows: unlike the exact kernels, which read only a coalition's members,
+ * the contraction multiplies EVERY selected row by its coefficient, so an inf or NaN
+ * in U[rows[k]][p] makes out[s][p] non-finite in every coalition s of the call, the
+ * ones with c_sk = 0 included (0 * inf is NaN; NaN where the row holds NaN or c_sk is
+ * 0, +-inf where c_sk != 0 meets an inf).  Other columns are not affected.  A caller
+ * that needs the coalitions without a diverged client to stay finite uses the exact
+ * kernels, or a call whose `rows` leaves that row out. */
 int dls_subset_gemm_f32(const float *C, int32_t S, int32_t K, const float *U, int64_t ldu,
                         const int32_t *rows, int64_t P, float *out, int64_t ldo,
                         dls_stream_t stream);

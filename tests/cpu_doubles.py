@@ -57,7 +57,9 @@ def subset_fedavg_union(U, urows, uweight, member, sub_total, P, out, stream=Non
 def subset_gemm(C, U, rows, P, out, stream=None):
     Cn = _f32(C).astype(np.float64)
     Un = _f32(U)[_f32(rows).astype(np.int64), :P].astype(np.float64)
-    out[:, :P].copy_(torch.from_numpy((Cn @ Un).astype(np.float32)))
+    with np.errstate(all="ignore"):  # a non-finite client row: inf / NaN as IEEE gives them
+        res = (Cn @ Un).astype(np.float32)
+    out[:Cn.shape[0], :P].copy_(torch.from_numpy(res))  # S rows, P columns, as the kernel
     return out
 
 
