@@ -657,7 +657,26 @@ int dls_pool_linear_split(const uint16_t *x, int64_t B, int32_t HW, int32_t C, c
  * order is fixed by the layer shapes alone (not by B, S, ldm, the image's or
  * the model's position, the grid or the stream) and the count is an integer
  * atomic: the same bits in any process.  B == 0 returns 0 without a launch.
- * models, x and logits 16-byte aligned; ldm a multiple of 4. */
+ * models, x and logits 16-byte aligned; ldm a multiple of 4.
+ * Pinned by tests/test_gpu_lenet_exact.py against tests/lenet_ref.py (fp64):
+ *  - accuracy: with u = 2^-24 and g(n) = n u / (1 - n u), a layer of reduction
+ *    length K (25, 150, 400, 120, 84) adds at most g(K + 2) (sum |w| (|h| + e_in)
+ *    + |b|) to the incoming error sum |w| e_in, h its fp64 input; ReLU and the
+ *    pooling pass the error on (a window: the largest of its members'); every
+ *    logit is within the bound this gives from e = 0 at the pixels.  Where every
+ *    product and partial sum is representable (integer models below 2^24) the
+ *    logits are the exact values bit for bit.
+ *  - special values are IEEE's: 0 * inf = NaN.  ReLU keeps a NaN and gives +0 for
+ *    -inf and -0; a pooling window with a NaN is NaN; in the count the first NaN
+ *    logit is the argmax, before +inf, else the lowest index among equal maxima
+ *    (a row of -inf: index 0).
+ *  - isolation: a NaN or inf pixel reaches that image's logits only, a NaN or inf
+ *    parameter that model's logits and count only; the zero images that fill a
+ *    ragged last tile, the zero weight rows past O and the padded k steps of conv2
+ *    produce nothing that is stored, whatever they are multiplied with; elements
+ *    of a row that no offset names and the row pitch's padding are never read.
+ *  - subnormals are kept (inputs, products, sums and results), in the VALU chains
+ *    of conv1 and in the MFMA layers alike, as observed on gfx950. */
 int dls_lenet5_eval_f32(const float *models, int64_t ldm, int32_t S, const int64_t *offsets,
                         const float *x, int64_t B, const int64_t *labels, int32_t O,
                         float *logits, int64_t *correct, dls_stream_t stream);
@@ -678,7 +697,9 @@ int dls_softmax_ce_f32(const float *logits, int32_t S, int64_t B, int32_t O, con
  * logits[s,b,:] and labels[b], ldn >= B, stored by the launch that computes the
  * logits (the same bits as dls_softmax_ce_f32 of them).  At least one of logits,
  * correct, loss is non-null; labels is needed for correct and for loss.  logits
- * and correct are the bits dls_lenet5_eval_f32 gives. */
+ * and correct are the bits dls_lenet5_eval_f32 gives, under the same pinned
+ * contract (bound, special values, isolation, subnormals): the tests launch every
+ * case through both entry points. */
 int dls_lenet5_eval_loss_f32(const float *models, int64_t ldm, int32_t S, const int64_t *offsets,
                              const float *x, int64_t B, const int64_t *labels, int32_t O,
                              float *logits, int64_t *correct, float *loss, int64_t ldn,
