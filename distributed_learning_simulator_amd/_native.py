@@ -721,10 +721,53 @@ def quantize_u8(x, seg_off, total, scale, zp, q, deq=None, stochastic=False, see
 
 
 # ----------------------------------------------------------- utility evaluation
+# The kernels index their operands from the shapes alone, so the wrappers refuse
+# whatever would send them out of bounds before any pointer reaches the library.
+
+def _check_f32_vector(fn, name, t, n, device):
+    if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.numel() != n
+            or not t.is_contiguous() or t.device != device):
+        raise RuntimeError(f"{fn}: {name} must be a contiguous fp32 tensor of {n} elements on {device}")
+
+
+def _check_bn_module(fn, bn, device):
+    """The module's tensors: fp32 [C], contiguous, on the outputs' device (weight and
+    bias may be None: affine=False)."""
+    C = int(bn.num_features)
+    if C <= 0:
+        raise RuntimeError(f"{fn}: num_features = {C}")
+    for name in ("running_mean", "running_var", "weight", "bias"):
+        t = getattr(bn, name)
+        if t is None and name in ("weight", "bias"):
+            continue
+        _check_f32_vector(fn, f"bn.{name}", t, C, device)
+    return C
+
+
+def _check_bn_activations(fn, x, residual, out, memory_format, layout):
+    """x: fp32 [N, C, H, W] in the given layout; residual and out: x's shape, dtype,
+    layout and device."""
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise RuntimeError(f"{fn}: x must be an fp32 [N, C, H, W] tensor, got {x.dtype} "
+                           f"{tuple(x.shape)}")
+    for name, t in (("x", x), ("residual", residual), ("out", out)):
+        if t is None:
+            continue
+        if t.shape != x.shape or t.dtype != x.dtype or t.device != x.device:
+            raise RuntimeError(f"{fn}: {name} must have x's shape, dtype and device "
+                               f"({tuple(x.shape)}, {x.dtype}, {x.device}), got {tuple(t.shape)}, "
+                               f"{t.dtype}, {t.device}")
+        if not t.is_contiguous(memory_format=memory_format):
+            raise RuntimeError(f"{fn}: activations must be {layout} contiguous ({name} is not)")
+
+
 def bn_fold(bn, alpha, beta, stream=None):
     """Eval-mode constants of a BatchNorm module (dls_bn_fold_f32) into alpha, beta [C]."""
+    C = _check_bn_module("bn_fold", bn, alpha.device)
+    _check_f32_vector("bn_fold", "alpha", alpha, C, alpha.device)
+    _check_f32_vector("bn_fold", "beta", beta, C, alpha.device)
     _check(lib().dls_bn_fold_f32(_ptr(bn.weight), _ptr(bn.bias), _ptr(bn.running_mean),
-                                 _ptr(bn.running_var), float(bn.eps), bn.num_features,
+                                 _ptr(bn.running_var), float(bn.eps), C,
                                  _ptr(alpha), _ptr(beta), _stream(stream, alpha)),
            "dls_bn_fold_f32")
 
@@ -732,12 +775,12 @@ def bn_fold(bn, alpha, beta, stream=None):
 def bn_act_nhwc(x, alpha, beta, residual=None, relu=True, out=None, inplace=False, stream=None):
     """y = act(x * alpha + beta [+ residual]) over a channels_last [N, C, H, W] fp32
     activation in one pass (dls_bn_act_nhwc_f32); returns y (channels_last;
-    x itself when inplace)."""
-    N, C, H, W = x.shape
+    x itself when inplace).  out may be x or residual."""
     cl = torch.channels_last
-    if not x.is_contiguous(memory_format=cl) or (
-            residual is not None and not residual.is_contiguous(memory_format=cl)):
-        raise RuntimeError("bn_act_nhwc: activations must be channels_last contiguous")
+    _check_bn_activations("bn_act_nhwc", x, residual, out, cl, "channels_last")
+    N, C, H, W = x.shape
+    _check_f32_vector("bn_act_nhwc", "alpha", alpha, C, x.device)
+    _check_f32_vector("bn_act_nhwc", "beta", beta, C, x.device)
     if out is None:
         out = x if inplace else torch.empty_like(x, memory_format=cl)
     _check(lib().dls_bn_act_nhwc_f32(_ptr(x), N * H * W, C, _ptr(alpha), _ptr(beta),
@@ -749,8 +792,10 @@ def bn_act_nhwc(x, alpha, beta, residual=None, relu=True, out=None, inplace=Fals
 def bn_fold_exact(bn, consts, stream=None):
     """The GPU library's eval batch-norm constants of a BatchNorm module into
     consts [4*C] = [mean | iv | w | b] (dls_bn_fold_exact_f32)."""
+    C = _check_bn_module("bn_fold_exact", bn, consts.device)
+    _check_f32_vector("bn_fold_exact", "consts", consts, 4 * C, consts.device)
     _check(lib().dls_bn_fold_exact_f32(_ptr(bn.weight), _ptr(bn.bias), _ptr(bn.running_mean),
-                                       _ptr(bn.running_var), float(bn.eps), bn.num_features,
+                                       _ptr(bn.running_var), float(bn.eps), C,
                                        _ptr(consts), _stream(stream, consts)),
            "dls_bn_fold_exact_f32")
 
@@ -758,11 +803,10 @@ def bn_fold_exact(bn, consts, stream=None):
 def bn_act_exact_nhwc(x, consts, residual=None, relu=True, out=None, inplace=False, stream=None):
     """y = act(fma(w, (x - mean) * iv, b) [+ residual]) over a channels_last
     [N, C, H, W] fp32 activation in one pass (dls_bn_act_exact_nhwc_f32)."""
-    N, C, H, W = x.shape
     cl = torch.channels_last
-    if not x.is_contiguous(memory_format=cl) or (
-            residual is not None and not residual.is_contiguous(memory_format=cl)):
-        raise RuntimeError("bn_act_exact_nhwc: activations must be channels_last contiguous")
+    _check_bn_activations("bn_act_exact_nhwc", x, residual, out, cl, "channels_last")
+    N, C, H, W = x.shape
+    _check_f32_vector("bn_act_exact_nhwc", "consts", consts, 4 * C, x.device)
     if out is None:
         out = x if inplace else torch.empty_like(x, memory_format=cl)
     _check(lib().dls_bn_act_exact_nhwc_f32(_ptr(x), N * H * W, C, _ptr(consts), _ptr(residual),
@@ -773,11 +817,11 @@ def bn_act_exact_nhwc(x, consts, residual=None, relu=True, out=None, inplace=Fal
 
 def bn_act_exact_nchw(x, consts, residual=None, relu=True, out=None, inplace=False, stream=None):
     """bn_act_exact_nhwc over an NCHW-contiguous [N, C, H, W] fp32 activation
-    (dls_bn_act_exact_nchw_f32: float4 planes when H*W is a multiple of 4, one
-    element per lane otherwise)."""
+    (dls_bn_act_exact_nchw_f32: float4 planes when H*W is a multiple of 4 and every
+    activation pointer is 16-byte aligned, one element per lane otherwise)."""
+    _check_bn_activations("bn_act_exact_nchw", x, residual, out, torch.contiguous_format, "NCHW")
     N, C, H, W = x.shape
-    if not x.is_contiguous() or (residual is not None and not residual.is_contiguous()):
-        raise RuntimeError("bn_act_exact_nchw: activations must be NCHW contiguous")
+    _check_f32_vector("bn_act_exact_nchw", "consts", consts, 4 * C, x.device)
     if out is None:
         out = x if inplace else torch.empty_like(x, memory_format=torch.contiguous_format)
     _check(lib().dls_bn_act_exact_nchw_f32(_ptr(x), N, C, H * W, _ptr(consts), _ptr(residual),

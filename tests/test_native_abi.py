@@ -194,6 +194,144 @@ def test_conv_wrappers_validate_operands_without_gpu():
         _native.pool_linear(x, torch.zeros(10, C), torch.zeros(20)[::2])
 
 
+def test_bn_wrappers_validate_operands_without_gpu():
+    """bn_fold / bn_fold_exact / bn_act_nhwc / bn_act_exact_nhwc / bn_act_exact_nchw
+    reject operands the kernels would read or write out of bounds: the checks run
+    before any pointer reaches the library, so CPU tensors exercise them here (an
+    operand set that passed them would stop at _ptr's "not on the GPU")."""
+    import torch
+    from distributed_learning_simulator_amd import _native
+    N, C, H, W = 2, 8, 3, 4
+    cl = torch.channels_last
+    x = torch.zeros(N, C, H, W)
+    xl = x.contiguous(memory_format=cl)
+    consts, alpha, beta = torch.zeros(4 * C), torch.zeros(C), torch.zeros(C)
+    acts = [(lambda x_, **kw: _native.bn_act_nhwc(x_, kw.pop("alpha", alpha), kw.pop("beta", beta), **kw), xl, cl),
+            (lambda x_, **kw: _native.bn_act_exact_nhwc(x_, kw.pop("consts", consts), **kw), xl, cl),
+            (lambda x_, **kw: _native.bn_act_exact_nchw(x_, kw.pop("consts", consts), **kw), x,
+             torch.contiguous_format)]
+    for call, good, mf in acts:
+        with pytest.raises(RuntimeError, match="not on the GPU"):  # every check passes
+            call(good, residual=good.clone(memory_format=mf), out=torch.empty_like(good, memory_format=mf))
+        with pytest.raises(RuntimeError, match="fp32"):
+            call(good.double())
+        with pytest.raises(RuntimeError, match="fp32"):
+            call(good.to(torch.float16))
+        with pytest.raises(RuntimeError, match=r"\[N, C, H, W\]"):
+            call(good[0])
+        for name in ("residual", "out"):
+            for bad in (torch.zeros(N, C, H, W + 1), torch.zeros(N, C, H, W, dtype=torch.float64),
+                        torch.zeros(N, C, H, W, dtype=torch.float16), torch.zeros(N, C, H, W, device="meta")):
+                with pytest.raises(RuntimeError, match=name + " must have"):
+                    call(good, **{name: bad.contiguous(memory_format=mf)})
+            other = x if mf is cl else xl  # the other layout
+            with pytest.raises(RuntimeError, match=name + " is not"):
+                call(good, **{name: other.clone(memory_format=torch.preserve_format)})
+            with pytest.raises(RuntimeError, match=name + " is not"):  # a strided view
+                call(good, **{name: torch.zeros(N, C, H, 2 * W)[..., ::2]})
+        with pytest.raises(RuntimeError, match="x is not"):
+            call(x if mf is cl else xl)
+    for key, n in (("consts", 4 * C),):
+        for call, good, mf in acts[1:]:
+            for bad in (torch.zeros(n - 4), torch.zeros(n + 4), torch.zeros(C), torch.zeros(n, dtype=torch.float64),
+                        torch.zeros(n, dtype=torch.float16), torch.zeros(2 * n)[::2],
+                        torch.zeros(n, device="meta")):
+                with pytest.raises(RuntimeError, match=key):
+                    call(good, **{key: bad})
+    for key in ("alpha", "beta"):
+        for bad in (torch.zeros(C - 4), torch.zeros(C + 4), torch.zeros(C, dtype=torch.float64),
+                    torch.zeros(2 * C)[::2], torch.zeros(C, device="meta")):
+            with pytest.raises(RuntimeError, match=key):
+                acts[0][0](xl, **{key: bad})
+
+    # the fold wrappers: module tensors and outputs fp32, contiguous, C long, one device
+    class Plain:  # any object with the module's attributes
+        def __init__(self, **kw):
+            self.weight = self.bias = None
+            self.running_mean, self.running_var, self.eps, self.num_features = \
+                torch.zeros(C), torch.ones(C), 1e-5, C
+            self.__dict__.update(kw)
+
+    folds = [(lambda bn, **kw: _native.bn_fold(bn, kw.get("alpha", alpha), kw.get("beta", beta))),
+             (lambda bn, **kw: _native.bn_fold_exact(bn, kw.get("consts", consts)))]
+    for fold in folds:
+        with pytest.raises(RuntimeError, match="not on the GPU"):
+            fold(torch.nn.BatchNorm2d(C).eval())
+        with pytest.raises(RuntimeError, match="not on the GPU"):
+            fold(Plain())  # affine=False: null weight and bias
+        for attr in ("running_mean", "running_var", "weight", "bias"):
+            for bad in (torch.zeros(C - 1), torch.zeros(C, dtype=torch.float64), torch.zeros(2 * C)[::2],
+                        torch.zeros(C, device="meta")):
+                with pytest.raises(RuntimeError, match=attr):
+                    fold(Plain(**{attr: bad}))
+        with pytest.raises(RuntimeError, match="num_features"):
+            fold(Plain(num_features=0))
+        with pytest.raises(RuntimeError, match="running_mean"):
+            fold(Plain(num_features=C + 4))
+    for key, n in (("alpha", C), ("beta", C)):
+        for bad in (torch.zeros(n - 1), torch.zeros(n, dtype=torch.float64), torch.zeros(2 * n)[::2]):
+            with pytest.raises(RuntimeError, match=key):
+                folds[0](Plain(), **{key: bad})
+    with pytest.raises(RuntimeError, match="beta"):
+        folds[0](Plain(), beta=torch.zeros(C, device="meta"))
+    for bad in (torch.zeros(C), torch.zeros(4 * C, dtype=torch.float64), torch.zeros(8 * C)[::2]):
+        with pytest.raises(RuntimeError, match="consts"):
+            folds[1](Plain(), consts=bad)
+
+
+def test_bn_entry_points_reject_bad_arguments_without_gpu():
+    """The eval batch-norm entry points validate pointers, channel counts and
+    alignment before any device call (the pointers below are never dereferenced)."""
+    from distributed_learning_simulator_amd import _native
+    L = _native.lib()
+    d, odd = ctypes.c_void_p(256), ctypes.c_void_p(260)  # 16- and 4-byte aligned
+    eps = ctypes.c_float(1e-5)
+    # null pointers
+    assert L.dls_bn_fold_f32(None, None, None, d, eps, 8, d, d, None) == -1
+    assert b"null pointer" in L.dls_last_error()
+    assert L.dls_bn_fold_f32(None, None, d, d, eps, 8, d, None, None) == -1
+    assert L.dls_bn_fold_exact_f32(None, None, d, None, eps, 8, d, None) == -1
+    assert L.dls_bn_fold_exact_f32(None, None, d, d, eps, 8, None, None) == -1
+    assert b"null pointer" in L.dls_last_error()
+    assert L.dls_bn_act_nhwc_f32(None, 4, 8, d, d, None, 1, d, None) == -1
+    assert L.dls_bn_act_nhwc_f32(d, 4, 8, d, None, None, 1, d, None) == -1
+    assert L.dls_bn_act_nhwc_f32(d, 4, 8, d, d, None, 1, None, None) == -1
+    assert L.dls_bn_act_exact_nhwc_f32(d, 4, 8, None, None, 1, d, None) == -1
+    assert L.dls_bn_act_exact_nhwc_f32(d, 4, 8, d, None, 1, None, None) == -1
+    assert L.dls_bn_act_exact_nchw_f32(None, 2, 8, 4, d, None, 1, d, None) == -1
+    assert L.dls_bn_act_exact_nchw_f32(d, 2, 8, 4, None, None, 1, d, None) == -1
+    assert L.dls_bn_act_exact_nchw_f32(d, 2, 8, 4, d, None, 1, None, None) == -1
+    assert b"null pointer" in L.dls_last_error()
+    # C <= 0, empty tensors
+    for C in (0, -4):
+        assert L.dls_bn_fold_f32(None, None, d, d, eps, C, d, d, None) == -1
+        assert b"C=" in L.dls_last_error()
+        assert L.dls_bn_fold_exact_f32(None, None, d, d, eps, C, d, None) == -1
+        assert L.dls_bn_act_nhwc_f32(d, 4, C, d, d, None, 1, d, None) == -1
+        assert L.dls_bn_act_exact_nhwc_f32(d, 4, C, d, None, 1, d, None) == -1
+        assert L.dls_bn_act_exact_nchw_f32(d, 2, C, 4, d, None, 1, d, None) == -1
+        assert b"C=" in L.dls_last_error()
+    assert L.dls_bn_act_nhwc_f32(d, 0, 8, d, d, None, 1, d, None) == -1
+    assert L.dls_bn_act_exact_nhwc_f32(d, -1, 8, d, None, 1, d, None) == -1
+    assert L.dls_bn_act_exact_nchw_f32(d, 0, 8, 4, d, None, 1, d, None) == -1
+    assert L.dls_bn_act_exact_nchw_f32(d, 2, 8, 0, d, None, 1, d, None) == -1
+    assert L.dls_bn_act_exact_nchw_f32(d, 2, 8, 1 << 32, d, None, 1, d, None) == -1  # HW / 4 >= 2^30
+    # the NHWC entries read float4 channel groups: C a multiple of 4
+    for C in (6, 7, 13):
+        assert L.dls_bn_act_nhwc_f32(d, 4, C, d, d, None, 1, d, None) == -1
+        assert b"multiple of 4" in L.dls_last_error()
+        assert L.dls_bn_act_exact_nhwc_f32(d, 4, C, d, None, 1, d, None) == -1
+        assert b"multiple of 4" in L.dls_last_error()
+    # ... at 16-byte aligned addresses, every operand
+    for args in ((odd, 4, 8, d, d, None, 1, d, None), (d, 4, 8, odd, d, None, 1, d, None),
+                 (d, 4, 8, d, odd, None, 1, d, None), (d, 4, 8, d, d, odd, 1, d, None),
+                 (d, 4, 8, d, d, None, 1, odd, None)):
+        assert L.dls_bn_act_nhwc_f32(*args) == -2 and b"alignment" in L.dls_last_error()
+    for args in ((odd, 4, 8, d, None, 1, d, None), (d, 4, 8, odd, None, 1, d, None),
+                 (d, 4, 8, d, odd, 1, d, None), (d, 4, 8, d, None, 1, odd, None)):
+        assert L.dls_bn_act_exact_nhwc_f32(*args) == -2 and b"alignment" in L.dls_last_error()
+
+
 def test_library_sources_read_no_environment():
     """The kernels a coalition's utility runs through are chosen from the shapes
     alone: no product source reads the process environment (the convolution
