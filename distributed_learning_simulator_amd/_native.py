@@ -202,6 +202,70 @@ def fedavg(U, rows, weight, total, P, out, mode=FEDAVG_EXACT, stream=None):
     return out
 
 
+def _rows_operands(fn, U, rows, P, names=("U", "rows")):
+    """The checks every rows-family wrapper makes on a matrix, a row table and P
+    (``names``: what the messages call the two tensors): returns (K, P, ldu)."""
+    return (_rows_table(fn, U, rows, names),) + _rows_extent(fn, U, P)
+
+
+def _rows_table(fn, U, rows, names=("U", "rows")):
+    """The first half of ``_rows_operands``, the two tensors: returns K."""
+    if (not torch.is_tensor(U) or U.dtype != torch.float32 or U.dim() != 2
+            or (U.shape[1] > 1 and U.stride(1) != 1)):
+        raise RuntimeError(f"{fn}: {names[0]} must be an fp32 [rows, ld] matrix with unit "
+                           "element stride")
+    if not torch.is_tensor(rows) or rows.dtype != torch.int32 or rows.dim() != 1 \
+            or not rows.is_contiguous():
+        raise RuntimeError(f"{fn}: {names[1]} must be a contiguous int32 [K] tensor")
+    K = rows.numel()
+    if not 1 <= K <= ROBUST_MAX_K:
+        raise RuntimeError(f"{fn}: K={K} rows (1..ROBUST_MAX_K={ROBUST_MAX_K})")
+    return K
+
+
+def _rows_extent(fn, U, P):
+    """The second half, P against the matrix (trimmed_mean checks its trim between the
+    two): returns (P, ldu)."""
+    P = int(P)
+    if P < 0 or P % 4 != 0 or P > U.shape[1]:
+        raise RuntimeError(f"{fn}: P={P} must be a multiple of 4 and at most the row "
+                           f"length {U.shape[1]}")
+    ldu = U.stride(0) if U.shape[0] > 1 else U.shape[1]
+    if ldu % 4 != 0 or ldu < P:
+        raise RuntimeError(f"{fn}: row pitch {ldu} must be a multiple of 4, at least P")
+    return P, ldu
+
+
+def _f32_vector(fn, name, t, P):
+    if (not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 1
+            or t.numel() < P or (t.numel() > 1 and t.stride(0) != 1)):
+        raise RuntimeError(f"{fn}: {name} must be an fp32 vector of at least P={P} elements "
+                           "with unit stride")
+
+
+def _k_tensor(fn, name, t, dtype, shape):
+    """t: a contiguous tensor of ``shape``, (K,) or (K, K), and ``dtype``, fp32 or fp64."""
+    if (not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != shape
+            or not t.is_contiguous()):
+        raise RuntimeError(f"{fn}: {name} must be a contiguous "
+                           f"{'fp32' if dtype == torch.float32 else 'fp64'} "
+                           f"[{', '.join('K' * len(shape))}] = {list(shape)} tensor")
+
+
+def _f64_out(fn, name, t, shape):
+    """An optional output (None: the wrapper allocates it): contiguous fp64 of ``shape``."""
+    if t is not None:
+        _k_tensor(fn, name, t, torch.float64, shape)
+
+
+def _workspace(query_name, K, P, device):
+    """The scratch buffer the library's ``query_name`` asks for (K rows, P elements)."""
+    nbytes = int(getattr(lib(), query_name)(K, P))
+    if nbytes < 0:
+        _check(nbytes, query_name)
+    return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+
+
 def trimmed_mean(U, rows, trim, P, out, stream=None):
     """Coordinate-wise trimmed mean of the K = rows.numel() selected rows of U into
     out[:P] (dls_trimmed_mean_f32): per coordinate the ``trim`` lowest and highest
@@ -210,28 +274,12 @@ def trimmed_mean(U, rows, trim, P, out, stream=None):
     element stride; rows: int32 [K], 1 <= K <= ROBUST_MAX_K; 0 <= 2*trim < K; P a
     multiple of 4, at most the row length."""
     fn = "trimmed_mean"
-    if (not torch.is_tensor(U) or U.dtype != torch.float32 or U.dim() != 2
-            or (U.shape[1] > 1 and U.stride(1) != 1)):
-        raise RuntimeError(f"{fn}: U must be an fp32 [rows, ld] matrix with unit element stride")
-    if not torch.is_tensor(rows) or rows.dtype != torch.int32 or rows.dim() != 1 \
-            or not rows.is_contiguous():
-        raise RuntimeError(f"{fn}: rows must be a contiguous int32 [K] tensor")
-    K = rows.numel()
-    if not 1 <= K <= ROBUST_MAX_K:
-        raise RuntimeError(f"{fn}: K={K} rows (1..ROBUST_MAX_K={ROBUST_MAX_K})")
-    trim, P = int(trim), int(P)
+    K = _rows_table(fn, U, rows)
+    trim = int(trim)
     if trim < 0 or 2 * trim >= K:
         raise RuntimeError(f"{fn}: trim={trim} (0 <= 2*trim < K={K})")
-    if P < 0 or P % 4 != 0 or P > U.shape[1]:
-        raise RuntimeError(f"{fn}: P={P} must be a multiple of 4 and at most the row "
-                           f"length {U.shape[1]}")
-    ldu = U.stride(0) if U.shape[0] > 1 else U.shape[1]
-    if ldu % 4 != 0 or ldu < P:
-        raise RuntimeError(f"{fn}: row pitch {ldu} must be a multiple of 4, at least P")
-    if (not torch.is_tensor(out) or out.dtype != torch.float32 or out.dim() != 1
-            or out.numel() < P or (out.numel() > 1 and out.stride(0) != 1)):
-        raise RuntimeError(f"{fn}: out must be an fp32 vector of at least P={P} elements "
-                           "with unit stride")
+    P, ldu = _rows_extent(fn, U, P)
+    _f32_vector(fn, "out", out, P)
     _check_same_device(fn, U, rows=rows, out=out)
     if U.data_ptr() % 16 != 0 or out.data_ptr() % 16 != 0:
         raise RuntimeError(f"{fn}: U and out must be 16-byte aligned")
@@ -251,81 +299,20 @@ def pairwise_sqdist(U, rows, P, out=None, stream=None):
     1 <= K <= ROBUST_MAX_K; P a multiple of 4, at most the row length; out: a
     contiguous fp64 [K, K] tensor (default: a new one)."""
     fn = "pairwise_sqdist"
-    if (not torch.is_tensor(U) or U.dtype != torch.float32 or U.dim() != 2
-            or (U.shape[1] > 1 and U.stride(1) != 1)):
-        raise RuntimeError(f"{fn}: U must be an fp32 [rows, ld] matrix with unit element stride")
-    if not torch.is_tensor(rows) or rows.dtype != torch.int32 or rows.dim() != 1 \
-            or not rows.is_contiguous():
-        raise RuntimeError(f"{fn}: rows must be a contiguous int32 [K] tensor")
-    K = rows.numel()
-    if not 1 <= K <= ROBUST_MAX_K:
-        raise RuntimeError(f"{fn}: K={K} rows (1..ROBUST_MAX_K={ROBUST_MAX_K})")
-    P = int(P)
-    if P < 0 or P % 4 != 0 or P > U.shape[1]:
-        raise RuntimeError(f"{fn}: P={P} must be a multiple of 4 and at most the row "
-                           f"length {U.shape[1]}")
-    ldu = U.stride(0) if U.shape[0] > 1 else U.shape[1]
-    if ldu % 4 != 0 or ldu < P:
-        raise RuntimeError(f"{fn}: row pitch {ldu} must be a multiple of 4, at least P")
-    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.float64
-                            or tuple(out.shape) != (K, K) or not out.is_contiguous()):
-        raise RuntimeError(f"{fn}: out must be a contiguous fp64 [K, K] = [{K}, {K}] tensor")
+    K, P, ldu = _rows_operands(fn, U, rows, P)
+    _f64_out(fn, "out", out, (K, K))
     _check_same_device(fn, U, rows=rows, out=out)
     if U.data_ptr() % 16 != 0:
         raise RuntimeError(f"{fn}: U must be 16-byte aligned")
     if out is None:
         out = torch.empty((K, K), dtype=torch.float64, device=U.device)
     _ptr(U), _ptr(rows), _ptr(out)  # no CPU path
-    nbytes = int(lib().dls_pairwise_sqdist_workspace(K, P))
-    if nbytes < 0:
-        _check(nbytes, "dls_pairwise_sqdist_workspace")
-    work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=U.device)
+    work = _workspace("dls_pairwise_sqdist_workspace", K, P, U.device)
     _check(lib().dls_pairwise_sqdist_f32(_ptr(U), ldu, _ptr(rows), K, P, _ptr(out), _ptr(work),
                                          _stream(stream, U)), "dls_pairwise_sqdist_f32")
     if stream is not None:
         work.record_stream(stream)
     return out
-
-
-def _rows_operands(fn, U, rows, P):
-    """The checks of pairwise_sqdist on (U, rows, P): returns (K, P, ldu)."""
-    if (not torch.is_tensor(U) or U.dtype != torch.float32 or U.dim() != 2
-            or (U.shape[1] > 1 and U.stride(1) != 1)):
-        raise RuntimeError(f"{fn}: U must be an fp32 [rows, ld] matrix with unit element stride")
-    if not torch.is_tensor(rows) or rows.dtype != torch.int32 or rows.dim() != 1 \
-            or not rows.is_contiguous():
-        raise RuntimeError(f"{fn}: rows must be a contiguous int32 [K] tensor")
-    K = rows.numel()
-    if not 1 <= K <= ROBUST_MAX_K:
-        raise RuntimeError(f"{fn}: K={K} rows (1..ROBUST_MAX_K={ROBUST_MAX_K})")
-    P = int(P)
-    if P < 0 or P % 4 != 0 or P > U.shape[1]:
-        raise RuntimeError(f"{fn}: P={P} must be a multiple of 4 and at most the row "
-                           f"length {U.shape[1]}")
-    ldu = U.stride(0) if U.shape[0] > 1 else U.shape[1]
-    if ldu % 4 != 0 or ldu < P:
-        raise RuntimeError(f"{fn}: row pitch {ldu} must be a multiple of 4, at least P")
-    return K, P, ldu
-
-
-def _gram_operands(fn, U, P, base, out, K):
-    """base: None or an fp32 vector of at least P elements; out: None or a contiguous
-    fp64 [K, K] tensor."""
-    if base is not None and (not torch.is_tensor(base) or base.dtype != torch.float32
-                             or base.dim() != 1 or base.numel() < P
-                             or (base.numel() > 1 and base.stride(0) != 1)):
-        raise RuntimeError(f"{fn}: base must be an fp32 vector of at least P={P} elements "
-                           "with unit stride")
-    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.float64
-                            or tuple(out.shape) != (K, K) or not out.is_contiguous()):
-        raise RuntimeError(f"{fn}: out must be a contiguous fp64 [K, K] = [{K}, {K}] tensor")
-
-
-def _gram_work(K, P, device):
-    nbytes = int(lib().dls_rows_gram_workspace(K, P))
-    if nbytes < 0:
-        _check(nbytes, "dls_rows_gram_workspace")
-    return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
 
 
 def rows_gram(U, rows, P, base=None, out=None, stream=None):
@@ -340,14 +327,16 @@ def rows_gram(U, rows, P, base=None, out=None, stream=None):
     a new one)."""
     fn = "rows_gram"
     K, P, ldu = _rows_operands(fn, U, rows, P)
-    _gram_operands(fn, U, P, base, out, K)
+    if base is not None:
+        _f32_vector(fn, "base", base, P)
+    _f64_out(fn, "out", out, (K, K))
     _check_same_device(fn, U, rows=rows, base=base, out=out)
     if U.data_ptr() % 16 != 0 or (base is not None and base.data_ptr() % 16 != 0):
         raise RuntimeError(f"{fn}: U and base must be 16-byte aligned")
     if out is None:
         out = torch.empty((K, K), dtype=torch.float64, device=U.device)
     _ptr(U), _ptr(rows), _ptr(base), _ptr(out)  # no CPU path
-    work = _gram_work(K, P, U.device)
+    work = _workspace("dls_rows_gram_workspace", K, P, U.device)
     _check(lib().dls_rows_gram_f32(_ptr(U), ldu, _ptr(rows), K, P, _ptr(base), _ptr(out),
                                    _ptr(work), _stream(stream, U)), "dls_rows_gram_f32")
     if stream is not None:
@@ -367,14 +356,12 @@ def history_gram(U, rows, H, hrows, P, base=None, out=None, stream=None):
     ``hrows`` distinct (two lanes folding into one row would race).  Returns (H, G)."""
     fn = "history_gram"
     K, P, ldu = _rows_operands(fn, U, rows, P)
-    try:
-        Kh, _, ldh = _rows_operands(fn, H, hrows, P)
-    except RuntimeError as e:
-        raise RuntimeError(str(e).replace("U must be", "H must be")
-                           .replace("rows must be", "hrows must be")) from None
+    Kh, _, ldh = _rows_operands(fn, H, hrows, P, names=("H", "hrows"))
     if Kh != K:
         raise RuntimeError(f"{fn}: hrows holds {Kh} rows, rows holds {K}")
-    _gram_operands(fn, U, P, base, out, K)
+    if base is not None:
+        _f32_vector(fn, "base", base, P)
+    _f64_out(fn, "out", out, (K, K))
     _check_same_device(fn, U, rows=rows, H=H, hrows=hrows, base=base, out=out)
     if U.data_ptr() % 16 != 0 or H.data_ptr() % 16 != 0 \
             or (base is not None and base.data_ptr() % 16 != 0):
@@ -390,7 +377,7 @@ def history_gram(U, rows, H, hrows, P, base=None, out=None, stream=None):
             raise RuntimeError(f"{fn}: hrows must be distinct, not {idx}")
     if out is None:
         out = torch.empty((K, K), dtype=torch.float64, device=U.device)
-    work = _gram_work(K, P, U.device)
+    work = _workspace("dls_rows_gram_workspace", K, P, U.device)
     _check(lib().dls_history_gram_f32(_ptr(U), ldu, _ptr(rows), _ptr(H), ldh, _ptr(hrows), K, P,
                                       _ptr(base), _ptr(out), _ptr(work), _stream(stream, U)),
            "dls_history_gram_f32")
@@ -413,10 +400,7 @@ def mean_around_median(U, rows, keep, P, out, stream=None):
     keep = int(keep)
     if not 1 <= keep <= K:
         raise RuntimeError(f"{fn}: keep={keep} (1 <= keep <= K={K})")
-    if (not torch.is_tensor(out) or out.dtype != torch.float32 or out.dim() != 1
-            or out.numel() < P or (out.numel() > 1 and out.stride(0) != 1)):
-        raise RuntimeError(f"{fn}: out must be an fp32 vector of at least P={P} elements "
-                           "with unit stride")
+    _f32_vector(fn, "out", out, P)
     _check_same_device(fn, U, rows=rows, out=out)
     if U.data_ptr() % 16 != 0 or out.data_ptr() % 16 != 0:
         raise RuntimeError(f"{fn}: U and out must be 16-byte aligned")
@@ -444,11 +428,8 @@ def craft_rows(U, hrows, arows, a, b, P, base=None, stream=None):
     a, b = float(a), float(b)
     if not (math.isfinite(a) and math.isfinite(b)):
         raise RuntimeError(f"{fn}: a={a} and b={b} must be finite")
-    if base is not None and (not torch.is_tensor(base) or base.dtype != torch.float32
-                             or base.dim() != 1 or base.numel() < P
-                             or (base.numel() > 1 and base.stride(0) != 1)):
-        raise RuntimeError(f"{fn}: base must be an fp32 vector of at least P={P} elements "
-                           "with unit stride")
+    if base is not None:
+        _f32_vector(fn, "base", base, P)
     _check_same_device(fn, U, hrows=hrows, arows=arows, base=base)
     if U.data_ptr() % 16 != 0 or (base is not None and base.data_ptr() % 16 != 0):
         raise RuntimeError(f"{fn}: U and base must be 16-byte aligned")
@@ -461,26 +442,6 @@ def craft_rows(U, hrows, arows, a, b, P, base=None, stream=None):
     return U
 
 
-def _point_operands(fn, U, K, P, z, dist2, name):
-    """z: an fp32 vector of at least P elements; dist2: None or a contiguous fp64 [K]
-    tensor (``name`` in messages).  Returns dist2 (a new tensor when None)."""
-    if (not torch.is_tensor(z) or z.dtype != torch.float32 or z.dim() != 1
-            or z.numel() < P or (z.numel() > 1 and z.stride(0) != 1)):
-        raise RuntimeError(f"{fn}: z must be an fp32 vector of at least P={P} elements "
-                           "with unit stride")
-    if dist2 is not None and (not torch.is_tensor(dist2) or dist2.dtype != torch.float64
-                              or tuple(dist2.shape) != (K,) or not dist2.is_contiguous()):
-        raise RuntimeError(f"{fn}: {name} must be a contiguous fp64 [K] = [{K}] tensor")
-    return dist2
-
-
-def _weiszfeld_work(K, P, device):
-    nbytes = int(lib().dls_weiszfeld_workspace(K, P))
-    if nbytes < 0:
-        _check(nbytes, "dls_weiszfeld_workspace")
-    return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
-
-
 def rows_sqdist_to(U, rows, P, z, out=None, stream=None):
     """Squared Euclidean distances of the K = rows.numel() selected rows of U to the
     point z over their first P elements (dls_rows_sqdist_to_f32): an fp64 [K] device
@@ -491,14 +452,15 @@ def rows_sqdist_to(U, rows, P, z, out=None, stream=None):
     tensor (default: a new one)."""
     fn = "rows_sqdist_to"
     K, P, ldu = _rows_operands(fn, U, rows, P)
-    out = _point_operands(fn, U, K, P, z, out, "out")
+    _f32_vector(fn, "z", z, P)
+    _f64_out(fn, "out", out, (K,))
     _check_same_device(fn, U, rows=rows, z=z, out=out)
     if U.data_ptr() % 16 != 0 or z.data_ptr() % 16 != 0:
         raise RuntimeError(f"{fn}: U and z must be 16-byte aligned")
     if out is None:
         out = torch.empty((K,), dtype=torch.float64, device=U.device)
     _ptr(U), _ptr(rows), _ptr(z), _ptr(out)  # no CPU path
-    work = _weiszfeld_work(K, P, U.device)
+    work = _workspace("dls_weiszfeld_workspace", K, P, U.device)
     _check(lib().dls_rows_sqdist_to_f32(_ptr(U), ldu, _ptr(rows), K, P, _ptr(z), _ptr(out),
                                         _ptr(work), _stream(stream, U)), "dls_rows_sqdist_to_f32")
     if stream is not None:
@@ -515,17 +477,16 @@ def weiszfeld_step(U, rows, w, P, z, dist2=None, stream=None):
     rows_sqdist_to.  Returns (z, dist2)."""
     fn = "weiszfeld_step"
     K, P, ldu = _rows_operands(fn, U, rows, P)
-    if (not torch.is_tensor(w) or w.dtype != torch.float32 or tuple(w.shape) != (K,)
-            or not w.is_contiguous()):
-        raise RuntimeError(f"{fn}: w must be a contiguous fp32 [K] = [{K}] tensor")
-    dist2 = _point_operands(fn, U, K, P, z, dist2, "dist2")
+    _k_tensor(fn, "w", w, torch.float32, (K,))
+    _f32_vector(fn, "z", z, P)
+    _f64_out(fn, "dist2", dist2, (K,))
     _check_same_device(fn, U, rows=rows, w=w, z=z, dist2=dist2)
     if U.data_ptr() % 16 != 0 or z.data_ptr() % 16 != 0:
         raise RuntimeError(f"{fn}: U and z must be 16-byte aligned")
     if dist2 is None:
         dist2 = torch.empty((K,), dtype=torch.float64, device=U.device)
     _ptr(U), _ptr(rows), _ptr(w), _ptr(z), _ptr(dist2)  # no CPU path
-    work = _weiszfeld_work(K, P, U.device)
+    work = _workspace("dls_weiszfeld_workspace", K, P, U.device)
     _check(lib().dls_weiszfeld_step_f32(_ptr(U), ldu, _ptr(rows), K, _ptr(w), P, _ptr(z),
                                         _ptr(dist2), _ptr(work), _stream(stream, U)),
            "dls_weiszfeld_step_f32")
@@ -544,17 +505,16 @@ def centered_clip_step(U, rows, c, P, z, dist2=None, stream=None):
     in rows_sqdist_to.  Returns (z, dist2)."""
     fn = "centered_clip_step"
     K, P, ldu = _rows_operands(fn, U, rows, P)
-    if (not torch.is_tensor(c) or c.dtype != torch.float32 or tuple(c.shape) != (K,)
-            or not c.is_contiguous()):
-        raise RuntimeError(f"{fn}: c must be a contiguous fp32 [K] = [{K}] tensor")
-    dist2 = _point_operands(fn, U, K, P, z, dist2, "dist2")
+    _k_tensor(fn, "c", c, torch.float32, (K,))
+    _f32_vector(fn, "z", z, P)
+    _f64_out(fn, "dist2", dist2, (K,))
     _check_same_device(fn, U, rows=rows, c=c, z=z, dist2=dist2)
     if U.data_ptr() % 16 != 0 or z.data_ptr() % 16 != 0:
         raise RuntimeError(f"{fn}: U and z must be 16-byte aligned")
     if dist2 is None:
         dist2 = torch.empty((K,), dtype=torch.float64, device=U.device)
     _ptr(U), _ptr(rows), _ptr(c), _ptr(z), _ptr(dist2)  # no CPU path
-    work = _weiszfeld_work(K, P, U.device)
+    work = _workspace("dls_weiszfeld_workspace", K, P, U.device)
     _check(lib().dls_centered_clip_step_f32(_ptr(U), ldu, _ptr(rows), K, _ptr(c), P, _ptr(z),
                                             _ptr(dist2), _ptr(work), _stream(stream, U)),
            "dls_centered_clip_step_f32")

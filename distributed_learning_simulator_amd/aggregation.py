@@ -33,6 +33,20 @@ def _f32(xs, device):
     return torch.tensor(list(xs), dtype=torch.float32).to(device, non_blocking=True)
 
 
+def finite_number(name, v, positive=False):
+    """float(v); ValueError unless v is a finite (``positive``: and positive) int or float."""
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) \
+            or (positive and v <= 0):
+        raise ValueError(f"{name} must be a {'positive finite' if positive else 'finite'} "
+                         f"number, not {v!r}")
+    return float(v)
+
+
+def _finite_distances(dist2):
+    """The indices of the squared distances that are finite and not negative."""
+    return [k for k, v in enumerate(dist2) if math.isfinite(v) and v >= 0.0]
+
+
 def union_order(subsets):
     """One client order that lists every subset's clients in that subset's own
     order (a topological merge of the subsets), or None if there is none (two
@@ -171,12 +185,9 @@ def weiszfeld_weights(dist2, nu):
     order, and weights[j] = float32(beta_i / S) (a Python float holding the fp32
     value) for the j-th kept index i.  ValueError: nothing is kept, or ``nu`` is not
     a positive finite number."""
-    if isinstance(nu, bool) or not isinstance(nu, (int, float)) or not math.isfinite(nu) \
-            or nu <= 0:
-        raise ValueError(f"nu must be a positive finite number, not {nu!r}")
-    nu = float(nu)
+    nu = finite_number("nu", nu, positive=True)
     d2 = [float(v) for v in dist2]
-    kept = [i for i, v in enumerate(d2) if math.isfinite(v) and v >= 0.0]
+    kept = _finite_distances(d2)
     if not kept:
         raise ValueError(f"no client has a finite distance (0 of {len(d2)})")
     beta = [1.0 / max(nu, math.sqrt(d2[i])) for i in kept]
@@ -197,12 +208,9 @@ def clip_scales(dist2, tau):
     float32(s_i / n_kept) (a Python float holding the fp32 value) for the j-th kept
     index i: what dls_centered_clip_step_f32 multiplies the client's difference by.
     ValueError: nothing is kept, or ``tau`` is not a positive finite number."""
-    if isinstance(tau, bool) or not isinstance(tau, (int, float)) or not math.isfinite(tau) \
-            or tau <= 0:
-        raise ValueError(f"tau must be a positive finite number, not {tau!r}")
-    tau = float(tau)
+    tau = finite_number("tau", tau, positive=True)
     d2 = [float(v) for v in dist2]
-    kept = [i for i, v in enumerate(d2) if math.isfinite(v) and v >= 0.0]
+    kept = _finite_distances(d2)
     if not kept:
         raise ValueError(f"no client has a finite distance (0 of {len(d2)})")
     dist = [math.sqrt(d2[i]) for i in kept]
@@ -238,17 +246,14 @@ def foolsgold_weights(G, kappa=1.0):
     its maximum cosine after pardoning; nan for a rejected or a single client) and
     ``rejected`` (ascending indices).  ValueError: G is not [K, K] with K >= 1, or
     ``kappa`` is not a positive finite number."""
-    if isinstance(kappa, bool) or not isinstance(kappa, (int, float)) \
-            or not math.isfinite(kappa) or kappa <= 0:
-        raise ValueError(f"kappa must be a positive finite number, not {kappa!r}")
-    kappa = float(kappa)
+    kappa = finite_number("kappa", kappa, positive=True)
     M = [[float(v) for v in row] for row in G]
     K = len(M)
     if K < 1 or any(len(r) != K for r in M):
         raise ValueError(f"G must be a [K, K] matrix with K >= 1, not {K} rows of lengths "
                          f"{sorted({len(r) for r in M})}")
-    rejected = [i for i in range(K) if not (math.isfinite(M[i][i]) and M[i][i] >= 0.0)]
-    live = [i for i in range(K) if i not in set(rejected)]
+    live = _finite_distances([M[i][i] for i in range(K)])
+    rejected = [i for i in range(K) if i not in live]
     alpha = [0.0] * K
     sim = [math.nan] * K
     info = {"similarity": sim, "rejected": rejected}
@@ -316,16 +321,11 @@ def attack_coefficients(attack, n, f, z=None, eps=0.1):
     manipulation, Xie, Koyejo & Gupta 2019) sends -eps times the honest mean update
     relative to the previous global model, (-eps, 0.0, True).  ValueError: another
     attack name, or a z / eps that is not a finite number."""
-    def finite(name, v):
-        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
-            raise ValueError(f"{name} must be a finite number, not {v!r}")
-        return float(v)
-
     if attack == "alie":
-        z = alie_z(n, f) if z is None else finite("z", z)
+        z = alie_z(n, f) if z is None else finite_number("z", z)
         return 1.0, -z, False
     if attack == "ipm":
-        return -finite("eps", eps), 0.0, True
+        return -finite_number("eps", eps), 0.0, True
     raise ValueError(f"attack_coefficients: attack must be 'alie' or 'ipm', not {attack!r}")
 
 
@@ -389,15 +389,22 @@ class ClientUpdateStore:
         (multiples of 4) reduces only flat elements [c0, c1) into ``out`` (of that
         length); rows / ns may then be device int32 / fp32 tensors, reused across
         column ranges."""
-        c0, c1 = cols if cols is not None else (0, self.layout.P)
-        if out is None:
-            out = torch.empty(c1 - c0, dtype=torch.float32, device=self.device)
+        U, r, width = self._reduced(rows, cols)
         if total is None:
             total = sum(int(n) for n in ns)
-        r = rows if torch.is_tensor(rows) else _i32(rows, self.device)
         w = ns if torch.is_tensor(ns) else _f32([int(n) for n in ns], self.device)
-        _native.fedavg(self.U[:, c0:], r, w, float(total), c1 - c0, out, mode=mode)
-        return out
+        return _native.fedavg(U, r, w, float(total), width, self._vector(width, out), mode=mode)
+
+    def _reduced(self, rows, cols):
+        """What a call over ``cols = (c0, c1)`` (default: every column) of ``rows`` hands
+        its kernel: U from column c0 on, the rows as a device int32 tensor, c1 - c0."""
+        c0, c1 = cols if cols is not None else (0, self.layout.P)
+        r = rows if torch.is_tensor(rows) else _i32(rows, self.device)
+        return self.U[:, c0:], r, c1 - c0
+
+    def _vector(self, n, out=None):
+        """``out``, or a new fp32 device vector of n elements."""
+        return torch.empty(n, dtype=torch.float32, device=self.device) if out is None else out
 
     def trimmed_mean(self, rows, trim, out=None, cols=None):
         """Coordinate-wise trimmed mean of the given rows (dls_trimmed_mean_f32): per
@@ -405,12 +412,8 @@ class ClientUpdateStore:
         the rest averaged in ascending order.  The clients' sample counts play no
         part, and the result is the same bits for any order of ``rows``.  K <=
         _native.ROBUST_MAX_K, 0 <= 2*trim < K; ``cols`` as in ``fedavg``."""
-        c0, c1 = cols if cols is not None else (0, self.layout.P)
-        if out is None:
-            out = torch.empty(c1 - c0, dtype=torch.float32, device=self.device)
-        r = rows if torch.is_tensor(rows) else _i32(rows, self.device)
-        _native.trimmed_mean(self.U[:, c0:], r, trim, c1 - c0, out)
-        return out
+        U, r, width = self._reduced(rows, cols)
+        return _native.trimmed_mean(U, r, trim, width, self._vector(width, out))
 
     def median(self, rows, out=None, cols=None):
         """Coordinate-wise median of the given rows: ``trimmed_mean`` with
@@ -425,12 +428,8 @@ class ClientUpdateStore:
         2018; stage 2 of Bulyan).  The sample counts play no part, and the result is the
         same bits for any order of ``rows``.  K <= _native.ROBUST_MAX_K, 1 <= keep <= K;
         ``cols`` as in ``fedavg``."""
-        c0, c1 = cols if cols is not None else (0, self.layout.P)
-        if out is None:
-            out = torch.empty(c1 - c0, dtype=torch.float32, device=self.device)
-        r = rows if torch.is_tensor(rows) else _i32(rows, self.device)
-        _native.mean_around_median(self.U[:, c0:], r, keep, c1 - c0, out)
-        return out
+        U, r, width = self._reduced(rows, cols)
+        return _native.mean_around_median(U, r, keep, width, self._vector(width, out))
 
     def craft(self, honest_rows, attacker_rows, a, b, base=None, cols=None):
         """Rewrite the attacker rows in place from the honest rows (dls_craft_rows_f32):
@@ -466,13 +465,11 @@ class ClientUpdateStore:
         of ``layout.P`` elements, the previous global model); without ``base``, x <-
         -(scale * x).  Three elementwise fp32 operations in this order, each rounded
         once: d = x - base; d *= fl32(scale); x = base - d."""
-        if isinstance(scale, bool) or not isinstance(scale, (int, float)) \
-                or not math.isfinite(scale):
-            raise ValueError(f"scale must be a finite number, not {scale!r}")
+        scale = finite_number("scale", scale)
         rows = [int(r) for r in rows]
         if len(set(rows)) != len(rows):
             raise ValueError(f"sign_flip: a row is listed twice: {rows}")
-        scale = torch.tensor(float(scale), dtype=torch.float32).item()  # its fp32 value
+        scale = torch.tensor(scale, dtype=torch.float32).item()  # its fp32 value
         for r in rows:
             x = self.U[r]
             if base is None:
@@ -488,9 +485,8 @@ class ClientUpdateStore:
         an fp64 [K, K] device tensor, symmetric in bits, +0.0 on the diagonal, the
         same bits under any permutation of ``rows`` (permuted).  K <=
         _native.ROBUST_MAX_K; ``cols`` as in ``fedavg``."""
-        c0, c1 = cols if cols is not None else (0, self.layout.P)
-        r = rows if torch.is_tensor(rows) else _i32(rows, self.device)
-        return _native.pairwise_sqdist(self.U[:, c0:], r, c1 - c0)
+        U, r, width = self._reduced(rows, cols)
+        return _native.pairwise_sqdist(U, r, width)
 
     def multi_krum(self, rows, ids, byzantine, select, out=None):
         """Multi-Krum over the given rows (client ``ids[i]`` in ``rows[i]``): one distance
@@ -534,9 +530,56 @@ class ClientUpdateStore:
         """Squared Euclidean distances of the given rows to ``point`` (an fp32 device
         vector of the reduced length; dls_rows_sqdist_to_f32): an fp64 [K] device
         tensor.  K <= _native.ROBUST_MAX_K; ``cols`` as in ``fedavg``."""
-        c0, c1 = cols if cols is not None else (0, self.layout.P)
-        r = rows if torch.is_tensor(rows) else _i32(rows, self.device)
-        return _native.rows_sqdist_to(self.U[:, c0:], r, c1 - c0, point)
+        U, r, width = self._reduced(rows, cols)
+        return _native.rows_sqdist_to(U, r, width, point)
+
+    @staticmethod
+    def _in_id_order(name, rows, ids, iters):
+        """(int(iters), the clients as [(id, row)] in id order) of the iterated rules;
+        ValueError unless iters >= 1 and every row has one distinct id."""
+        iters = int(iters)
+        if iters < 1:
+            raise ValueError(f"iters={iters} must be at least 1")
+        ids = list(ids)
+        if len(set(ids)) != len(ids) or len(ids) != len(rows):
+            raise ValueError(f"{name} needs one distinct id per row")
+        return iters, sorted(zip(ids, (int(r) for r in rows)))
+
+    def _iterate(self, name, active, iters, flat, step, info, trace):
+        """The passes ``geometric_median`` and ``centered_clip`` share: one distance pass of
+        the clients ``active`` against the iterate ``flat``, then ``iters`` times
+        ``step(it, active, d2)``, which moves ``flat`` from the squared distances d2 of the
+        clients that go on and returns (the fp32 coefficients it used, the fp64 device
+        tensor of their squared distances to the new iterate), each followed by one copy
+        of those distances to the host.  After every pass the clients whose distance is
+        not finite are rejected for the rest of the call; ValueError when none is left.
+        Fills ``info``: ``rejected`` (sorted ids), ``distances`` {id: distance to the
+        last iterate} and, with ``trace``, per pass the (ids, coefficients or None, dist2)
+        the pass ran on and gave.  Returns per pass the squared distances that went on."""
+        K, passes, settled = len(active), [], []
+
+        def settle(coeffs, d2):
+            """Book one pass's distances; the clients that go on."""
+            if trace:
+                passes.append(([i for i, _ in active], coeffs, list(d2)))
+            good = _finite_distances(d2)
+            info["rejected"] = sorted(info["rejected"]
+                                      + [active[k][0] for k in range(len(d2)) if k not in good])
+            if not good:
+                raise ValueError(f"{name}: no client is at a finite distance from the "
+                                 f"iterate after pass {len(settled)} "
+                                 f"({K - len(info['rejected'])} of {K} finite)")
+            settled.append([d2[k] for k in good])
+            return [active[k] for k in good]
+
+        active = settle(None, self.sqdist_to([r for _, r in active], flat).cpu().tolist())
+        for it in range(iters):
+            coeffs, dist2 = step(it, active, settled[-1])
+            active = settle(coeffs, dist2.cpu().tolist())
+        info["distances"] = {i: math.sqrt(v) for (i, _), v in zip(active, settled[-1])}
+        if trace:
+            info["trace"] = passes
+        return settled
 
     def geometric_median(self, rows, ids, iters, nu, out=None, trace=False):
         """The geometric median of the given rows (client ``ids[i]`` in ``rows[i]``) by
@@ -551,45 +594,21 @@ class ClientUpdateStore:
         ``objective`` (the sum of distances after the start and after each step, added
         in id order) and, with ``trace``, per pass the (ids, fp32 weights or None,
         dist2) the pass ran on and gave."""
-        iters = int(iters)
-        if iters < 1:
-            raise ValueError(f"iters={iters} must be at least 1")
-        ids = list(ids)
-        if len(set(ids)) != len(ids) or len(ids) != len(rows):
-            raise ValueError("geometric_median needs one distinct id per row")
-        active = sorted(zip(ids, (int(r) for r in rows)))
-        K, P = len(active), self.layout.P
+        iters, active = self._in_id_order("geometric_median", rows, ids, iters)
         flat = self.median([r for _, r in active], out=out)
         info = {"distances": {}, "rejected": [], "objective": []}
-        passes = []
 
-        def settle(weights, d2):
-            """Book one pass's distances; the clients that go on."""
-            if trace:
-                passes.append(([i for i, _ in active], weights, list(d2)))
-            good = [k for k, v in enumerate(d2) if math.isfinite(v) and v >= 0.0]
-            info["rejected"] = sorted(info["rejected"]
-                                      + [active[k][0] for k in range(len(d2)) if k not in good])
-            if not good:
-                raise ValueError(f"geometric_median: no client is at a finite distance from the "
-                                 f"iterate after pass {len(info['objective'])} "
-                                 f"({K - len(info['rejected'])} of {K} finite)")
-            obj = 0.0
-            for k in good:
-                obj += math.sqrt(d2[k])
-            info["objective"].append(obj)
-            return [active[k] for k in good], [d2[k] for k in good]
-
-        d2 = self.sqdist_to([r for _, r in active], flat).cpu().tolist()
-        active, d2 = settle(None, d2)
-        for _ in range(iters):
+        def step(it, active, d2):
             _, weights = weiszfeld_weights(d2, nu)
             _, dist2 = _native.weiszfeld_step(self.U, _i32([r for _, r in active], self.device),
-                                              _f32(weights, self.device), P, flat)
-            active, d2 = settle(weights, dist2.cpu().tolist())
-        info["distances"] = {i: math.sqrt(v) for (i, _), v in zip(active, d2)}
-        if trace:
-            info["trace"] = passes
+                                              _f32(weights, self.device), self.layout.P, flat)
+            return weights, dist2
+
+        for d2 in self._iterate("geometric_median", active, iters, flat, step, info, trace):
+            obj = 0.0
+            for v in d2:
+                obj += math.sqrt(v)
+            info["objective"].append(obj)
         return flat, info
 
     def centered_clip(self, rows, ids, start, tau, iters, out=None, trace=False):
@@ -611,41 +630,18 @@ class ClientUpdateStore:
         step is kept, and one device norm of the fp32 difference per step, summed in
         fp64, is copied to the host once at the end) and, with ``trace``, per pass the
         (ids, fp32 coefficients or None, dist2) the pass ran on and gave."""
-        iters = int(iters)
-        if iters < 1:
-            raise ValueError(f"iters={iters} must be at least 1")
-        ids = list(ids)
-        if len(set(ids)) != len(ids) or len(ids) != len(rows):
-            raise ValueError("centered_clip needs one distinct id per row")
-        active = sorted(zip(ids, (int(r) for r in rows)))
-        K, P = len(active), self.layout.P
+        iters, active = self._in_id_order("centered_clip", rows, ids, iters)
+        P = self.layout.P
         if (not torch.is_tensor(start) or start.dtype != torch.float32 or start.dim() != 1
                 or start.numel() != P or start.device != self.U.device):
             raise ValueError(f"start must be an fp32 vector of P={P} elements on {self.U.device}")
-        flat = torch.empty(P, dtype=torch.float32, device=self.device) if out is None else out
+        flat = self._vector(P, out)
         flat.copy_(start)
         prev = torch.empty_like(flat)
         moved = torch.zeros(iters, dtype=torch.float64, device=self.device)
         info = {"distances": {}, "rejected": [], "scales": {}, "moved": []}
-        passes, n_pass = [], [0]
 
-        def settle(coeffs, d2):
-            """Book one pass's distances; the clients that go on."""
-            if trace:
-                passes.append(([i for i, _ in active], coeffs, list(d2)))
-            good = [k for k, v in enumerate(d2) if math.isfinite(v) and v >= 0.0]
-            info["rejected"] = sorted(info["rejected"]
-                                      + [active[k][0] for k in range(len(d2)) if k not in good])
-            if not good:
-                raise ValueError(f"centered_clip: no client is at a finite distance from the "
-                                 f"iterate after pass {n_pass[0]} "
-                                 f"({K - len(info['rejected'])} of {K} finite)")
-            n_pass[0] += 1
-            return [active[k] for k in good], [d2[k] for k in good]
-
-        d2 = self.sqdist_to([r for _, r in active], flat).cpu().tolist()
-        active, d2 = settle(None, d2)
-        for it in range(iters):
+        def step(it, active, d2):
             _, scales, coeffs = clip_scales(d2, tau)
             info["scales"] = {i: s for (i, _), s in zip(active, scales)}
             prev.copy_(flat)
@@ -653,11 +649,10 @@ class ClientUpdateStore:
                 self.U, _i32([r for _, r in active], self.device), _f32(coeffs, self.device), P,
                 flat)
             moved[it] = torch.linalg.vector_norm(flat - prev, dtype=torch.float64)
-            active, d2 = settle(coeffs, dist2.cpu().tolist())
-        info["distances"] = {i: math.sqrt(v) for (i, _), v in zip(active, d2)}
+            return coeffs, dist2
+
+        self._iterate("centered_clip", active, iters, flat, step, info, trace)
         info["moved"] = moved.cpu().tolist()
-        if trace:
-            info["trace"] = passes
         return flat, info
 
     def gram(self, rows, base=None, cols=None):
@@ -666,9 +661,8 @@ class ClientUpdateStore:
         bits under any permutation of ``rows`` (permuted); a cosine from it is within
         2^-17 absolute.  ``base``: an fp32 device vector of the reduced length.  K <=
         _native.ROBUST_MAX_K; ``cols`` as in ``fedavg``."""
-        c0, c1 = cols if cols is not None else (0, self.layout.P)
-        r = rows if torch.is_tensor(rows) else _i32(rows, self.device)
-        return _native.rows_gram(self.U[:, c0:], r, c1 - c0, base=base)
+        U, r, width = self._reduced(rows, cols)
+        return _native.rows_gram(U, r, width, base=base)
 
     def _history_rows(self, n):
         """The history buffer with at least ``n`` rows (one per worker id), zeroed on
@@ -747,7 +741,7 @@ class ClientUpdateStore:
         info = {"weights": dict(zip(sids, alpha)),
                 "similarity": dict(zip(sids, winfo["similarity"])),
                 "rejected": [sids[i] for i in winfo["rejected"]], "coefficients": {}}
-        flat = torch.empty(P, dtype=torch.float32, device=self.device) if out is None else out
+        flat = self._vector(P, out)
         flat.copy_(base)
         kept = [k for k, a in enumerate(alpha) if a > 0.0]
         total = 0.0

@@ -156,8 +156,9 @@ class ShardedFedServer(_ShardedMixin, FedServer):
                            "ranks, which a coordinate-wise order statistic is not")
 
     def __init__(self, group=None, chunks=3, exchange="allreduce", order="arrival", **kwargs):
-        self._check_rule(kwargs.get("aggregation_rule", "mean"), kwargs.get("trim", 0),
-                         kwargs.get("aggregation_mode", "exact"), kwargs.get("worker_number"))
+        self._check_rule(kwargs.get("aggregation_rule", "mean"),
+                         kwargs.get("aggregation_mode", "exact"), kwargs.get("worker_number"),
+                         **{k: kwargs[k] for k in ("trim",) if k in kwargs})
         if exchange not in ("allreduce", "alltoall"):
             raise ValueError(f"exchange must be 'allreduce' or 'alltoall', not {exchange!r}")
         if order not in ("arrival", "worker_id"):

@@ -6,10 +6,10 @@ loop of K x (#tensors) torch ops, bit-exact with the reference's op order.
 """
 import copy
 import logging
-import math
 
 from .. import _native
-from ..aggregation import ATTACKS, ClientParameters, ClientUpdateStore, attack_coefficients
+from ..aggregation import (ATTACKS, ClientParameters, ClientUpdateStore, attack_coefficients,
+                           finite_number)
 from ..layout import ParameterLayout
 from ..model_util import ModelUtil
 from ..task_queue import RepeatedResult
@@ -18,13 +18,59 @@ from .server import Server
 log = logging.getLogger("distributed_learning_simulator_amd")
 
 _MODES = {"exact": _native.FEDAVG_EXACT, "fma": _native.FEDAVG_FMA}
-_RULES = ("mean", "median", "trimmed_mean", "multi_krum", "geometric_median", "centered_clip",
-          "mean_around_median", "bulyan", "foolsgold")
-_BYZANTINE_RULES = ("multi_krum", "bulyan", "mean_around_median")
-_GM_ITERS, _GM_NU = 3, 1e-6  # the defaults of RFA (Pillutla et al.)
-_CC_TAU, _CC_ITERS = 10.0, 3
-_FG_KAPPA = 1.0  # the paper's confidence parameter
-_ATTACK_EPS, _ATTACK_SCALE = 0.1, 1.0
+# The rules' constructor parameters and their defaults (gm_*: RFA's, Pillutla et al.;
+# fg_kappa: the paper's confidence), in the order they are checked.
+DEFAULTS = {"trim": 0, "byzantine": 0, "krum_select": None, "gm_iters": 3, "gm_nu": 1e-6,
+            "cc_iters": 3, "cc_tau": 10.0, "fg_kappa": 1.0}
+_AT_LEAST = {"trim": 0, "byzantine": 0, "gm_iters": 1, "cc_iters": 1}  # the integer ones
+ATTACK_DEFAULTS = {"attack_z": None, "attack_eps": 0.1, "attack_scale": 1.0}
+_ATTACK_OF = {"attack_z": "alie", "attack_eps": "ipm", "attack_scale": "sign_flip"}
+# What a parameter set under a rule that does not own it is told: the parameters the
+# message lists and the rule it names.
+_GROUPS = ((("trim",), "trimmed_mean"), (("byzantine", "krum_select"), "multi_krum"),
+           (("gm_iters", "gm_nu"), "geometric_median"), (("cc_tau", "cc_iters"), "centered_clip"),
+           (("fg_kappa",), "foolsgold"))
+# Every robust rule needs 2*trim < K (trim is 0 under all but the trimmed mean).
+_TRIM_FITS = (lambda K, p: 2 * p["trim"] < K,
+              "trim={trim} leaves nothing of {clients} (2*trim < {n} is needed)")
+# The rules, in the order they are listed to the user.  owns: the constructor parameters
+# the rule takes; ids: whether get_subset_model hands it the worker ids (it reports,
+# breaks ties and orders by them); count: its condition on the number of clients K, a
+# predicate of (K, parameters) and the message when it fails (_count_error fills in
+# {group}, {clients} and {n}); run: the FedServer method (store, rows, ids) -> flat.
+RULES = {
+    "mean": dict(owns=(), ids=False, count=None, run=None),  # store.fedavg, with the n_i
+    "median": dict(owns=(), ids=False, count=None, run="_median"),
+    "trimmed_mean": dict(owns=("trim",), ids=False, count=None, run="_trimmed_mean"),
+    "multi_krum": dict(owns=("byzantine", "krum_select"), ids=True, run="_multi_krum", count=(
+        lambda K, p: 2 * p["byzantine"] + 3 <= K,
+        "byzantine={byzantine} is too many for {group} (2*byzantine + 3 <= {n} is needed)")),
+    "geometric_median": dict(owns=("gm_iters", "gm_nu"), ids=True, count=None,
+                             run="_geometric_median"),
+    "centered_clip": dict(owns=("cc_tau", "cc_iters"), ids=True, count=None, run="_centered_clip"),
+    "mean_around_median": dict(owns=("byzantine",), ids=False, run="_mean_around_median", count=(
+        lambda K, p: 2 * p["byzantine"] < K,
+        "byzantine={byzantine} leaves no majority of {clients} (2*byzantine < {n} is needed)")),
+    "bulyan": dict(owns=("byzantine",), ids=True, run="_bulyan", count=(
+        lambda K, p: 4 * p["byzantine"] + 3 <= K,
+        "byzantine={byzantine} is too many for {group} (4*byzantine + 3 <= {n} is needed)")),
+    "foolsgold": dict(owns=("fg_kappa",), ids=True, count=None, run="_foolsgold"),
+}
+
+
+def _count_error(rule, K, p, subset):
+    """The message for K clients that robust ``rule`` with the parameters ``p`` cannot
+    take, or None; K is the constructor's worker_number, or a subset's length."""
+    if K > _native.ROBUST_MAX_K:
+        return (f"aggregation_rule={rule!r} takes at most ROBUST_MAX_K={_native.ROBUST_MAX_K} "
+                f"clients, not {K if subset else f'worker_number={K}'}")
+    group = f"a subset of {K} clients" if subset else f"worker_number={K}"
+    for fits, text in filter(None, (_TRIM_FITS, RULES[rule]["count"])):
+        if not fits(K, p):
+            return text.format(group=group, clients=group if subset else group + " clients",
+                               n="len(subset)" if subset else "worker_number",
+                               trim=p["trim"], byzantine=p["byzantine"])
+    return None
 
 
 class FedServer(Server):
@@ -118,14 +164,19 @@ class FedServer(Server):
     # why a subclass cannot run the Byzantine client attacks (None: it can)
     _attack_unsupported = None
 
-    def __init__(self, aggregation_mode="exact", aggregation_rule="mean", trim=0, byzantine=0,
-                 krum_select=None, gm_iters=_GM_ITERS, gm_nu=_GM_NU, cc_tau=_CC_TAU,
-                 cc_iters=_CC_ITERS, attack=None, attackers=(), attack_z=None,
-                 attack_eps=_ATTACK_EPS, attack_scale=_ATTACK_SCALE, fg_kappa=_FG_KAPPA, **kwargs):
+    def __init__(self, aggregation_mode="exact", aggregation_rule="mean",
+                 trim=DEFAULTS["trim"], byzantine=DEFAULTS["byzantine"],
+                 krum_select=DEFAULTS["krum_select"], gm_iters=DEFAULTS["gm_iters"],
+                 gm_nu=DEFAULTS["gm_nu"], cc_tau=DEFAULTS["cc_tau"], cc_iters=DEFAULTS["cc_iters"],
+                 attack=None, attackers=(), attack_z=ATTACK_DEFAULTS["attack_z"],
+                 attack_eps=ATTACK_DEFAULTS["attack_eps"],
+                 attack_scale=ATTACK_DEFAULTS["attack_scale"], fg_kappa=DEFAULTS["fg_kappa"],
+                 **kwargs):
         if aggregation_mode not in _MODES:
             raise ValueError(f"aggregation_mode must be one of {sorted(_MODES)}, not {aggregation_mode!r}")
-        self._check_rule(aggregation_rule, trim, aggregation_mode, kwargs.get("worker_number"),
-                         byzantine, krum_select, gm_iters, gm_nu, cc_tau, cc_iters,
+        self._check_rule(aggregation_rule, aggregation_mode, kwargs.get("worker_number"),
+                         trim=trim, byzantine=byzantine, krum_select=krum_select,
+                         gm_iters=gm_iters, gm_nu=gm_nu, cc_iters=cc_iters, cc_tau=cc_tau,
                          fg_kappa=fg_kappa)
         attackers = self._check_attack(attack, attackers, attack_z, attack_eps, attack_scale,
                                        kwargs.get("worker_number"))
@@ -163,46 +214,27 @@ class FedServer(Server):
             RepeatedResult(data=self.prev_model, num=self.clients_per_round))
 
     @classmethod
-    def _check_rule(cls, rule, trim, mode, worker_number, byzantine=0, krum_select=None,
-                    gm_iters=_GM_ITERS, gm_nu=_GM_NU, cc_tau=_CC_TAU, cc_iters=_CC_ITERS,
-                    fg_kappa=_FG_KAPPA):
-        if rule not in _RULES:
-            raise ValueError(f"aggregation_rule must be one of {list(_RULES)}, not {rule!r}")
-        if isinstance(trim, bool) or not isinstance(trim, int) or trim < 0:
-            raise ValueError(f"trim must be a non-negative integer, not {trim!r}")
-        if rule != "trimmed_mean" and trim != 0:
-            raise ValueError(f"trim={trim} needs aggregation_rule='trimmed_mean', not {rule!r}")
-        if isinstance(byzantine, bool) or not isinstance(byzantine, int) or byzantine < 0:
-            raise ValueError(f"byzantine must be a non-negative integer, not {byzantine!r}")
-        if krum_select is not None and (isinstance(krum_select, bool)
-                                        or not isinstance(krum_select, int)):
-            raise ValueError(f"krum_select must be an integer or None, not {krum_select!r}")
-        if (rule not in _BYZANTINE_RULES and byzantine != 0) or (rule != "multi_krum"
-                                                                  and krum_select is not None):
-            raise ValueError(f"byzantine={byzantine} / krum_select={krum_select} needs "
-                             f"aggregation_rule='multi_krum', not {rule!r}")
-        if isinstance(gm_iters, bool) or not isinstance(gm_iters, int) or gm_iters < 1:
-            raise ValueError(f"gm_iters must be a positive integer, not {gm_iters!r}")
-        if (isinstance(gm_nu, bool) or not isinstance(gm_nu, (int, float))
-                or not math.isfinite(gm_nu) or gm_nu <= 0):
-            raise ValueError(f"gm_nu must be a positive finite number, not {gm_nu!r}")
-        if rule != "geometric_median" and (gm_iters != _GM_ITERS or gm_nu != _GM_NU):
-            raise ValueError(f"gm_iters={gm_iters} / gm_nu={gm_nu} needs "
-                             f"aggregation_rule='geometric_median', not {rule!r}")
-        if isinstance(cc_iters, bool) or not isinstance(cc_iters, int) or cc_iters < 1:
-            raise ValueError(f"cc_iters must be a positive integer, not {cc_iters!r}")
-        if (isinstance(cc_tau, bool) or not isinstance(cc_tau, (int, float))
-                or not math.isfinite(cc_tau) or cc_tau <= 0):
-            raise ValueError(f"cc_tau must be a positive finite number, not {cc_tau!r}")
-        if rule != "centered_clip" and (cc_tau != _CC_TAU or cc_iters != _CC_ITERS):
-            raise ValueError(f"cc_tau={cc_tau} / cc_iters={cc_iters} needs "
-                             f"aggregation_rule='centered_clip', not {rule!r}")
-        if (isinstance(fg_kappa, bool) or not isinstance(fg_kappa, (int, float))
-                or not math.isfinite(fg_kappa) or fg_kappa <= 0):
-            raise ValueError(f"fg_kappa must be a positive finite number, not {fg_kappa!r}")
-        if rule != "foolsgold" and fg_kappa != _FG_KAPPA:
-            raise ValueError(f"fg_kappa={fg_kappa} needs aggregation_rule='foolsgold', not "
-                             f"{rule!r}")
+    def _check_rule(cls, rule, mode, worker_number, **parameters):
+        """ValueError for a rule, or rule parameters (keywords of ``DEFAULTS``, the rest
+        at their defaults), that no round could run."""
+        if rule not in RULES:
+            raise ValueError(f"aggregation_rule must be one of {list(RULES)}, not {rule!r}")
+        p = {**DEFAULTS, **parameters}
+        for names, owner in _GROUPS:
+            for name in (n for n in DEFAULTS if n in names):
+                v = p[name]
+                if name in _AT_LEAST:
+                    if isinstance(v, bool) or not isinstance(v, int) or v < _AT_LEAST[name]:
+                        raise ValueError(f"{name} must be a "
+                                         f"{'positive' if _AT_LEAST[name] else 'non-negative'} "
+                                         f"integer, not {v!r}")
+                elif name != "krum_select":
+                    finite_number(name, v, positive=True)
+                elif v is not None and (isinstance(v, bool) or not isinstance(v, int)):
+                    raise ValueError(f"krum_select must be an integer or None, not {v!r}")
+            if any(p[n] != DEFAULTS[n] and n not in RULES[rule]["owns"] for n in names):
+                raise ValueError(" / ".join(f"{n}={p[n]}" for n in names)
+                                 + f" needs aggregation_rule={owner!r}, not {rule!r}")
         if rule == "mean":
             return
         if cls._robust_unsupported is not None:
@@ -215,32 +247,22 @@ class FedServer(Server):
             raise ValueError(f"aggregation_mode={mode!r} applies to aggregation_rule='mean' only; "
                              f"{rule!r} has one arithmetic")
         if worker_number is not None:
-            if worker_number > _native.ROBUST_MAX_K:
-                raise ValueError(f"aggregation_rule={rule!r} takes at most ROBUST_MAX_K="
-                                 f"{_native.ROBUST_MAX_K} clients, not worker_number={worker_number}")
-            if 2 * trim >= worker_number:
-                raise ValueError(f"trim={trim} leaves nothing of worker_number={worker_number} "
-                                 "clients (2*trim < worker_number is needed)")
-            if rule == "multi_krum":
-                if 2 * byzantine + 3 > worker_number:
-                    raise ValueError(f"byzantine={byzantine} is too many for worker_number="
-                                     f"{worker_number} (2*byzantine + 3 <= worker_number is needed)")
-                if krum_select is not None and not 1 <= krum_select <= worker_number - byzantine:
-                    raise ValueError(f"krum_select={krum_select} must be in 1..worker_number - "
-                                     f"byzantine = {worker_number - byzantine}")
-            if rule == "mean_around_median" and 2 * byzantine >= worker_number:
-                raise ValueError(f"byzantine={byzantine} leaves no majority of worker_number="
-                                 f"{worker_number} clients (2*byzantine < worker_number is "
-                                 "needed)")
-            if rule == "bulyan" and 4 * byzantine + 3 > worker_number:
-                raise ValueError(f"byzantine={byzantine} is too many for worker_number="
-                                 f"{worker_number} (4*byzantine + 3 <= worker_number is needed)")
-        elif rule == "multi_krum" and krum_select is not None and krum_select < 1:
-            raise ValueError(f"krum_select={krum_select} must be at least 1")
+            error = _count_error(rule, worker_number, p, subset=False)
+            if error:
+                raise ValueError(error)
+        select = p["krum_select"]
+        if rule == "multi_krum" and select is not None:
+            if worker_number is None:
+                if select < 1:
+                    raise ValueError(f"krum_select={select} must be at least 1")
+            elif not 1 <= select <= worker_number - p["byzantine"]:
+                raise ValueError(f"krum_select={select} must be in 1..worker_number - "
+                                 f"byzantine = {worker_number - p['byzantine']}")
 
     @classmethod
-    def _check_attack(cls, attack, attackers, attack_z=None, attack_eps=_ATTACK_EPS,
-                      attack_scale=_ATTACK_SCALE, worker_number=None):
+    def _check_attack(cls, attack, attackers, attack_z=ATTACK_DEFAULTS["attack_z"],
+                      attack_eps=ATTACK_DEFAULTS["attack_eps"],
+                      attack_scale=ATTACK_DEFAULTS["attack_scale"], worker_number=None):
         """The sorted tuple of attacker ids; ValueError for what no round could run."""
         if attack is not None and attack not in ATTACKS:
             raise ValueError(f"attack must be None or one of {list(ATTACKS)}, not {attack!r}")
@@ -252,20 +274,15 @@ class FedServer(Server):
             raise ValueError(f"attackers must be non-negative integer worker ids, not {ids!r}")
         if len(set(ids)) != len(ids):
             raise ValueError(f"attackers must be distinct worker ids, not {ids!r}")
-        for name, v in (("attack_z", attack_z), ("attack_eps", attack_eps),
-                        ("attack_scale", attack_scale)):
-            if v is not None and (isinstance(v, bool) or not isinstance(v, (int, float))
-                                  or not math.isfinite(v)):
-                raise ValueError(f"{name} must be a finite number, not {v!r}")
+        given = {"attack_z": attack_z, "attack_eps": attack_eps, "attack_scale": attack_scale}
+        for name, v in given.items():
+            if v is not None:
+                finite_number(name, v)
         if attack is None and ids:
             raise ValueError(f"attackers={ids} needs an attack, one of {list(ATTACKS)}")
-        if attack != "alie" and attack_z is not None:
-            raise ValueError(f"attack_z={attack_z} needs attack='alie', not {attack!r}")
-        if attack != "ipm" and attack_eps != _ATTACK_EPS:
-            raise ValueError(f"attack_eps={attack_eps} needs attack='ipm', not {attack!r}")
-        if attack != "sign_flip" and attack_scale != _ATTACK_SCALE:
-            raise ValueError(f"attack_scale={attack_scale} needs attack='sign_flip', not "
-                             f"{attack!r}")
+        for name, v in given.items():
+            if attack != _ATTACK_OF[name] and v != ATTACK_DEFAULTS[name]:
+                raise ValueError(f"{name}={v} needs attack={_ATTACK_OF[name]!r}, not {attack!r}")
         if attack is None:
             return ()
         if cls._attack_unsupported is not None:
@@ -331,6 +348,14 @@ class FedServer(Server):
     def _set_prev_model(self, model):
         self.__prev_model = model
 
+    def _prev_flat(self, store):
+        """The previous global model as a flat vector on the store's device, or None while
+        there is none the store accepts (round 1 of a server without a tester)."""
+        prev = self.__prev_model
+        if prev and store.accepts(prev):
+            return store.layout.flatten(prev, device=store.U.device)
+        return None
+
     def _process_client_parameter(self, client_parameter: dict):
         return client_parameter
 
@@ -346,12 +371,9 @@ class FedServer(Server):
             return self.__prev_model
         ids = list(client_subset)
         store = self.parameters.store
-        # multi-Krum, Bulyan, the geometric median, centered clipping and FoolsGold report,
-        # break ties and order by worker id (no subclass that overrides _aggregate runs
-        # those rules)
-        extra = {"ids": ids} if self.aggregation_rule in ("multi_krum", "geometric_median",
-                                                          "centered_clip", "bulyan",
-                                                          "foolsgold") else {}
+        # the rules that report, break ties and order by worker id are handed the ids (no
+        # subclass that overrides _aggregate runs those rules)
+        extra = {"ids": ids} if RULES[self.aggregation_rule]["ids"] else {}
         flat = self._aggregate(store, [self.parameters.row_of(i) for i in ids],
                                [self.parameters.n_of(i) for i in ids], **extra)
         return store.layout.views(flat)
@@ -360,36 +382,23 @@ class FedServer(Server):
         if self.aggregation_rule == "mean":
             return store.fedavg(rows, ns, mode=_MODES[self.aggregation_mode], total=total)
         K = len(rows)
-        if K > _native.ROBUST_MAX_K:
-            raise ValueError(f"aggregation_rule={self.aggregation_rule!r} takes at most "
-                             f"ROBUST_MAX_K={_native.ROBUST_MAX_K} clients, not {K}")
-        if self.aggregation_rule == "median":
-            return store.median(rows)
-        if self.aggregation_rule == "multi_krum":
-            return self._multi_krum(store, rows, list(range(K)) if ids is None else ids)
-        if self.aggregation_rule == "geometric_median":
-            return self._geometric_median(store, rows, list(range(K)) if ids is None else ids)
-        if self.aggregation_rule == "centered_clip":
-            return self._centered_clip(store, rows, list(range(K)) if ids is None else ids)
-        if self.aggregation_rule == "bulyan":
-            return self._bulyan(store, rows, list(range(K)) if ids is None else ids)
-        if self.aggregation_rule == "foolsgold":
-            return self._foolsgold(store, rows, list(range(K)) if ids is None else ids)
-        if self.aggregation_rule == "mean_around_median":
-            if 2 * self.byzantine >= K:
-                raise ValueError(f"byzantine={self.byzantine} leaves no majority of a subset of "
-                                 f"{K} clients (2*byzantine < len(subset) is needed)")
-            return store.mean_around_median(rows, K - self.byzantine)
-        if 2 * self.trim >= K:
-            raise ValueError(f"trim={self.trim} leaves nothing of a subset of {K} clients "
-                             "(2*trim < len(subset) is needed)")
+        error = _count_error(self.aggregation_rule, K, vars(self), subset=True)
+        if error:
+            raise ValueError(error)
+        run = getattr(self, RULES[self.aggregation_rule]["run"])
+        return run(store, rows, list(range(K)) if ids is None else ids)
+
+    def _median(self, store, rows, ids):
+        return store.median(rows)
+
+    def _trimmed_mean(self, store, rows, ids):
         return store.trimmed_mean(rows, self.trim)
+
+    def _mean_around_median(self, store, rows, ids):
+        return store.mean_around_median(rows, len(rows) - self.byzantine)
 
     def _multi_krum(self, store, rows, ids):
         K, f = len(rows), self.byzantine
-        if 2 * f + 3 > K:
-            raise ValueError(f"byzantine={f} is too many for a subset of {K} clients "
-                             "(2*byzantine + 3 <= len(subset) is needed)")
         select = K - f if self.krum_select is None else self.krum_select
         if select > K - f:
             raise ValueError(f"krum_select={select} exceeds len(subset) - byzantine = {K - f}")
@@ -403,9 +412,6 @@ class FedServer(Server):
 
     def _bulyan(self, store, rows, ids):
         K, f = len(rows), self.byzantine
-        if 4 * f + 3 > K:
-            raise ValueError(f"byzantine={f} is too many for a subset of {K} clients "
-                             "(4*byzantine + 3 <= len(subset) is needed)")
         flat, selected, scores = store.bulyan(rows, ids, f)
         self.last_selection = tuple(selected)
         self.last_scores = scores
@@ -426,10 +432,8 @@ class FedServer(Server):
     def _centered_clip(self, store, rows, ids):
         # from the model the clients started from; the coordinate-wise median of the
         # subset while there is none (round 1 of a server without a tester)
-        prev = self.__prev_model
-        if prev and store.accepts(prev):
-            start = store.layout.flatten(prev, device=store.U.device)
-        else:
+        start = self._prev_flat(store)
+        if start is None:
             start = store.median(rows)
         flat, info = store.centered_clip(rows, ids, start, self.cc_tau, self.cc_iters)
         self.last_distances = info["distances"]
@@ -455,12 +459,10 @@ class FedServer(Server):
             raise ValueError("aggregation_rule='foolsgold' keeps one history row per worker id: "
                              f"the ids must be non-negative integers, not {ids!r}")
         rows = [self.parameters.row_of(w) for w in ids]
-        # updates are taken from the model the clients started from, flattened as
-        # _centered_clip does it; from the round's coordinate-wise median while there is none
-        prev = self.__prev_model
-        if prev and store.accepts(prev):
-            base = store.layout.flatten(prev, device=store.U.device)
-        else:
+        # updates are taken from the model the clients started from; from the round's
+        # coordinate-wise median while there is none
+        base = self._prev_flat(store)
+        if base is None:
             base = store.median(rows)
             log.info("foolsgold: no previous model in round %s, updates are taken from the "
                      "coordinate-wise median of the round's %s rows", self.round, len(rows))
@@ -504,12 +506,8 @@ class FedServer(Server):
             raise ValueError(f"attack={self.attack!r}: attackers "
                              f"{[w for w in self.attackers if w not in self.parameters]} sent no "
                              "update this round")
-        # relative to the model the clients started from, flattened as _centered_clip
-        # does it; while there is none (round 1 of a server without a tester), to zero
-        prev = self.__prev_model
-        base = None
-        if self.attack != "alie" and prev and store.accepts(prev):
-            base = store.layout.flatten(prev, device=store.U.device)
+        # relative to the model the clients started from; while there is none, to zero
+        base = None if self.attack == "alie" else self._prev_flat(store)
         info = {"attack": self.attack, "attackers": self.attackers}
         if self.attack == "sign_flip":
             store.sign_flip([self.parameters.row_of(w) for w in bad], self.attack_scale,

@@ -29,8 +29,10 @@ import threading
 
 import torch
 
+from .aggregation import ATTACKS
 from .factory import get_server, get_worker
 from .models import MODELS, synthetic_classification
+from .servers.fed_server import ATTACK_DEFAULTS, DEFAULTS, RULES
 from .trainer import Inferencer, Trainer
 
 DATASETS = {"MNIST": (1, 32, 32), "CIFAR10": (3, 32, 32)}
@@ -79,37 +81,28 @@ def get_config(argv=None):
     # but 2 x --byzantine updates by iterated Krum and then averages per coordinate the
     # chosen values closest to their median, all but another 2 x --byzantine (it needs
     # 4 x --byzantine + 3 clients).  The robust rules ignore the clients' sample counts.
-    ap.add_argument("--aggregation_rule", type=str, default="mean",
-                    choices=("mean", "median", "trimmed_mean", "multi_krum",
-                             "geometric_median", "centered_clip", "mean_around_median",
-                             "bulyan", "foolsgold"))
-    ap.add_argument("--trim", type=int, default=0)
-    ap.add_argument("--byzantine", type=int, default=0)
-    ap.add_argument("--krum_select", type=int, default=None)
+    ap.add_argument("--aggregation_rule", type=str, default="mean", choices=tuple(RULES))
     # geometric_median: --gm_iters smoothed Weiszfeld steps from the coordinate-wise
     # median, smoothing --gm_nu in the units of the parameters (RFA's defaults)
-    ap.add_argument("--gm_iters", type=int, default=3)
-    ap.add_argument("--gm_nu", type=float, default=1e-6)
     # centered_clip: --cc_iters clipped steps from the previous global model, each
     # client's difference to the aggregate shortened to at most --cc_tau (in the units
     # of the parameters); --cc_iters 1 is norm clipping
-    ap.add_argument("--cc_tau", type=float, default=10.0)
-    ap.add_argument("--cc_iters", type=int, default=3)
     # foolsgold: clients whose accumulated updates keep pointing the same way (sybils,
     # e.g. --attack alie --attackers 3,7) are down-weighted; --fg_kappa is the paper's
     # confidence parameter (larger pushes the weights towards 0 and 1)
-    ap.add_argument("--fg_kappa", type=float, default=1.0)
+    for name, default in DEFAULTS.items():  # the counts are integers, the rest real numbers
+        ap.add_argument("--" + name, type=float if isinstance(default, float) else int,
+                        default=default)
     # Byzantine clients: the workers listed in --attackers (comma-separated ids) have
     # their update of every round rewritten on the server before anything reads it:
     # "alie" (a little is enough) sends mean - z * std of the honest updates per
     # coordinate, z = --attack_z (default: from the worker and attacker counts), "ipm"
     # (inner product manipulation) -(--attack_eps) times the honest mean update,
     # "sign_flip" the attacker's own update mirrored and scaled by --attack_scale
-    ap.add_argument("--attack", type=str, default=None, choices=("alie", "ipm", "sign_flip"))
+    ap.add_argument("--attack", type=str, default=None, choices=ATTACKS)
     ap.add_argument("--attackers", type=_worker_ids, default=())
-    ap.add_argument("--attack_z", type=float, default=None)
-    ap.add_argument("--attack_eps", type=float, default=0.1)
-    ap.add_argument("--attack_scale", type=float, default=1.0)
+    for name, default in ATTACK_DEFAULTS.items():
+        ap.add_argument("--" + name, type=float, default=default)
     config = ap.parse_args(argv)
     if config.distributed_algorithm == "sign_SGD" and config.aggregation_rule != "mean":
         ap.error("--aggregation_rule applies to the FedAvg-based servers; sign_SGD votes")
@@ -145,26 +138,13 @@ def server_kwargs(config):
         kwargs["utility_metric"] = getattr(config, "utility_metric", "acc")
     if getattr(config, "aggregation_rule", "mean") != "mean":
         kwargs["aggregation_rule"] = config.aggregation_rule
-        kwargs["trim"] = getattr(config, "trim", 0)
-        if config.aggregation_rule == "multi_krum":
-            kwargs["byzantine"] = getattr(config, "byzantine", 0)
-            kwargs["krum_select"] = getattr(config, "krum_select", None)
-        if config.aggregation_rule in ("bulyan", "mean_around_median"):
-            kwargs["byzantine"] = getattr(config, "byzantine", 0)
-        if config.aggregation_rule == "geometric_median":
-            kwargs["gm_iters"] = getattr(config, "gm_iters", 3)
-            kwargs["gm_nu"] = getattr(config, "gm_nu", 1e-6)
-        if config.aggregation_rule == "centered_clip":
-            kwargs["cc_tau"] = getattr(config, "cc_tau", 10.0)
-            kwargs["cc_iters"] = getattr(config, "cc_iters", 3)
-        if config.aggregation_rule == "foolsgold":
-            kwargs["fg_kappa"] = getattr(config, "fg_kappa", 1.0)
+        for name in ("trim",) + RULES[config.aggregation_rule]["owns"]:
+            kwargs[name] = getattr(config, name, DEFAULTS[name])
     if getattr(config, "attack", None) is not None:
         kwargs["attack"] = config.attack
         kwargs["attackers"] = tuple(getattr(config, "attackers", ()))
-        kwargs["attack_z"] = getattr(config, "attack_z", None)
-        kwargs["attack_eps"] = getattr(config, "attack_eps", 0.1)
-        kwargs["attack_scale"] = getattr(config, "attack_scale", 1.0)
+        for name, default in ATTACK_DEFAULTS.items():
+            kwargs[name] = getattr(config, name, default)
     return kwargs
 
 

@@ -1,0 +1,354 @@
+"""Characterization of the robust-aggregation host path, CPU only: what every rejected
+call raises (type and message, byte for byte) and what the accepted ones return, in
+the order the checks fire, recorded in ``tests/golden/robust_messages.json``.
+
+The inputs are enumerated in a fixed order, section by section, and each outcome,
+``"ok"``, a repr of what came back or ``"<ExceptionType>: <message>"``, is compared
+with the recorded string (the fixture lists each distinct string once and, per input,
+its index).  A recorded string never changes: a difference is a change of behaviour.  ``python -m tests.test_robust_messages_host`` rewrites the fixture (to add
+inputs); to see that a change of the package kept every message, run this file against
+the fixture with the package directory of the parent commit in place of the new one.
+
+Servers are constructed on the CPU doubles (``cpu_doubles.install``); ``_native.lib`` is
+a stub, so no case needs the library: a well-formed wrapper call ends in "not on the
+GPU" before anything reaches it.
+"""
+import hashlib
+import itertools
+import json
+import os
+import textwrap
+
+import pytest
+import torch
+
+from tests import cpu_doubles
+
+CPU = torch.device("cpu")
+FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden",
+                       "robust_messages.json")
+NAN, INF = float("nan"), float("inf")
+
+RULES = ("mean", "median", "trimmed_mean", "multi_krum", "geometric_median", "centered_clip",
+         "mean_around_median", "bulyan", "foolsgold")
+ATTACKS = ("alie", "ipm", "sign_flip")
+WORKER_NUMBERS = (None, 2, 3, 7, 10, 64, 65)
+MODES = ("exact", "fma")
+ONE_SET = (("trim", 1), ("byzantine", 1), ("byzantine", 2), ("krum_select", 1), ("gm_iters", 2),
+           ("gm_nu", 1e-3), ("cc_tau", 1.0), ("cc_iters", 2), ("fg_kappa", 2.0))
+OWNERS = {"trim": ("trimmed_mean",), "byzantine": ("multi_krum", "bulyan", "mean_around_median"),
+          "krum_select": ("multi_krum",), "gm_iters": ("geometric_median",),
+          "gm_nu": ("geometric_median",), "cc_tau": ("centered_clip",),
+          "cc_iters": ("centered_clip",), "fg_kappa": ("foolsgold",),
+          "attack_z": ("alie",), "attack_eps": ("ipm",), "attack_scale": ("sign_flip",)}
+BAD_VALUES = (True, -1, 0, 1.5, "1", NAN, INF)
+LAST = ("last_selection", "last_scores", "last_distances", "last_rejected", "last_clip_scales",
+        "last_weights", "last_similarity")
+
+
+class _StubLibrary:
+    """Stands in for the loaded library: nothing recorded here reaches an entry point."""
+
+    def __getattr__(self, name):
+        def entry(*args):
+            raise AssertionError(f"{name} reached the library stub")
+        return entry
+
+
+def _outcome(call):
+    try:
+        result = call()
+    except Exception as e:  # the type and the text are what is recorded
+        return f"{type(e).__name__}: {e}"
+    return "ok" if result is None else result
+
+
+def _kw(kw):
+    return ",".join(f"{k}={v!r}" for k, v in kw.items())
+
+
+def _construct(make, **kw):
+    def call():
+        make(**kw).stop()
+    return _outcome(call)
+
+
+def _fed(**kw):
+    from distributed_learning_simulator_amd.servers.fed_server import FedServer
+    return FedServer(tester=None, device=CPU, synchronous=True, **kw)
+
+
+# ---------------------------------------------------------------- the constructor
+def constructor_grid():
+    for rule, wn, mode in itertools.product(RULES, WORKER_NUMBERS, MODES):
+        for extra in ((),) + tuple((p,) for p in ONE_SET):
+            kw = dict(aggregation_rule=rule, worker_number=wn, aggregation_mode=mode, **dict(extra))
+            yield _kw(kw), _construct(_fed, **kw)
+
+
+def constructor_values():
+    for name, owners in OWNERS.items():
+        for owner, value in itertools.product(owners, BAD_VALUES):
+            if name.startswith("attack"):
+                kw = dict(worker_number=10, attack=owner, attackers=(1,), **{name: value})
+            else:
+                kw = dict(worker_number=10, aggregation_rule=owner, **{name: value})
+            yield _kw(kw), _construct(_fed, **kw)
+
+
+def constructor_pairs():
+    for wn, select in itertools.product((10, None), (0, 1, 8, 9)):
+        kw = dict(aggregation_rule="multi_krum", byzantine=2, krum_select=select, worker_number=wn)
+        yield _kw(kw), _construct(_fed, **kw)
+    for wn in (6, 7):
+        kw = dict(aggregation_rule="bulyan", byzantine=1, worker_number=wn)
+        yield _kw(kw), _construct(_fed, **kw)
+    kw = dict(aggregation_rule="mean_around_median", byzantine=5, worker_number=10)
+    yield _kw(kw), _construct(_fed, **kw)
+    for rule, wn in itertools.product(RULES, (0, -1)):  # no client at all
+        kw = dict(aggregation_rule=rule, worker_number=wn)
+        yield _kw(kw), _construct(_fed, **kw)
+
+
+def constructor_attacks():
+    foreign = ((), ("attack_z", 1.0), ("attack_eps", 0.2), ("attack_scale", 2.0))
+    attackers = ((), (1,), (1, 1), (9,), (10,), (-1,), (True,), 5)
+    for attack, ids, extra, wn in itertools.product((None,) + ATTACKS, attackers, foreign,
+                                                    (10, None)):
+        kw = dict(attack=attack, attackers=ids, worker_number=wn, **dict((extra,) if extra else ()))
+        yield _kw(kw), _construct(_fed, **kw)
+
+
+def subclasses():
+    from distributed_learning_simulator_amd import factory
+    combos = [(a, False) for a in ("fed_quant", "GTG_shapley_value", "multiround_shapley_value")]
+    combos += [(a, True) for a in ("fed", "fed_quant", "GTG_shapley_value",
+                                   "multiround_shapley_value")]
+    for (algo, sharded), kw in itertools.product(combos, (
+            dict(aggregation_rule="median"), dict(byzantine=1),
+            dict(attack="alie", attackers=(1,)))):
+        def make(**kw):
+            return factory.get_server(algo, sharded=sharded, tester=None, worker_number=5,
+                                      synchronous=True, device=CPU, **kw)
+        yield f"{algo},sharded={sharded},{_kw(kw)}", _construct(make, **kw)
+
+
+# ---------------------------------------------------------------- get_subset_model
+def subset_models():
+    configs = [dict(aggregation_rule=r) for r in RULES]
+    for kw in configs:
+        kw.update({"trimmed_mean": dict(trim=2), "multi_krum": dict(byzantine=2),
+                   "bulyan": dict(byzantine=1),
+                   "mean_around_median": dict(byzantine=2)}.get(kw["aggregation_rule"], {}))
+    configs.append(dict(aggregation_rule="multi_krum", byzantine=1, krum_select=9))
+    for kw in configs:
+        s = _fed(worker_number=10, **kw)
+        for w in range(10):
+            s.parameters[w] = (w + 1, {"w": torch.arange(16.0).reshape(4, 4) * (w - 4.5)})
+        for subset in ([0], [0, 1], list(range(6)), list(range(10))):
+            def call():
+                model = s.get_subset_model(subset)
+                return repr(({k: v.tolist() for k, v in model.items()},
+                             {a: getattr(s, a) for a in LAST}))
+            yield f"{_kw(kw)},subset={subset}", _outcome(call)
+        s.stop()
+
+
+# ---------------------------------------------------------------- the _native wrappers
+K0 = 3  # clients of a well-formed call; matrices are [8, 16], P = 8
+
+
+def _strided(flat, defects):
+    """``flat`` (a new 1-D tensor of twice the length + 1) cut to what the defects ask."""
+    off = 1 if "misaligned" in defects else 0
+    n = (flat.numel() - 1) // 2
+    return flat[off:off + 2 * n:2] if "stride" in defects else flat[off:off + n]
+
+
+def _matrix(defects):
+    width = 32 if "stride" in defects else 16
+    pitch = width + (2 if "pitch" in defects else 0)
+    off = 1 if "misaligned" in defects else 0
+    buf = torch.zeros(8 * pitch + off,
+                      dtype=torch.float64 if "dtype" in defects else torch.float32)
+    t = buf[off:].view(8, pitch)[:, :width]
+    t = t[:, ::2] if "stride" in defects else t
+    return t[None] if "rank" in defects else t
+
+
+def _table(defects):
+    K = 0 if "K0" in defects else 65 if "K65" in defects else K0
+    values = [k % 8 for k in range(K)]
+    if "range" in defects:
+        values[-1] = 99
+    if "dup" in defects:
+        values[0] = values[1]
+    t = torch.zeros(2 * K + 1, dtype=torch.int64 if "dtype" in defects else torch.int32)
+    t = _strided(t, defects)
+    t.copy_(torch.tensor(values, dtype=t.dtype))
+    return t[None] if "rank" in defects else t
+
+
+def _vector(n, dtype, wrong):
+    def make(defects):
+        m = 4 if "short" in defects else n + 1 if "shape" in defects else n
+        t = _strided(torch.zeros(2 * m + 1, dtype=wrong if "dtype" in defects else dtype), defects)
+        return t[None] if "rank" in defects else t
+    return make
+
+
+def _square(defects):
+    cols = K0 + 1 if "shape" in defects else K0
+    t = _strided(torch.zeros(2 * K0 * cols + 1,
+                             dtype=torch.float32 if "dtype" in defects else torch.float64), defects)
+    t = t.view(K0, cols) if t.is_contiguous() else t.unflatten(0, (K0, cols))
+    return t[None] if "rank" in defects else t
+
+
+MATRIX = (_matrix, ("dtype", "rank", "stride", "pitch", "misaligned"))
+TABLE = (_table, ("dtype", "rank", "stride", "misaligned", "K0", "K65", "range", "dup"))
+F32VEC = (_vector(16, torch.float32, torch.float64),
+          ("dtype", "rank", "stride", "misaligned", "short"))
+KVEC32 = (_vector(K0, torch.float32, torch.float64),
+          ("dtype", "rank", "stride", "misaligned", "shape"))
+KVEC64 = (_vector(K0, torch.float64, torch.float32),
+          ("dtype", "rank", "stride", "misaligned", "shape"))
+SQUARE = (_square, ("dtype", "rank", "stride", "misaligned", "shape"))
+EXCLUSIVE = ({"K0", "K65"}, {"K0", "range"}, {"K0", "dup"}, {"range", "dup"}, {"short", "shape"})
+
+# the scalar arguments: (the well-formed value, the values no call accepts)
+SCALARS = {"trim": (1, (-1, 2)), "keep": (2, (0, 4)), "a": (1.0, (NAN,))}
+
+# wrapper -> (its tensor operands in call order, the call on the built operands o and P)
+WRAPPERS = {
+    "trimmed_mean": ({"U": MATRIX, "rows": TABLE, "out": F32VEC},
+                     lambda n, o, P: n.trimmed_mean(o["U"], o["rows"], o["trim"], P, o["out"])),
+    "mean_around_median": ({"U": MATRIX, "rows": TABLE, "out": F32VEC},
+                           lambda n, o, P: n.mean_around_median(o["U"], o["rows"], o["keep"], P,
+                                                                o["out"])),
+    "pairwise_sqdist": ({"U": MATRIX, "rows": TABLE, "out": SQUARE},
+                        lambda n, o, P: n.pairwise_sqdist(o["U"], o["rows"], P, out=o["out"])),
+    "rows_gram": ({"U": MATRIX, "rows": TABLE, "base": F32VEC, "out": SQUARE},
+                  lambda n, o, P: n.rows_gram(o["U"], o["rows"], P, base=o["base"], out=o["out"])),
+    "history_gram": ({"U": MATRIX, "rows": TABLE, "H": MATRIX, "hrows": TABLE, "base": F32VEC,
+                      "out": SQUARE},
+                     lambda n, o, P: n.history_gram(o["U"], o["rows"], o["H"], o["hrows"], P,
+                                                    base=o["base"], out=o["out"])),
+    "craft_rows": ({"U": MATRIX, "hrows": TABLE, "arows": TABLE, "base": F32VEC},
+                   lambda n, o, P: n.craft_rows(o["U"], o["hrows"], o["arows"], o["a"], -0.5, P,
+                                                base=o["base"])),
+    "rows_sqdist_to": ({"U": MATRIX, "rows": TABLE, "z": F32VEC, "out": KVEC64},
+                       lambda n, o, P: n.rows_sqdist_to(o["U"], o["rows"], P, o["z"], out=o["out"])),
+    "weiszfeld_step": ({"U": MATRIX, "rows": TABLE, "w": KVEC32, "z": F32VEC, "dist2": KVEC64},
+                       lambda n, o, P: n.weiszfeld_step(o["U"], o["rows"], o["w"], P, o["z"],
+                                                        dist2=o["dist2"])),
+    "centered_clip_step": ({"U": MATRIX, "rows": TABLE, "c": KVEC32, "z": F32VEC, "dist2": KVEC64},
+                           lambda n, o, P: n.centered_clip_step(o["U"], o["rows"], o["c"], P,
+                                                                o["z"], dist2=o["dist2"])),
+}
+OPTIONAL = ("base", "out", "dist2")  # the defaults (None) are a base case of their own
+
+
+def _wrapper_cases(name):
+    from distributed_learning_simulator_amd import _native
+    operands, call = WRAPPERS[name]
+    defects = [(op, kind) for op, (_, kinds) in operands.items() for kind in kinds]
+    defects += [("P", p) for p in (-4, 0, 2, 20)]
+    if "H" in operands:
+        defects.append(("H", "overlap"))
+    scalar = {"trimmed_mean": "trim", "mean_around_median": "keep", "craft_rows": "a"}.get(name)
+    if scalar:
+        defects += [(scalar, v) for v in SCALARS[scalar][1]]
+    singles = [()] + [(d,) for d in defects]
+    pairs = [(a, b) for a, b in itertools.combinations(defects, 2)
+             if not (a[0] == b[0] and (a[0] in ("P", scalar) or {a[1], b[1]} in EXCLUSIVE
+                                       or "overlap" in (a[1], b[1])))]
+
+    def run(case, omit=()):
+        P = 8
+        asked = {op: set() for op in operands}
+        o = {scalar: SCALARS[scalar][0]} if scalar else {}
+        for op, kind in case:
+            if op == "P":
+                P = kind
+            elif op == scalar:
+                o[op] = kind
+            else:
+                asked[op].add(kind)
+        o.update({op: make(asked[op]) for op, (make, _) in operands.items()})
+        if "overlap" in asked.get("H", ()):
+            o["H"] = o["U"]
+        if name in ("trimmed_mean", "mean_around_median"):
+            omit = ()  # out is not optional there
+        for op in omit:
+            if op in o:
+                o[op] = None
+
+        def invoke():
+            result = call(_native, o, P)
+            return "ok" if torch.is_tensor(result) or isinstance(result, tuple) else result
+        return _outcome(invoke)
+
+    yield "defaults", run((), omit=OPTIONAL)
+    for case in singles + pairs:
+        yield "+".join(f"{op}:{kind}" for op, kind in case) or "well-formed", run(case)
+
+
+SECTIONS = {"constructor_grid": constructor_grid, "constructor_values": constructor_values,
+            "constructor_pairs": constructor_pairs, "constructor_attacks": constructor_attacks,
+            "subclasses": subclasses, "subset_models": subset_models}
+SECTIONS.update({f"native_{name}": (lambda name=name: _wrapper_cases(name)) for name in WRAPPERS})
+
+
+def enumerate_section(section):
+    """[(key, outcome)] of one section, on the CPU doubles and the library stub."""
+    from distributed_learning_simulator_amd import _native
+    with pytest.MonkeyPatch.context() as mp:
+        cpu_doubles.install(mp)
+        mp.setattr(_native, "lib", _StubLibrary)
+        return list(SECTIONS[section]())
+
+
+# The fixture holds every distinct outcome once ("messages") and per section the digest
+# of its inputs' keys in order and, input by input, the index of the recorded outcome.
+def _digest(cases):
+    return hashlib.sha256("\n".join(k for k, _ in cases).encode()).hexdigest()[:16]
+
+
+@pytest.fixture(scope="module")
+def recorded():
+    with open(FIXTURE) as fh:
+        return json.load(fh)
+
+
+@pytest.mark.parametrize("section", list(SECTIONS))
+def test_outcomes_are_the_recorded_ones(section, recorded):
+    got = enumerate_section(section)
+    want = [recorded["messages"][i] for i in recorded["sections"][section]["outcomes"]]
+    assert (len(got), _digest(got)) == (len(want), recorded["sections"][section]["inputs"]), \
+        "the enumeration and the fixture list other inputs"
+    differ = [(k, v, w) for (k, v), w in zip(got, want) if v != w]
+    assert not differ, f"{len(differ)} of {len(got)} outcomes changed; the first: {differ[0]}"
+
+
+def test_the_fixture_holds_every_section(recorded):
+    assert list(recorded["sections"]) == list(SECTIONS)
+    assert len(set(recorded["messages"])) == len(recorded["messages"])
+
+
+if __name__ == "__main__":
+    messages, sections = {}, {}
+    for section_name in SECTIONS:
+        cases = enumerate_section(section_name)
+        assert len({k for k, _ in cases}) == len(cases), f"{section_name}: a key repeats"
+        sections[section_name] = {
+            "inputs": _digest(cases),
+            "outcomes": [messages.setdefault(v, len(messages)) for _, v in cases]}
+    with open(FIXTURE, "w") as fh:  # one message per line, the indices in lines of 100 columns
+        fh.write('{"messages": [\n' + ",\n".join(json.dumps(m) for m in messages) + '],\n')
+        fh.write('"sections": {\n' + ",\n".join(
+            f'{json.dumps(name)}: {{"inputs": {json.dumps(sec["inputs"])}, "outcomes": [\n'
+            + "\n".join(textwrap.wrap(", ".join(map(str, sec["outcomes"])), 100)) + "]}"
+            for name, sec in sections.items()) + "}}\n")
+    print({k: len(v["outcomes"]) for k, v in sections.items()}, len(messages), "messages",
+          os.path.getsize(FIXTURE), "bytes")
