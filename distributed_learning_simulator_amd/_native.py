@@ -77,6 +77,8 @@ SIGNATURES = {
     "dls_rows_sqdist_to_f32": ([_p, _i64, _p, _i32, _i64, _p, _p, _p, _p], _i32),
     "dls_weiszfeld_step_f32": ([_p, _i64, _p, _i32, _p, _i64, _p, _p, _p, _p], _i32),
     "dls_centered_clip_step_f32": ([_p, _i64, _p, _i32, _p, _i64, _p, _p, _p, _p], _i32),
+    "dls_server_opt_step_f32": ([_i32, _p, _p, _p, _p, _p, _i64, _f32, _f32, _f32, _f32, _f32, _f32,
+                                 _p], _i32),
     "dls_subset_gemm_f32": ([_p, _i32, _i32, _p, _i64, _p, _i64, _p, _i64, _p], _i32),
     "dls_sign_pack_f32": ([_p, _i64, _i32, _i64, _p, _i64, _p, _p], _i32),
     "dls_sign_vote_count": ([_p, _i64, _p, _i32, _i64, _p, _p], _i32),
@@ -164,7 +166,7 @@ def _stream(stream=None, like=None):
 
 
 CSRC_HASHED = ["dls_runtime.hip", "fedavg.hip", "sign.hip", "quant.hip", "quant_fma.hip", "shapley.hip",
-               "infer.hip", "conv.hip", "lenet.hip", "loss.hip", "robust.hip", "pairdist.hip", "weiszfeld.hip", "gram.hip", "dls_common.h", "quant_common.h",
+               "infer.hip", "conv.hip", "lenet.hip", "loss.hip", "robust.hip", "pairdist.hip", "weiszfeld.hip", "gram.hip", "serveropt.hip", "dls_common.h", "quant_common.h",
                "loss_common.h", os.path.join("..", "..", "include", "dls_hip.h")]
 
 
@@ -521,6 +523,85 @@ def centered_clip_step(U, rows, c, P, z, dist2=None, stream=None):
     if stream is not None:
         work.record_stream(stream)
     return z, dist2
+
+
+# DLS_SERVER_OPT_* (include/dls_hip.h): the kinds, and the launch shape of the step
+SERVER_OPT_SGD, SERVER_OPT_ADAGRAD, SERVER_OPT_ADAM, SERVER_OPT_YOGI = range(4)
+SERVER_OPT_KINDS = {"sgd": SERVER_OPT_SGD, "adagrad": SERVER_OPT_ADAGRAD,
+                    "adam": SERVER_OPT_ADAM, "yogi": SERVER_OPT_YOGI}
+SERVER_OPT_BLOCK = 256  # threads per block
+SERVER_OPT_MAX_BLOCKS = 2048  # the grid's cap: further vectors are grid-strided
+SERVER_OPT_UNROLL = 2  # 16-byte vectors (of 4 elements) per thread and visit
+
+
+def fl32(x):
+    """The fp32 value nearest to x (ties to even), as a Python float."""
+    return ctypes.c_float(float(x)).value
+
+
+def server_opt_coeffs(lr, beta1, beta2, tau):
+    """The coefficients dls_server_opt_step_f32 is handed, as Python floats that hold
+    fp32 values: (lr, beta1, omb1, beta2, omb2, tau), each of lr, beta1, beta2, tau
+    rounded to fp32 once and omb = fl32(1.0 - float64(fl32(beta))).  RuntimeError if one
+    of them is not finite after the rounding."""
+    lr, beta1, beta2, tau = fl32(lr), fl32(beta1), fl32(beta2), fl32(tau)
+    coeffs = (lr, beta1, fl32(1.0 - beta1), beta2, fl32(1.0 - beta2), tau)
+    if not all(math.isfinite(c) for c in coeffs):
+        raise RuntimeError(f"server_opt_step: lr={lr}, beta1={beta1}, beta2={beta2} and tau={tau} "
+                           "must be finite in fp32")
+    return coeffs
+
+
+def server_opt_step(kind, agg, x, m, v, out, P, lr, beta1, beta2, tau, stream=None):
+    """One fused server-optimizer step (dls_server_opt_step_f32): with d = fl32(agg - x),
+    SERVER_OPT_SGD: m' = fl32(fl32(beta1 * m) + d), out = fl32(x + fl32(lr * m'));
+    the adaptive kinds: m' = fl32(fl32(beta1 * m) + fl32(omb1 * d)), v' from d2 = fl32(d *
+    d) - ADAGRAD v + d2, ADAM fl32(beta2 * v) + fl32(omb2 * d2), YOGI v - fl32(omb2 *
+    d2) * sign(v - d2) - and out = fl32(x + fl32(lr * m') / fl32(sqrt(v') + tau)), every
+    operation rounded once, with the coefficients of ``server_opt_coeffs(lr, beta1,
+    beta2, tau)``: numpy float32 reproduces out, m' and v' bit for bit.  agg, x, m, v,
+    out: fp32 vectors of at least P elements with unit stride on one device; m and v
+    are updated in place; v is None for SGD, m may be None for SGD with beta1 == 0;
+    out may be x itself (the same first element) and nothing else may overlap.  Returns
+    out."""
+    fn = "server_opt_step"
+    if isinstance(kind, bool) or not isinstance(kind, int) or not 0 <= kind <= SERVER_OPT_YOGI:
+        raise RuntimeError(f"{fn}: kind={kind!r} must be one of {SERVER_OPT_KINDS}")
+    P = int(P)
+    if P < 0:
+        raise RuntimeError(f"{fn}: P={P}")
+    lr, beta1, omb1, beta2, omb2, tau = server_opt_coeffs(lr, beta1, beta2, tau)
+    sgd = kind == SERVER_OPT_SGD
+    if sgd and v is not None:
+        raise RuntimeError(f"{fn}: v must be None for SERVER_OPT_SGD")
+    if not sgd and v is None:
+        raise RuntimeError(f"{fn}: kind={kind} needs v")
+    if m is None and not (sgd and beta1 == 0.0):
+        raise RuntimeError(f"{fn}: m may be None for SERVER_OPT_SGD with beta1 == 0 alone")
+    ops = {"agg": agg, "x": x, "m": m, "v": v, "out": out}
+    given = {name: t for name, t in ops.items() if not (t is None and name in ("m", "v"))}
+    for name, t in given.items():
+        _f32_vector(fn, name, t, P)
+    for name, t in given.items():  # (_check_same_device names its first operand x)
+        if t.device != agg.device:
+            raise RuntimeError(f"{fn}: {name} is on {t.device}, agg on {agg.device}")
+    names = list(given)
+    for i, a in enumerate(names):
+        for b in names[i + 1:]:
+            ta, tb = given[a][:P], given[b][:P]
+            if (a, b) == ("x", "out") and ta.data_ptr() == tb.data_ptr():
+                continue
+            if _overlaps(ta, tb):
+                raise RuntimeError(f"{fn}: {a} and {b} overlap (out may be x itself, nothing "
+                                   "else may overlap)")
+    for t in given.values():
+        _ptr(t)  # no CPU path
+    if P == 0:
+        return out
+    _check(lib().dls_server_opt_step_f32(kind, _ptr(agg), _ptr(x), _ptr(m), _ptr(v), _ptr(out), P,
+                                         lr, beta1, omb1, beta2, omb2, tau, _stream(stream, agg)),
+           "dls_server_opt_step_f32")
+    return out
 
 
 def subset_fedavg(U, sub_off, sub_rows, sub_weight, sub_total, P, out, stream=None):

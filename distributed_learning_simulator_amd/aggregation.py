@@ -344,6 +344,8 @@ class ClientUpdateStore:
         self._free = list(range(lo, hi))[::-1]
         self._lock = threading.Lock()
         self.history = None  # fp32 [worker ids, P], zeroed on first use (fold_history)
+        self.model = None  # the current global model, fp32 [P] (set_model)
+        self.server_opt = None  # the server optimizer's state (reset_server_opt)
 
     @property
     def capacity(self):
@@ -756,6 +758,67 @@ class ClientUpdateStore:
         _native.centered_clip_step(self.U, _i32([rows[order[k]] for k in kept], self.device),
                                    _f32(coeffs, self.device), P, flat)
         return flat, info
+
+    # ------------------------------------------------------- server optimizer
+    def set_model(self, flat):
+        """Hold ``flat`` (an fp32 device vector of ``layout.P`` elements, padding zero) as
+        the current global model: what the next ``server_opt_step`` steps from."""
+        P = self.layout.P
+        if (not torch.is_tensor(flat) or flat.dtype != torch.float32 or flat.dim() != 1
+                or flat.numel() != P or flat.device != self.U.device):
+            raise ValueError(f"the model must be an fp32 vector of P={P} elements on "
+                             f"{self.U.device}")
+        self.model = flat
+
+    def reset_server_opt(self, kind=None, coeffs=None):
+        """The server optimizer's initial state for ``kind`` (a ``_native.SERVER_OPT_*``)
+        and ``coeffs`` (``_native.server_opt_coeffs``): step 0, m zero, v = fl32(tau *
+        tau) on the tensors' elements (Reddi et al. start from v >= tau^2) and zero on
+        the padding between them; SGD has no v, and no m either without momentum.
+        Without arguments: the state goes back to its start for the kind and coefficients
+        it was made with (nothing happens while there is none)."""
+        if kind is None:
+            if self.server_opt is None:
+                return
+            kind, coeffs = self.server_opt["kind"], self.server_opt["coeffs"]
+        P = self.layout.P
+        _, beta1, _, _, _, tau = coeffs
+        sgd = kind == _native.SERVER_OPT_SGD
+        m = None if sgd and beta1 == 0.0 else torch.zeros(P, dtype=torch.float32,
+                                                            device=self.device)
+        v = None
+        if not sgd:
+            v = torch.zeros(P, dtype=torch.float32, device=self.device)
+            v0 = _native.fl32(tau * tau)  # the product of two fp32 is exact in fp64
+            for o, n in zip(self.layout.offsets, self.layout.numels):
+                v[o:o + n] = v0
+        self.server_opt = {"kind": kind, "coeffs": tuple(coeffs), "step": 0, "m": m, "v": v}
+
+    def server_opt_step(self, flat_agg, kind, coeffs):
+        """One server-optimizer step (dls_server_opt_step_f32) from the held model
+        (``set_model``) towards the aggregate ``flat_agg``, an fp32 device vector of
+        ``layout.P`` elements: the pseudo-gradient is flat_agg - model.  ``kind`` is a
+        ``_native.SERVER_OPT_*``, ``coeffs`` the fp32 values of
+        ``_native.server_opt_coeffs``; the state (``server_opt``: step, m, v) is made by
+        ``reset_server_opt`` on first use, or when the kind or the coefficients change,
+        and updated in place.  The new model is a new vector: it is returned and held as
+        the current model; flat_agg and the old model are left alone.  The padding
+        between the tensors stays exactly zero in the model, m and v: there d = 0, m = 0
+        and v = 0, so the update is 0 / tau = 0."""
+        if self.model is None:
+            raise ValueError("server_opt_step: no current model (set_model)")
+        coeffs = tuple(coeffs)
+        st = self.server_opt
+        if st is None or st["kind"] != kind or st["coeffs"] != coeffs:
+            self.reset_server_opt(kind, coeffs)
+            st = self.server_opt
+        lr, beta1, _, beta2, _, tau = coeffs
+        out = _native.server_opt_step(kind, flat_agg, self.model, st["m"], st["v"],
+                                      self._vector(self.layout.P), self.layout.P, lr, beta1, beta2,
+                                      tau)
+        st["step"] += 1
+        self.model = out
+        return out
 
     def subset_models(self, subsets, n_of_row, method="exact", out=None):
         """S subset models at once.  subsets: list of row lists (non-empty, in order).

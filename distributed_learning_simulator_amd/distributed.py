@@ -97,6 +97,8 @@ def allreduce_chunked(flat, chunks=3, group=None, produce=None):
 class _ShardedMixin:
     _attack_unsupported = ("a rank of the sharded servers holds only its own clients' rows, "
                            "not every honest update the attackers craft from")
+    _server_opt_unsupported = ("the optimizer state would have to be kept identical on every "
+                               "rank of the sharded servers")
 
     def _init_shard(self, worker_number, group, chunks):
         # before FedServer.__init__, which publishes the initial broadcast to

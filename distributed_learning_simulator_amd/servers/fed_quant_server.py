@@ -54,6 +54,8 @@ class FedQuantServer(FedServer):
 
     _robust_unsupported = "its weighted mean is fused with the dequantization of the int payloads"
     _attack_unsupported = "its store holds the clients' int payloads, not fp32 rows to rewrite"
+    _server_opt_unsupported = ("its round model is re-quantized before it is broadcast, so the "
+                               "clients never start from the stepped model")
 
     def __init__(self, quantization_level=256, stochastic=False, seed=0, granularity="model",
                  **kwargs):

@@ -7,6 +7,8 @@ loop of K x (#tensors) torch ops, bit-exact with the reference's op order.
 import copy
 import logging
 
+import torch
+
 from .. import _native
 from ..aggregation import (ATTACKS, ClientParameters, ClientUpdateStore, attack_coefficients,
                            finite_number)
@@ -30,6 +32,15 @@ _ATTACK_OF = {"attack_z": "alie", "attack_eps": "ipm", "attack_scale": "sign_fli
 _GROUPS = ((("trim",), "trimmed_mean"), (("byzantine", "krum_select"), "multi_krum"),
            (("gm_iters", "gm_nu"), "geometric_median"), (("cc_tau", "cc_iters"), "centered_clip"),
            (("fg_kappa",), "foolsgold"))
+# The server optimizers (FedAvgM: Hsu et al. 2019; FedAdagrad / FedAdam / FedYogi: Reddi et al.
+# 2021), their constructor parameters with the defaults that mean "not set", and the
+# optimizers that own each parameter.
+SERVER_OPTIMIZERS = tuple(_native.SERVER_OPT_KINDS)
+_ADAPTIVE = ("adagrad", "adam", "yogi")
+SERVER_OPT_DEFAULTS = {"server_lr": None, "server_momentum": None, "server_beta2": 0.99,
+                       "server_tau": 1e-3}
+_SERVER_OPT_OWNERS = {"server_lr": SERVER_OPTIMIZERS, "server_momentum": SERVER_OPTIMIZERS,
+                      "server_beta2": ("adam", "yogi"), "server_tau": _ADAPTIVE}
 # Every robust rule needs 2*trim < K (trim is 0 under all but the trimmed mean).
 _TRIM_FITS = (lambda K, p: 2 * p["trim"] < K,
               "trim={trim} leaves nothing of {clients} (2*trim < {n} is needed)")
@@ -154,6 +165,35 @@ class FedServer(Server):
 
     ``last_attack`` holds the latest round's attack, attackers and coefficients.
 
+    ``server_optimizer`` turns the round's aggregate, of whichever rule, into the next
+    global model through a server optimizer instead of storing it as it is (None, the
+    default and the reference's behaviour: server learning rate 1, no momentum).  The
+    pseudo-gradient is d = aggregate - previous model and one fused launch
+    (dls_server_opt_step_f32) updates the moments and the model:
+
+    * ``"sgd"``: server momentum, FedAvgM (Hsu et al. 2019): m <- ``server_momentum`` *
+      m + d, model += ``server_lr`` * m;
+    * ``"adagrad"``, ``"adam"``, ``"yogi"``: FedAdagrad, FedAdam and FedYogi (Reddi et al.
+      2021, without bias correction, as in the paper): m <- beta1 * m + (1 - beta1) * d
+      with beta1 = ``server_momentum``; v <- v + d^2 (adagrad), beta2 * v + (1 - beta2) *
+      d^2 (adam) or v - (1 - beta2) * d^2 * sign(v - d^2) (yogi) with beta2 =
+      ``server_beta2``; model += ``server_lr`` * m / (sqrt(v) + ``server_tau``).  m starts at
+      zero and v at ``server_tau``^2.
+
+    ``server_lr`` defaults to 1.0 for sgd and to 0.01 for the adaptive optimizers (this
+    project's choice: Reddi et al. tune it per task between 1e-3 and 1), ``server_momentum``
+    to 0.0 for sgd (with ``server_lr`` 1.0 that is plain FedAvg again, up to one rounding)
+    and 0.9 for the adaptive ones, ``server_beta2`` to 0.99 and ``server_tau`` to 1e-3.  A
+    parameter given to an optimizer that does not use it raises.  While there is no
+    previous model (round 1 of a server without a tester) the aggregate becomes the model
+    as it is and the state is created.  An aggregate that is not finite raises
+    ``ValueError`` before the step and leaves the state alone: a poisoned m or v would
+    never recover.  ``get_subset_model`` stays the pure aggregate of the subset (what the
+    subset would have averaged to).  ``server_opt_state`` holds the step count and the
+    views of m and v, ``last_server_step`` the Euclidean norms of the latest
+    pseudo-gradient and applied update, ``reset_server_optimizer()`` starts the state
+    over.
+
     The robust rules ignore the clients' sample counts n_i (every client counts
     once), take at most ``_native.ROBUST_MAX_K`` clients and are bit-identical for
     any arrival order.  Hooks, ``prev_model``, ``get_metric`` and the round protocol
@@ -163,6 +203,8 @@ class FedServer(Server):
     _robust_unsupported = None
     # why a subclass cannot run the Byzantine client attacks (None: it can)
     _attack_unsupported = None
+    # why a subclass cannot run a server optimizer (None: it can)
+    _server_opt_unsupported = None
 
     def __init__(self, aggregation_mode="exact", aggregation_rule="mean",
                  trim=DEFAULTS["trim"], byzantine=DEFAULTS["byzantine"],
@@ -171,7 +213,10 @@ class FedServer(Server):
                  attack=None, attackers=(), attack_z=ATTACK_DEFAULTS["attack_z"],
                  attack_eps=ATTACK_DEFAULTS["attack_eps"],
                  attack_scale=ATTACK_DEFAULTS["attack_scale"], fg_kappa=DEFAULTS["fg_kappa"],
-                 **kwargs):
+                 server_optimizer=None, server_lr=SERVER_OPT_DEFAULTS["server_lr"],
+                 server_momentum=SERVER_OPT_DEFAULTS["server_momentum"],
+                 server_beta2=SERVER_OPT_DEFAULTS["server_beta2"],
+                 server_tau=SERVER_OPT_DEFAULTS["server_tau"], **kwargs):
         if aggregation_mode not in _MODES:
             raise ValueError(f"aggregation_mode must be one of {sorted(_MODES)}, not {aggregation_mode!r}")
         self._check_rule(aggregation_rule, aggregation_mode, kwargs.get("worker_number"),
@@ -180,9 +225,18 @@ class FedServer(Server):
                          fg_kappa=fg_kappa)
         attackers = self._check_attack(attack, attackers, attack_z, attack_eps, attack_scale,
                                        kwargs.get("worker_number"))
+        server_opt = self._check_server_opt(server_optimizer, server_lr, server_momentum,
+                                            server_beta2, server_tau)
         super().__init__(**kwargs)
         _native.require_gpu()
         self.round = 0
+        self.server_optimizer = server_optimizer
+        # the resolved lr, momentum, beta2, tau, and the fp32 values the kernel is handed
+        self.server_lr, self.server_momentum, self.server_beta2, self.server_tau = \
+            server_opt if server_opt else (None,) * 4
+        self._server_opt_coeffs = _native.server_opt_coeffs(*server_opt) if server_opt else None
+        self.last_server_step = {}
+        self._server_opt_adopted = False  # "no previous model" is logged once
         self.aggregation_mode = aggregation_mode
         self.aggregation_rule = aggregation_rule
         self.trim = int(trim)
@@ -314,6 +368,52 @@ class FedServer(Server):
                     attack_coefficients("alie", worker_number, len(ids))  # alie_z's ValueError
         return tuple(sorted(ids))
 
+    @classmethod
+    def _check_server_opt(cls, optimizer, server_lr=SERVER_OPT_DEFAULTS["server_lr"],
+                          server_momentum=SERVER_OPT_DEFAULTS["server_momentum"],
+                          server_beta2=SERVER_OPT_DEFAULTS["server_beta2"],
+                          server_tau=SERVER_OPT_DEFAULTS["server_tau"]):
+        """The resolved (server_lr, server_momentum, server_beta2, server_tau) of a server
+        optimizer, or None without one; ValueError for what no round could run."""
+        if optimizer is not None and optimizer not in SERVER_OPTIMIZERS:
+            raise ValueError(f"server_optimizer must be None or one of {list(SERVER_OPTIMIZERS)}, "
+                             f"not {optimizer!r}")
+        given = {"server_lr": server_lr, "server_momentum": server_momentum,
+                 "server_beta2": server_beta2, "server_tau": server_tau}
+        for name, v in given.items():
+            if v is None and SERVER_OPT_DEFAULTS[name] is None:
+                continue
+            if name in ("server_lr", "server_tau"):
+                finite_number(name, v, positive=True)
+            elif finite_number(name, v) < 0.0 or v >= 1.0:
+                raise ValueError(f"{name} must be in [0, 1), not {v!r}")
+        for name, v in given.items():
+            if v != SERVER_OPT_DEFAULTS[name] and optimizer not in _SERVER_OPT_OWNERS[name]:
+                owners = _SERVER_OPT_OWNERS[name]
+                raise ValueError(f"{name}={v} needs server_optimizer "
+                                 + (f"in {list(owners)}" if len(owners) < len(SERVER_OPTIMIZERS)
+                                    else f"set, one of {list(owners)}") + f", not {optimizer!r}")
+        if optimizer is None:
+            return None
+        if cls._server_opt_unsupported is not None:
+            raise ValueError(
+                f"{cls.__name__} does not support server_optimizer={optimizer!r} "
+                f"({cls._server_opt_unsupported}); the one-process FedServer "
+                "(factory.get_server('fed', ...)) is the server that runs the server optimizers")
+        sgd = optimizer == "sgd"
+        lr = float(server_lr) if server_lr is not None else (1.0 if sgd else 0.01)
+        beta1 = float(server_momentum) if server_momentum is not None else (0.0 if sgd else 0.9)
+        try:
+            _native.server_opt_coeffs(lr, beta1, server_beta2, server_tau)
+        except RuntimeError as e:
+            raise ValueError(str(e))
+        if _native.fl32(lr) == 0.0 or _native.fl32(server_tau) == 0.0 or _native.fl32(beta1) >= 1.0 \
+                or _native.fl32(server_beta2) >= 1.0:
+            raise ValueError(f"server_lr={lr} and server_tau={server_tau} must be positive and "
+                             f"server_momentum={beta1} and server_beta2={server_beta2} below 1 "
+                             "when rounded to fp32")
+        return lr, beta1, float(server_beta2), float(server_tau)
+
     @property
     def clients_per_round(self):
         """Clients whose updates this process receives per round (all of them here;
@@ -369,14 +469,16 @@ class FedServer(Server):
         """servers/fed_server.py:44-66 (empty subset -> previous model)."""
         if not client_subset:
             return self.__prev_model
-        ids = list(client_subset)
         store = self.parameters.store
+        return store.layout.views(self._subset_flat(store, list(client_subset)))
+
+    def _subset_flat(self, store, ids):
+        """The aggregate of the clients ``ids`` under the server's rule, as a flat vector."""
         # the rules that report, break ties and order by worker id are handed the ids (no
         # subclass that overrides _aggregate runs those rules)
         extra = {"ids": ids} if RULES[self.aggregation_rule]["ids"] else {}
-        flat = self._aggregate(store, [self.parameters.row_of(i) for i in ids],
+        return self._aggregate(store, [self.parameters.row_of(i) for i in ids],
                                [self.parameters.n_of(i) for i in ids], **extra)
-        return store.layout.views(flat)
 
     def _aggregate(self, store, rows, ns, total=None, ids=None):
         if self.aggregation_rule == "mean":
@@ -530,6 +632,54 @@ class FedServer(Server):
                  self.attack, list(self.attackers), len(honest), info["a"], info["b"],
                  "relative to the previous model" if base is not None else "no base")
 
+    @property
+    def server_opt_state(self):
+        """None without a server optimizer; else {"step": the steps taken, "m": the first
+        moment as a dict of views (None before the state exists, and for sgd without
+        momentum), "v": the second moment likewise (None for sgd)}."""
+        if self.server_optimizer is None:
+            return None
+        store = self.parameters.store
+        st = store.server_opt if store is not None else None
+        if st is None:
+            return {"step": 0, "m": None, "v": None}
+        views = store.layout.views
+        return {"step": st["step"], "m": None if st["m"] is None else views(st["m"]),
+                "v": None if st["v"] is None else views(st["v"])}
+
+    def reset_server_optimizer(self):
+        """Start the server optimizer's state over: step 0, m zero, v = server_tau^2."""
+        if self.parameters.store is not None:
+            self.parameters.store.reset_server_opt()
+
+    def _server_opt_round(self, store, flat):
+        """The round's model from its aggregate ``flat``: one server-optimizer step from
+        the previous global model; the aggregate itself while there is none."""
+        kind = _native.SERVER_OPT_KINDS[self.server_optimizer]
+        if not bool(torch.isfinite(flat).all()):
+            raise ValueError(f"server_optimizer={self.server_optimizer!r}: the aggregate of round "
+                             f"{self.round} is not finite; the optimizer state is left as it was")
+        prev = self._prev_flat(store)
+        if prev is None:
+            if not self._server_opt_adopted:
+                log.info("server_optimizer %s: no previous model in round %s, the aggregate "
+                         "becomes the model and the state starts from it",
+                         self.server_optimizer, self.round)
+                self._server_opt_adopted = True
+            if store.server_opt is None:
+                store.reset_server_opt(kind, self._server_opt_coeffs)
+            store.set_model(flat)
+            self.last_server_step = {}
+            return flat
+        store.set_model(prev)
+        out = store.server_opt_step(flat, kind, self._server_opt_coeffs)
+        norms = torch.stack([torch.linalg.vector_norm(flat - prev, dtype=torch.float64),
+                             torch.linalg.vector_norm(out - prev, dtype=torch.float64)]).tolist()
+        self.last_server_step = {"pseudo_gradient_norm": norms[0], "update_norm": norms[1]}
+        log.info("server_optimizer %s: step %s, pseudo-gradient norm %s, update norm %s",
+                 self.server_optimizer, store.server_opt["step"], norms[0], norms[1])
+        return out
+
     def _process_worker_data(self, data, __):
         worker_id, training_dataset_size, parameter_dict = data
         self.parameters[worker_id] = (
@@ -545,7 +695,12 @@ class FedServer(Server):
         if self.aggregation_rule == "foolsgold":
             self._fold_round()
         log.info("begin aggregating")
-        avg_parameter = self.get_subset_model(self.parameters.keys())
+        if self.server_optimizer is None:
+            avg_parameter = self.get_subset_model(self.parameters.keys())
+        else:
+            store = self.parameters.store
+            avg_parameter = store.layout.views(self._server_opt_round(
+                store, self._subset_flat(store, list(self.parameters.keys()))))
         data = self._process_aggregated_parameter(avg_parameter)
         self.__prev_model = copy.deepcopy(data)
         acc = self.get_metric(self.prev_model)

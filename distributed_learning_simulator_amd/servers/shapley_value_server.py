@@ -37,6 +37,8 @@ from .fed_server import FedServer
 
 class ShapleyValueServer(FedServer):
     _robust_unsupported = "coalition models come from the batched subset-mean kernels"
+    _server_opt_unsupported = ("its round hook picks or records the round model among the "
+                               "coalitions' plain means")
 
     def __init__(self, subset_method="exact", subset_batch=None, eval_streams=1,
                  utility_metric="acc", **kwargs):

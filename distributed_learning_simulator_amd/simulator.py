@@ -10,6 +10,9 @@
          --aggregation_rule mean_around_median --byzantine 2 |
          --aggregation_rule bulyan --byzantine 2 |
          --aggregation_rule foolsgold [--fg_kappa 1.0]]
+        [--server_optimizer sgd [--server_lr 1.0] [--server_momentum 0.9] |
+         --server_optimizer adagrad|adam|yogi [--server_lr 0.01] [--server_momentum 0.9]
+             [--server_beta2 0.99] [--server_tau 1e-3]]
         [--attack alie --attackers 3,7 [--attack_z 1.0] |
          --attack ipm --attackers 3,7 [--attack_eps 0.1] |
          --attack sign_flip --attackers 3,7 [--attack_scale 1.0]]
@@ -32,7 +35,8 @@ import torch
 from .aggregation import ATTACKS
 from .factory import get_server, get_worker
 from .models import MODELS, synthetic_classification
-from .servers.fed_server import ATTACK_DEFAULTS, DEFAULTS, RULES
+from .servers.fed_server import (ATTACK_DEFAULTS, DEFAULTS, RULES, SERVER_OPT_DEFAULTS,
+                                 SERVER_OPTIMIZERS)
 from .trainer import Inferencer, Trainer
 
 DATASETS = {"MNIST": (1, 32, 32), "CIFAR10": (3, 32, 32)}
@@ -103,7 +107,21 @@ def get_config(argv=None):
     ap.add_argument("--attackers", type=_worker_ids, default=())
     for name, default in ATTACK_DEFAULTS.items():
         ap.add_argument("--" + name, type=float, default=default)
+    # the server optimizer that turns the round's aggregate (of any rule) into the next
+    # model, with aggregate - previous model as its pseudo-gradient: "sgd" is server
+    # momentum (FedAvgM), "adagrad" / "adam" / "yogi" are FedAdagrad / FedAdam / FedYogi
+    # (Reddi et al. 2021); none given: the aggregate is the next model.  --server_lr
+    # defaults to 1.0 for sgd and 0.01 for the adaptive ones, --server_momentum (beta1) to
+    # 0.0 and 0.9; --server_beta2 and --server_tau belong to the adaptive ones
+    ap.add_argument("--server_optimizer", type=str, default=None, choices=SERVER_OPTIMIZERS)
+    for name in SERVER_OPT_DEFAULTS:
+        ap.add_argument("--" + name, type=float, default=None)
     config = ap.parse_args(argv)
+    if config.distributed_algorithm == "sign_SGD" and any(
+            getattr(config, name) is not None
+            for name in ("server_optimizer",) + tuple(SERVER_OPT_DEFAULTS)):
+        ap.error("--server_optimizer and its parameters apply to the fed server, whose round "
+                 "ends in a model; sign_SGD broadcasts a vote")
     if config.distributed_algorithm == "sign_SGD" and config.aggregation_rule != "mean":
         ap.error("--aggregation_rule applies to the FedAvg-based servers; sign_SGD votes")
     if config.distributed_algorithm == "sign_SGD" and config.attack is not None:
@@ -130,7 +148,8 @@ def server_kwargs(config):
     gm_iters / gm_nu, centered clipping's cc_tau / cc_iters and FoolsGold's fg_kappa for
     those rules alone, and
     the attack with its attackers and parameters when --attack is given (the server
-    rejects a parameter that belongs to another attack)."""
+    rejects a parameter that belongs to another attack), and --server_optimizer and
+    each of its parameters that was given."""
     if config.distributed_algorithm == "sign_SGD":
         return {}
     kwargs = {"aggregation_mode": config.aggregation_mode}
@@ -145,6 +164,9 @@ def server_kwargs(config):
         kwargs["attackers"] = tuple(getattr(config, "attackers", ()))
         for name, default in ATTACK_DEFAULTS.items():
             kwargs[name] = getattr(config, name, default)
+    for name in ("server_optimizer",) + tuple(SERVER_OPT_DEFAULTS):  # only the ones given
+        if getattr(config, name, None) is not None:
+            kwargs[name] = getattr(config, name)
     return kwargs
 
 

@@ -353,6 +353,51 @@ int dls_centered_clip_step_f32(const float *U, int64_t ldu, const int32_t *rows,
                                const float *c, int64_t P, float *z, double *dist2,
                                void *workspace, dls_stream_t stream);
 
+/* Fused server-optimizer step: the round's aggregate becomes the next global model
+ * through a server optimizer instead of being stored as it is.  It replaces the round
+ * end of servers/fed_server.py (:81-84, where the aggregate is stored as the next
+ * model: server learning rate 1, no momentum): agg - x is the pseudo-gradient of
+ * FedAvgM (Hsu et al. 2019; DLS_SERVER_OPT_SGD) or of FedAdagrad / FedAdam / FedYogi
+ * (Reddi et al. 2021, "Adaptive Federated Optimization"; no bias correction).
+ * agg, x, m, v, out are device fp32 [P], 4-byte aligned (DLS_ELAYOUT otherwise); m and
+ * v are read and overwritten in place.  Per coordinate p, every operation rounded
+ * once to fp32 and never fused; the coefficients are the bits passed in (omb1 and omb2
+ * are the caller's roundings of 1 - beta1 and 1 - beta2; they are not recomputed):
+ *   d = fl(agg - x)
+ *   SGD:      m' = fl(fl(beta1*m) + d)            (m may be NULL only with beta1 == 0:
+ *             out = fl(x + fl(lr*m'))              then m' = d and is not stored; v
+ *                                                  must be NULL)
+ *   adaptive: m' = fl(fl(beta1*m) + fl(omb1*d));  d2 = fl(d*d)
+ *     ADAGRAD: v' = fl(v + d2)
+ *     ADAM:    v' = fl(fl(beta2*v) + fl(omb2*d2))
+ *     YOGI:    t = fl(v - d2);  s = (t > 0) - (t < 0);  v' = fl(v - fl(fl(omb2*d2) * s))
+ *             out = fl(x + fl(lr*m') / fl(sqrt(v') + tau))
+ * with the division and the square root correctly rounded and denormals kept.  Given
+ * the input bits, out, m' and v' are defined bit for bit (numpy float32 reproduces
+ * them) wherever the result is not NaN; where the arithmetic gives NaN the kernel
+ * gives some NaN.  A NaN or inf in one coordinate never changes another coordinate.
+ * The bits do not depend on the stream, the CU count or the pointers' alignment.
+ * out may be x itself (the same pointer) or disjoint from everything; any other
+ * overlap among the operands is an error.
+ * Checks, all before any device call (DLS_EINVAL): kind outside 0..3, P < 0, a null
+ * agg, x or out, v given for SGD or missing for an adaptive kind, m missing where it
+ * is needed, a non-finite coefficient, overlapping operands.  P == 0 launches
+ * nothing.
+ * Launch shape (a thread steps DLS_SERVER_OPT_UNROLL 16-byte vectors per visit; blocks
+ * of DLS_SERVER_OPT_BLOCK threads, at most DLS_SERVER_OPT_MAX_BLOCKS, grid-strided):
+ * 16-byte accesses where every operand shares one 16-byte phase (up to 3 elements at
+ * either end go one by one), one element at a time otherwise. */
+#define DLS_SERVER_OPT_SGD 0
+#define DLS_SERVER_OPT_ADAGRAD 1
+#define DLS_SERVER_OPT_ADAM 2
+#define DLS_SERVER_OPT_YOGI 3
+#define DLS_SERVER_OPT_BLOCK 256
+#define DLS_SERVER_OPT_MAX_BLOCKS 2048
+#define DLS_SERVER_OPT_UNROLL 2
+int dls_server_opt_step_f32(int32_t kind, const float *agg, const float *x, float *m, float *v,
+                            float *out, int64_t P, float lr, float beta1, float omb1,
+                            float beta2, float omb2, float tau, dls_stream_t stream);
+
 /* Subset aggregation as a dense fp32 MFMA contraction: out[S, P] = C[S, K] · U[rows, P]
  * (C row-major [S, K], c_si = n_i / N_S; rows[K] selects the K client rows of U).
  * fp32 in / fp32 accumulate (v_mfma_f32_32x32x2_f32): per element one fma chain in
