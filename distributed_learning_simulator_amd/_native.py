@@ -79,6 +79,9 @@ SIGNATURES = {
     "dls_centered_clip_step_f32": ([_p, _i64, _p, _i32, _p, _i64, _p, _p, _p, _p], _i32),
     "dls_server_opt_step_f32": ([_i32, _p, _p, _p, _p, _p, _i64, _f32, _f32, _f32, _f32, _f32, _f32,
                                  _p], _i32),
+    "dls_topk_workspace": ([_i64], _i64),
+    "dls_topk_compress_f32": ([_p, _p, _p, _i64, _i64, _p, _p, _p, _p, _p], _i32),
+    "dls_sparse_fedavg_f32": ([_p, _p, _p, _p, _p, _i32, _f32, _i64, _p, _p], _i32),
     "dls_subset_gemm_f32": ([_p, _i32, _i32, _p, _i64, _p, _i64, _p, _i64, _p], _i32),
     "dls_sign_pack_f32": ([_p, _i64, _i32, _i64, _p, _i64, _p, _p], _i32),
     "dls_sign_vote_count": ([_p, _i64, _p, _i32, _i64, _p, _p], _i32),
@@ -166,7 +169,7 @@ def _stream(stream=None, like=None):
 
 
 CSRC_HASHED = ["dls_runtime.hip", "fedavg.hip", "sign.hip", "quant.hip", "quant_fma.hip", "shapley.hip",
-               "infer.hip", "conv.hip", "lenet.hip", "loss.hip", "robust.hip", "pairdist.hip", "weiszfeld.hip", "gram.hip", "serveropt.hip", "dls_common.h", "quant_common.h",
+               "infer.hip", "conv.hip", "lenet.hip", "loss.hip", "robust.hip", "pairdist.hip", "weiszfeld.hip", "gram.hip", "serveropt.hip", "topk.hip", "dls_common.h", "quant_common.h",
                "loss_common.h", os.path.join("..", "..", "include", "dls_hip.h")]
 
 
@@ -601,6 +604,134 @@ def server_opt_step(kind, agg, x, m, v, out, P, lr, beta1, beta2, tau, stream=No
     _check(lib().dls_server_opt_step_f32(kind, _ptr(agg), _ptr(x), _ptr(m), _ptr(v), _ptr(out), P,
                                          lr, beta1, omb1, beta2, omb2, tau, _stream(stream, agg)),
            "dls_server_opt_step_f32")
+    return out
+
+
+# ------------------------------------------------------- top-k sparsification
+TOPK_MAX_P = (1 << 31) - 1  # idx is int32
+
+
+def _topk_vector(fn, name, t, dtype, n, exact=False):
+    """t: a ``dtype`` vector with unit stride of at least (``exact``: exactly) n elements."""
+    what = {torch.float32: "fp32", torch.int32: "int32", torch.int64: "int64"}[dtype]
+    if (not torch.is_tensor(t) or t.dtype != dtype or t.dim() != 1
+            or (t.numel() != n if exact else t.numel() < n)
+            or (t.numel() > 1 and t.stride(0) != 1)):
+        raise RuntimeError(f"{fn}: {name} must be an {what} vector of "
+                           f"{'exactly' if exact else 'at least'} {n} elements with unit stride")
+
+
+def _topk_one_device(fn, **tensors):
+    (first, t0), *rest = tensors.items()
+    for name, t in rest:
+        if t.device != t0.device:
+            raise RuntimeError(f"{fn}: {name} is on {t.device}, {first} on {t0.device}")
+
+
+def _topk_extent(fn, P):
+    P = int(P)
+    if not 1 <= P <= TOPK_MAX_P or P % 4 != 0:
+        raise RuntimeError(f"{fn}: P={P} must be a multiple of 4 in 4..2^31 - 4")
+    return P
+
+
+def topk_workspace(P, device):
+    """The scratch buffer dls_topk_compress_f32 needs for rows of P elements (a uint8
+    tensor on ``device``; its contents never matter between calls)."""
+    P = _topk_extent("topk_workspace", P)
+    nbytes = int(lib().dls_topk_workspace(P))
+    if nbytes < 0:
+        _check(nbytes, "dls_topk_workspace")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def topk_compress(w, base, e, k, P, idx, val, stats, workspace, stream=None):
+    """Top-k sparsification with error feedback (dls_topk_compress_f32): with u = fl32(
+    fl32(w - base) + e), the k coordinates of the largest |u| (keys bits(u) & 0x7fffffff,
+    ties to the lowest index) are written to idx[:k] (int32, strictly ascending) and
+    val[:k] (u's bits); e becomes +0.0 there and u elsewhere; stats (int32 [2]) becomes
+    (k, the number of non-finite u).  w, base, e: fp32 vectors of at least P elements
+    with unit stride; idx / val: at least k elements; workspace: ``topk_workspace(P)``.
+    1 <= k <= P, P a multiple of 4; e must not overlap w or base; w, base, e, idx, val
+    and the workspace 16-byte aligned.  Nothing is synchronised: the outputs are ready in
+    stream order.  Returns (idx, val)."""
+    fn = "topk_compress"
+    P = _topk_extent(fn, P)
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= P:
+        raise RuntimeError(f"{fn}: k={k!r} must be an integer in 1..P={P}")
+    for name, t in (("w", w), ("base", base), ("e", e)):
+        _f32_vector(fn, name, t, P)
+    _topk_vector(fn, "idx", idx, torch.int32, k)
+    _topk_vector(fn, "val", val, torch.float32, k)
+    _topk_vector(fn, "stats", stats, torch.int32, 2)
+    need = int(lib().dls_topk_workspace(P))
+    if (not torch.is_tensor(workspace) or workspace.dtype != torch.uint8 or workspace.dim() != 1
+            or workspace.numel() < need or (workspace.numel() > 1 and workspace.stride(0) != 1)):
+        raise RuntimeError(f"{fn}: workspace must be a uint8 vector of at least {need} bytes "
+                           "(topk_workspace(P))")
+    _topk_one_device(fn, w=w, base=base, e=e, idx=idx, val=val, stats=stats, workspace=workspace)
+    for name, other in (("w", w), ("base", base)):
+        if _overlaps(e[:P], other[:P]):
+            raise RuntimeError(f"{fn}: e and {name} overlap (the residual is updated in place)")
+    outs = {"e": e[:P], "idx": idx[:k], "val": val[:k], "stats": stats[:2], "workspace": workspace}
+    names = list(outs)
+    for i, a in enumerate(names):
+        for b in names[i + 1:]:
+            if _overlaps(outs[a], outs[b]):
+                raise RuntimeError(f"{fn}: {a} and {b} overlap")
+    for name, t in (("w", w), ("base", base), ("e", e), ("idx", idx), ("val", val),
+                    ("workspace", workspace)):
+        if t.data_ptr() % 16 != 0:
+            raise RuntimeError(f"{fn}: {name} must be 16-byte aligned")
+    for t in (w, base, e, idx, val, stats, workspace):
+        _ptr(t)  # no CPU path
+    _check(lib().dls_topk_compress_f32(_ptr(w), _ptr(base), _ptr(e), P, k, _ptr(idx), _ptr(val),
+                                       _ptr(stats), _ptr(workspace), _stream(stream, w)),
+           "dls_topk_compress_f32")
+    return idx, val
+
+
+def sparse_fedavg(base, idx, val, off, weight, total, P, out, stream=None):
+    """FedAvg over sparse client updates, added to ``base`` (dls_sparse_fedavg_f32): client
+    i of the K = weight.numel() clients, in the given order, holds the pairs idx / val[
+    off[i]:off[i + 1]], its indices strictly ascending in 0..P-1.  A coordinate nobody
+    sent keeps base's bits; elsewhere out = fl32(base + acc), acc the FedAvg chain
+    fl32(fl32(v * n_i) / N) over its senders in client order (the first assigns, the
+    rest add).  base, out: fp32 vectors of at least P elements with unit stride, 16-byte
+    aligned, not overlapping; idx int32 / val fp32 of one length; off int64 [K + 1] with
+    off[0] = 0 and off[K] = idx.numel() (the caller's word: it lives on the device);
+    weight fp32 [K] = the n_i, total = their fp32 sum.  Returns out."""
+    fn = "sparse_fedavg"
+    P = _topk_extent(fn, P)
+    _f32_vector(fn, "base", base, P)
+    _f32_vector(fn, "out", out, P)
+    if not torch.is_tensor(weight) or weight.dtype != torch.float32 or weight.dim() != 1 \
+            or not weight.is_contiguous() or weight.numel() < 1:
+        raise RuntimeError(f"{fn}: weight must be a contiguous fp32 [K] tensor, K >= 1")
+    K = weight.numel()
+    _topk_vector(fn, "off", off, torch.int64, K + 1, exact=True)
+    if not torch.is_tensor(idx) or not torch.is_tensor(val):
+        raise RuntimeError(f"{fn}: idx and val must be tensors")
+    _topk_vector(fn, "idx", idx, torch.int32, idx.numel() if idx.dim() == 1 else -1, exact=True)
+    _topk_vector(fn, "val", val, torch.float32, idx.numel(), exact=True)
+    total = fl32(total)
+    if not math.isfinite(total) or total <= 0.0:
+        raise RuntimeError(f"{fn}: total={total} must be a positive finite number")
+    _topk_one_device(fn, base=base, idx=idx, val=val, off=off, weight=weight, out=out)
+    if _overlaps(out[:P], base[:P]):
+        raise RuntimeError(f"{fn}: out and base overlap (untouched coordinates are copied)")
+    for name, t in (("idx", idx), ("val", val), ("off", off), ("weight", weight)):
+        if t.numel() and _overlaps(out[:P], t):
+            raise RuntimeError(f"{fn}: out and {name} overlap")
+    if base.data_ptr() % 16 != 0 or out.data_ptr() % 16 != 0:
+        raise RuntimeError(f"{fn}: base and out must be 16-byte aligned")
+    for t in (base, idx, val, off, weight, out):
+        _ptr(t)  # no CPU path
+    has = idx.numel() > 0  # an empty tensor's pointer means nothing: hand the library null
+    _check(lib().dls_sparse_fedavg_f32(_ptr(base), _ptr(idx) if has else None,
+                                       _ptr(val) if has else None, _ptr(off), _ptr(weight), K,
+                                       total, P, _ptr(out), _stream(stream, base)),
+           "dls_sparse_fedavg_f32")
     return out
 
 

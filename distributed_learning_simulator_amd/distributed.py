@@ -442,6 +442,10 @@ def get_sharded_server(algorithm, **kwargs):
     table = {"fed": ShardedFedServer, "fed_quant": ShardedFedQuantServer,
              "sign_SGD": ShardedSignSGDServer, "GTG_shapley_value": ShardedGTGShapleyValueServer,
              "multiround_shapley_value": ShardedMultiRoundShapleyValueServer}
+    if algorithm == "fed_topk":
+        raise RuntimeError("fed_topk runs on the one-process server only (factory.get_server("
+                           "'fed_topk', sharded=False, ...)): a sharded server over sparse "
+                           "payloads is not implemented")
     if algorithm not in table:
         raise RuntimeError("unknown algorithm:" + algorithm)
     return table[algorithm](**kwargs)

@@ -262,8 +262,7 @@ class FedServer(Server):
         self.attack_scale = float(attack_scale)
         self.last_attack = {}
         self.parameters: ClientParameters = ClientParameters(self._make_store)
-        self.__prev_model = copy.deepcopy(
-            ModelUtil(self.tester.model).get_parameter_dict()) if self.tester is not None else {}
+        self.__prev_model = self._initial_model()
         self.worker_data_queue.put_result(
             RepeatedResult(data=self.prev_model, num=self.clients_per_round))
 
@@ -413,6 +412,11 @@ class FedServer(Server):
                              f"server_momentum={beta1} and server_beta2={server_beta2} below 1 "
                              "when rounded to fp32")
         return lr, beta1, float(server_beta2), float(server_tau)
+
+    def _initial_model(self):
+        """The model the first round starts from: the tester's; none without a tester."""
+        return copy.deepcopy(
+            ModelUtil(self.tester.model).get_parameter_dict()) if self.tester is not None else {}
 
     @property
     def clients_per_round(self):

@@ -1,0 +1,128 @@
+"""Top-k sparsified FedAvg server ("sparsified SGD with memory", Stich, Cordonnier & Jaggi
+2018; Aji & Heafield 2017; Lin et al. 2018).
+
+Client payloads are ``SparseUpdate(idx, val, P)``: the k largest-magnitude coordinates of
+the client's update, a difference to the model this server broadcast.  The server holds the
+round's sparse payloads as they are, 8 * k bytes per client and never a dense client row,
+and when all have arrived one ``dls_sparse_fedavg_f32`` launch adds their FedAvg (the
+reference's chain fl(fl(v * n_i) / N) in arrival order, over the clients that sent the
+coordinate) to the previous global model.  The rest of the round is FedServer's; the
+downlink stays dense, as in the literature.
+"""
+import copy
+import logging
+
+import torch
+
+from .. import _native
+from ..layout import ParameterLayout
+from ..task_queue import RepeatedResult
+from ..workers.fed_topk_worker import SparseUpdate
+from .fed_server import FedServer
+
+log = logging.getLogger("distributed_learning_simulator_amd")
+
+
+class FedTopKServer(FedServer):
+    """``initial_model``: the parameter dict the first round starts from (default: the
+    tester's model); one of ``tester`` and ``initial_model`` is needed, because the
+    workers' updates are differences to the broadcast model.
+
+    ``payload_counts`` holds, per round, the number of entries each worker sent.
+
+    ``aggregation_rule`` other than "mean", ``attack`` and ``server_optimizer`` raise
+    ``ValueError``: composing sparsification with them is out of scope here."""
+
+    _robust_unsupported = "it holds the clients' sparse updates, not fp32 rows"
+    _attack_unsupported = "it holds the clients' sparse updates, not fp32 rows"
+    _server_opt_unsupported = "it holds the clients' sparse updates, not fp32 rows"
+
+    def __init__(self, initial_model=None, **kwargs):
+        if kwargs.get("tester") is None and not initial_model:
+            raise ValueError("FedTopKServer needs a model to start from, a tester or "
+                             "initial_model=: the workers' updates are differences to the "
+                             "broadcast model")
+        if kwargs.get("aggregation_mode", "exact") != "exact":
+            raise ValueError("FedTopKServer has one arithmetic (aggregation_mode='exact'), not "
+                             f"{kwargs['aggregation_mode']!r}")
+        self.__initial = initial_model
+        self._payloads = {}  # worker id -> (n, SparseUpdate), in arrival order
+        self.payload_counts = []  # per round: worker id -> entries it sent
+        super().__init__(**kwargs)
+        self.layout = ParameterLayout.from_dict(self.prev_model)
+
+    def _initial_model(self):
+        if self.__initial:
+            return {k: v.detach().clone().to(self.device) for k, v in self.__initial.items()}
+        return super()._initial_model()
+
+    def _check_payload(self, worker_id, payload):
+        who = f"worker {worker_id}"
+        if not isinstance(payload, SparseUpdate):
+            raise ValueError(f"{who}: the payload must be a SparseUpdate, not "
+                             f"{type(payload).__name__}")
+        P = self.layout.P
+        if payload.P != P:
+            raise ValueError(f"{who}: the payload is over rows of P={payload.P} elements, the "
+                             f"server's model has P={P}")
+        idx, val = payload.idx, payload.val
+        if not torch.is_tensor(idx) or idx.dtype != torch.int32 or idx.dim() != 1:
+            raise ValueError(f"{who}: idx must be an int32 vector")
+        if not torch.is_tensor(val) or val.dtype != torch.float32 or val.dim() != 1 \
+                or val.numel() != idx.numel():
+            raise ValueError(f"{who}: val must be an fp32 vector as long as idx "
+                             f"({idx.numel()} elements)")
+        if idx.numel():
+            bad = torch.stack([(idx[1:] <= idx[:-1]).any(), idx[0] < 0, idx[-1] >= P]).tolist()
+            if bad[0]:
+                raise ValueError(f"{who}: idx must be strictly ascending (no duplicates)")
+            if bad[1] or bad[2]:
+                raise ValueError(f"{who}: idx must lie in 0..P-1 = {P - 1}")
+        return SparseUpdate(idx.contiguous().to(self.device), val.contiguous().to(self.device), P)
+
+    def _sparse_flat(self, ids):
+        """prev_model + the sparse FedAvg of the clients ``ids``, in that order, as a flat row."""
+        ns = [int(self._payloads[i][0]) for i in ids]
+        ups = [self._payloads[i][1] for i in ids]
+        dev = self.device
+        off = [0]
+        for u in ups:
+            off.append(off[-1] + len(u))
+        idx = torch.cat([u.idx for u in ups])
+        val = torch.cat([u.val for u in ups])
+        base = self.layout.flatten(self.prev_model, device=dev)
+        out = torch.empty(self.layout.P, dtype=torch.float32, device=dev)
+        return _native.sparse_fedavg(base, idx, val, torch.tensor(off, dtype=torch.int64).to(dev),
+                                     torch.tensor(ns, dtype=torch.float32).to(dev),
+                                     float(sum(ns)), self.layout.P, out)
+
+    def get_subset_model(self, client_subset):
+        """The model the subset's updates alone would have given, in the subset's order
+        (empty subset -> previous model)."""
+        ids = list(client_subset)
+        if not ids:
+            return self.prev_model
+        missing = [i for i in ids if i not in self._payloads]
+        if missing:
+            raise ValueError(f"workers {missing} sent no update this round")
+        return self.layout.views(self._sparse_flat(ids))
+
+    def _process_worker_data(self, data, __):
+        worker_id, training_dataset_size, payload = data
+        self._payloads[worker_id] = (training_dataset_size, self._check_payload(worker_id, payload))
+        if len(self._payloads) != self.clients_per_round:
+            log.debug("%s %s,skip", len(self._payloads), self.clients_per_round)
+            return None
+        self.round += 1
+        log.info("begin aggregating")
+        self.payload_counts.append({w: len(u) for w, (_, u) in self._payloads.items()})
+        sent = sum(u.nbytes for _, u in self._payloads.values())
+        dense = 4 * self.layout.numel * len(self._payloads)
+        log.info("round %s: uplink %s bytes against %s dense, ratio %s", self.round, sent, dense,
+                 float(sent) / float(dense))
+        data = self._process_aggregated_parameter(self.get_subset_model(self._payloads.keys()))
+        self._set_prev_model(copy.deepcopy(data))
+        acc = self.get_metric(self.prev_model)
+        log.info("end aggregating, test accuracy is %s", acc)
+        self._payloads.clear()
+        return RepeatedResult(data=data, num=self.clients_per_round)

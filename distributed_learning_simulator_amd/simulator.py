@@ -16,6 +16,8 @@
         [--attack alie --attackers 3,7 [--attack_z 1.0] |
          --attack ipm --attackers 3,7 [--attack_eps 0.1] |
          --attack sign_flip --attackers 3,7 [--attack_scale 1.0]]
+    python -m distributed_learning_simulator_amd.simulator --distributed_algorithm fed_topk \\
+        --worker_number 10 --round 5 [--topk_ratio 0.01] [--topk_error_feedback 1]
 
 Same flags and flow as the reference: IID split of the training set over the
 workers (:48-50), a tester on the test split (:51), ``factory.get_server``
@@ -39,6 +41,7 @@ from .servers.fed_server import (ATTACK_DEFAULTS, DEFAULTS, RULES, SERVER_OPT_DE
                                  SERVER_OPTIMIZERS)
 from .trainer import Inferencer, Trainer
 
+TOPK_DEFAULTS = {"topk_ratio": 0.01, "topk_error_feedback": 1}
 DATASETS = {"MNIST": (1, 32, 32), "CIFAR10": (3, 32, 32)}
 
 
@@ -116,7 +119,20 @@ def get_config(argv=None):
     ap.add_argument("--server_optimizer", type=str, default=None, choices=SERVER_OPTIMIZERS)
     for name in SERVER_OPT_DEFAULTS:
         ap.add_argument("--" + name, type=float, default=None)
+    # fed_topk: every worker sends the ceil(--topk_ratio x parameters) largest-magnitude
+    # coordinates of its update and keeps the rest in a residual that is added back next
+    # round (--topk_error_feedback 0: the residual is dropped, plain top-k)
+    ap.add_argument("--topk_ratio", type=float, default=None)
+    ap.add_argument("--topk_error_feedback", type=int, default=None, choices=(0, 1))
     config = ap.parse_args(argv)
+    if config.distributed_algorithm != "fed_topk" and (
+            config.topk_ratio is not None or config.topk_error_feedback is not None):
+        ap.error("--topk_ratio and --topk_error_feedback apply to --distributed_algorithm "
+                 "fed_topk alone")
+    if config.topk_ratio is None:
+        config.topk_ratio = TOPK_DEFAULTS["topk_ratio"]
+    if config.topk_error_feedback is None:
+        config.topk_error_feedback = TOPK_DEFAULTS["topk_error_feedback"]
     if config.distributed_algorithm == "sign_SGD" and any(
             getattr(config, name) is not None
             for name in ("server_optimizer",) + tuple(SERVER_OPT_DEFAULTS)):
@@ -170,6 +186,16 @@ def server_kwargs(config):
     return kwargs
 
 
+def worker_kwargs(config):
+    """The keyword arguments run() passes to factory.get_worker beside trainer / queue /
+    round / worker_id: the sparsifier's for fed_topk, none for the other algorithms."""
+    if config.distributed_algorithm != "fed_topk":
+        return {}
+    return {"topk_ratio": getattr(config, "topk_ratio", TOPK_DEFAULTS["topk_ratio"]),
+            "error_feedback": bool(getattr(config, "topk_error_feedback",
+                                           TOPK_DEFAULTS["topk_error_feedback"]))}
+
+
 def get_cuda_devices():
     return [torch.device("cuda", i) for i in range(torch.cuda.device_count())]
 
@@ -215,7 +241,7 @@ def run(config, devices=None, sharded=None):
                               seed=config.seed + worker_id)
             worker = get_worker(config.distributed_algorithm, trainer=trainer,
                                 worker_data_queue=server.worker_data_queue, round=config.round,
-                                worker_id=worker_id)
+                                worker_id=worker_id, **worker_kwargs(config))
             worker.train(device=device)
         except BaseException as e:  # surfaced after join
             errors.append(e)

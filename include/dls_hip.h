@@ -765,6 +765,63 @@ int dls_lenet5_eval_loss_f32(const float *models, int64_t ldm, int32_t S, const 
 int dls_sum_rows_f64(const float *v, int64_t ldn, int32_t S, int64_t n, double *out,
                      dls_stream_t stream);
 
+/* Top-k sparsification with error feedback ("sparsified SGD with memory", Stich,
+ * Cordonnier & Jaggi 2018; Aji & Heafield 2017; Lin et al. 2018; csrc/topk.hip).  The
+ * reference simulator has no sparsifier, so there is no reference hook to cite: the
+ * definitions below are this library's and tests/topk_ref.py restates them in numpy.
+ *
+ * The client's compressor.  All pointers are device memory the caller owns; nothing is
+ * allocated and no pointer is kept.  In fp32, one rounding per operation:
+ *   u[j]   = fl(fl(w[j] - base[j]) + e[j])          j in 0..P-1 (e: the residual, zero
+ *                                                   before the first round)
+ *   key[j] = bits(u[j]) & 0x7fffffff, compared as an unsigned integer: +x and -x tie,
+ *            -0.0 ties with +0.0, infinities and NaNs carry the largest keys
+ *   selected: exactly k coordinates, those with the k largest keys; among the
+ *            coordinates whose key equals the k-th largest key the lowest indices win,
+ *            so the selection is a function of u alone
+ *   idx[0..k) the selected coordinates, strictly ascending; val[i] = u[idx[i]], the
+ *            same bits (sign of zero included)
+ *   e[j]   = +0.0 where j is selected, u[j] elsewhere (in place): for every j exactly
+ *            one of the sent value and the new residual holds u[j] bit for bit
+ *   stats[0] = k; stats[1] = #{j : u[j] is not finite} (the call completes with the
+ *            outputs the key order defines; the caller decides)
+ * Where the arithmetic gives NaN, u[j] is some NaN (the same one in val or e).
+ * 1 <= k <= P < 2^31 (DLS_EINVAL); P a multiple of 4 and w, base, e, val, idx, workspace
+ * 16-byte aligned (DLS_ELAYOUT); e must not overlap w or base (DLS_EINVAL); all checked
+ * before any device call.  workspace: the number of bytes the query below returns for P
+ * (negative: the status of a bad P); it may hold anything on entry.
+ * One launch sequence on the stream (a memset and nine kernels: a radix select on the
+ * key, digits of 11 + 10 + 10 bits, the threshold staying on the device, then a count
+ * per 4096-coordinate chunk, a scan and an ordered write), five passes over P-sized
+ * arrays, nothing synchronised inside the call.  Integer histogram counts use LDS and
+ * global integer atomics (order-independent sums); every output position comes from
+ * the scans; there are no floating-point atomics: the outputs do not depend on the
+ * stream, the grid or the scheduling. */
+int64_t dls_topk_workspace(int64_t P);
+int dls_topk_compress_f32(const float *w, const float *base, float *e, int64_t P, int64_t k,
+                          int32_t *idx, float *val, int32_t *stats, void *workspace,
+                          dls_stream_t stream);
+/* The server's side: FedAvg over sparse client updates, added to the model the clients
+ * started from.  Client i, in the given order, holds the pairs idx / val[off[i] ..
+ * off[i+1]) (off int64 [K+1], ascending); its indices are strictly ascending and lie in
+ * 0..P-1; a segment may be empty (idx and val may both be null when all are).
+ * weight[i] = fl32(n_i) and total = fl32(sum of the n_i), as dls_fedavg_f32 takes them.
+ * Per coordinate c:
+ *   no client sent c:  out[c] = base[c], the same bits (copied, so -0.0 survives)
+ *   otherwise:         acc = the reference FedAvg chain (servers/fed_server.py:44-66)
+ *                      over the clients that sent c, in client order: the first assigns
+ *                      fl(fl(v * n_i) / N), the later ones add theirs with fp32 +;
+ *                      out[c] = fl(base[c] + acc)
+ * with the correctly rounded division of DLS_FEDAVG_EXACT.  K >= 1, 1 <= P < 2^31
+ * (DLS_EINVAL); P a multiple of 4, base and out 16-byte aligned (DLS_ELAYOUT); out must
+ * not overlap base (DLS_EINVAL).  An entry whose index falls outside the range its
+ * position implies (indices not ascending) is skipped, never written out of bounds.
+ * One launch; one wave per 2048 coordinates accumulates them in LDS, client after
+ * client; no atomics: the same bits on every run and for any launch geometry. */
+int dls_sparse_fedavg_f32(const float *base, const int32_t *idx, const float *val,
+                          const int64_t *off, const float *weight, int32_t K, float total,
+                          int64_t P, float *out, dls_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
