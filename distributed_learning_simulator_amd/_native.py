@@ -87,6 +87,8 @@ SIGNATURES = {
     "dls_sign_vote_count": ([_p, _i64, _p, _i32, _i64, _p, _p], _i32),
     "dls_sign_from_counts": ([_p, _i64, _p, _p, _p], _i32),
     "dls_sign_vote": ([_p, _i64, _p, _i32, _i64, _p, _p, _p, _p], _i32),
+    "dls_sign_vote_geometry": ([_i64, _i32, _i32, _p, _p, _p], _i32),
+    "dls_sign_vote_wave_ranges": ([_i64, _i32, _i32, _i64, _i64, _p, _p], _i32),
     "dls_sign_sgd_direction": ([_p, _p, _i64, _f32, _f32, _i32, _i32, _p, _p, _p], _i32),
     "dls_sign_sgd_apply": ([_p, _p, _i64, _f32, _f32, _p], _i32),
     "dls_dequant_fedavg": ([_p, _i32, _p, _p, _i64, _p, _i64, _p, _i64, _i64, _p, _p, _i32, _f32,
@@ -170,7 +172,7 @@ def _stream(stream=None, like=None):
 
 CSRC_HASHED = ["dls_runtime.hip", "fedavg.hip", "sign.hip", "quant.hip", "quant_fma.hip", "shapley.hip",
                "infer.hip", "conv.hip", "lenet.hip", "loss.hip", "robust.hip", "pairdist.hip", "weiszfeld.hip", "gram.hip", "serveropt.hip", "topk.hip", "dls_common.h", "quant_common.h",
-               "loss_common.h", os.path.join("..", "..", "include", "dls_hip.h")]
+               "loss_common.h", "sign_geometry.h", os.path.join("..", "..", "include", "dls_hip.h")]
 
 
 def source_hash():
@@ -1065,6 +1067,33 @@ def conv_stem_kernel_choice(B, C, H, W, Cout, ksize, stride, pad):
     negative status it would fail with (dls_conv_stem_kernel_choice: host only)."""
     kh, kw = ksize
     return int(lib().dls_conv_stem_kernel_choice(B, C, H, W, Cout, kh, kw, stride, pad))
+
+
+def sign_vote_geometry(P, K, cus=0):
+    """(nwaves, G, waves per block) of the sign_vote / sign_vote_count launch for P
+    parameters and K client rows on a part with ``cus`` compute units (0: the current
+    device; an explicit count needs no GPU): nwaves waves each own a contiguous
+    range of at most 64 G vote groups of 64 parameters (dls_sign_vote_geometry,
+    host only; the launch runs the same function)."""
+    nwaves, G, wpb = ctypes.c_int64(), ctypes.c_int32(), ctypes.c_int32()
+    _check(lib().dls_sign_vote_geometry(int(P), int(K), int(cus), ctypes.byref(nwaves),
+                                        ctypes.byref(G), ctypes.byref(wpb)),
+           "dls_sign_vote_geometry")
+    return nwaves.value, G.value, wpb.value
+
+
+def sign_vote_wave_ranges(P, K, cus=0, first_wave=0, count=None):
+    """The vote-group ranges [wlo, whi) of ``count`` waves from ``first_wave`` (default:
+    all of them) as two int64 numpy arrays, from the range function k_sign_vote itself
+    calls (dls_sign_vote_wave_ranges, host only)."""
+    import numpy as np
+    if count is None:
+        count = sign_vote_geometry(P, K, cus)[0] - first_wave
+    wlo, whi = np.empty(count, np.int64), np.empty(count, np.int64)
+    _check(lib().dls_sign_vote_wave_ranges(int(P), int(K), int(cus), int(first_wave), int(count),
+                                           wlo.ctypes.data, whi.ctypes.data),
+           "dls_sign_vote_wave_ranges")
+    return wlo, whi
 
 
 def conv_pack_input(x, stream=None):

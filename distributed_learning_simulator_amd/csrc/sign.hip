@@ -11,6 +11,7 @@
 // per plane word and no per-parameter unpacking; the counters are unpacked
 // once at the end.  Exact in any order.
 #include "dls_common.h"
+#include "sign_geometry.h"
 
 namespace dls {
 namespace {
@@ -187,7 +188,6 @@ constexpr int kVoteWPBMax = 4;  // waves per block
 constexpr int kVoteWPC = DLS_VOTE_WPC;  // waves per CU on large models (0: 256 groups per wave)
 constexpr int kVoteWPB = DLS_VOTE_WPB;
 static_assert(kVoteWPB >= 1 && kVoteWPB <= kVoteWPBMax, "DLS_VOTE_WPB");
-constexpr int kVoteG = 4;    // widest G (registers: single-buffered 8-client batches)
 constexpr int kVoteDbG = 1;  // widest G whose 8-client batches are double-buffered
 
 // LDS is per wave and the epilogue trip counts differ between the waves of a
@@ -304,18 +304,14 @@ __global__ __launch_bounds__(64 * kVoteWPBMax) void k_sign_vote(
     // the last 256-parameter tile (vote 0)
     const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (wave >= nwaves) return;  // wave-uniform
-    // nwaves near-equal ranges (sizes differ by at most one group; with G > 1, by
-    // up to 8: every range starts on a multiple of 8 groups = 128 bytes, so on rows
-    // whose pitch is a multiple of 128 bytes (_native.sign_row_pitch) no line is
-    // fetched by two waves: HBM reads 1.028 -> 1.016 x the algorithmic bytes even
-    // with the 64-byte pitch, -1.2 % time, profiles/r06_sign_vote_pmc.txt; the host
-    // sizes G for ranges up to 7 groups longer)
-    int64_t wlo = wave * vote_groups / nwaves;
-    int64_t whi = (wave + 1) * vote_groups / nwaves;
-    if (G > 1) {
-        wlo &= ~(int64_t)7;
-        whi = wave + 1 == nwaves ? vote_groups : whi & ~(int64_t)7;
-    }
+    // nwaves near-equal ranges (vote_wave_range; with G > 1 every range starts on a
+    // multiple of 8 groups = 128 bytes, so on rows whose pitch is a multiple of 128
+    // bytes (_native.sign_row_pitch) no line is fetched by two waves: HBM reads
+    // 1.028 -> 1.016 x the algorithmic bytes even with the 64-byte pitch, -1.2 %
+    // time, profiles/r06_sign_vote_pmc.txt; vote_geometry sizes G for ranges up to
+    // 7 groups longer, so whi - wlo <= 64 G)
+    int64_t wlo, whi;
+    vote_wave_range(wave, vote_groups, nwaves, G, wlo, whi);
     const int64_t gend = min(whi, ngroups);
     HSCounter<CB> cpa[G], cna[G];
     uint64_t nana[G];
@@ -526,35 +522,17 @@ int launch_vote(const uint64_t *planes, int64_t ldp, const int32_t *rows, int K,
                 int32_t *counts, float *sign_out, uint64_t *vote_planes, hipStream_t st) {
     const int64_t ngroups = (P + 63) / 64;
     const int64_t vote_groups = DLS_SIGN_WORDS(P) / 2;  // whole 256-parameter tiles
-    // Large models: kVoteWPC waves per CU, each a contiguous range of R groups,
-    // 2-4 groups per lane (each wave streams R x 16 B of every client row:
-    // multi-KB pieces measured 12 % faster than 1 KB at P = 11.2M).  Small
-    // models: R = 64, 1 group per lane, double-buffered batches.
-    int64_t nwaves = (vote_groups + 63) / 64;
-    int G = 1, wpb = 1;
-    if (CB <= 12) {
-        if (kVoteWPC > 0) {
-            // exactly kVoteWPC waves per CU, near-equal ranges of up to 64 G groups
-            int64_t waves = (int64_t)kVoteWPC * device_cus();
-            int64_t r = (vote_groups + waves - 1) / waves + 7;  // + the range alignment
-            if (r > 64 * kVoteG) {
-                // models past 64 kVoteG groups per wave (P > ~16.7M on 256 CUs, e.g.
-                // VGG-16): a multiple of kVoteWPC waves per CU, so that every wave
-                // keeps the wide layout (G = kVoteG at most) instead of G = 1
-                waves *= (r + 64 * kVoteG - 1) / (64 * kVoteG);
-                r = (vote_groups + waves - 1) / waves + 7;
-            }
-            if (r > 64) {
-                nwaves = waves;
-                G = (int)((r + 63) / 64);
-                wpb = kVoteWPB;
-            }
-        } else if ((vote_groups + 64 * kVoteG - 1) / (64 * kVoteG) >= 512) {
-            // the round-3 form: 256 groups per wave, one wave per block
-            nwaves = (vote_groups + 64 * kVoteG - 1) / (64 * kVoteG);
-            G = kVoteG;
-        }
-    }
+    // nwaves, G and waves per block: vote_geometry (sign_geometry.h), the function
+    // dls_sign_vote_geometry reports; every wave's range is at most 64 G <= 64
+    // kVoteG groups long
+    const VoteGeometry geo = vote_geometry(vote_groups, CB <= 12 ? device_cus() : 0, CB > 12,
+                                           kVoteWPC, kVoteWPB);
+    const int64_t nwaves = geo.nwaves;
+    const int G = geo.G, wpb = geo.wpb;
+    DLS_REQUIRE(G >= 1 && G <= (CB > 12 ? 1 : kVoteG) && nwaves >= 1 && wpb >= 1 && wpb <= kVoteWPBMax,
+                DLS_EINVAL, "dls_sign_vote: no kernel for %d groups per lane (1..%d), %lld waves, "
+                "%d waves per block (P=%lld)", G, CB > 12 ? 1 : kVoteG, (long long)nwaves, wpb,
+                (long long)P);
     const dim3 grid((unsigned)((nwaves + wpb - 1) / wpb));
     const size_t lds = (size_t)wpb * (counts ? 2 * (CB + 3) + 1 : 3) * 64 * sizeof(uint64_t);
 #define DLS_VOTE_LAUNCH(C_, G_)                                                                  \
@@ -565,7 +543,8 @@ int launch_vote(const uint64_t *planes, int64_t ldp, const int32_t *rows, int K,
         case 1: DLS_VOTE_LAUNCH(C_, 1); break; \
         case 2: DLS_VOTE_LAUNCH(C_, 2); break; \
         case 3: DLS_VOTE_LAUNCH(C_, 3); break; \
-        default: DLS_VOTE_LAUNCH(C_, 4); break; \
+        case 4: DLS_VOTE_LAUNCH(C_, 4); break; \
+        default: break; /* unreachable: 1 <= G <= kVoteG was required above */ \
     }
     if constexpr (CB > 12) {  // wide counters: 1 group per lane only (registers)
         if (counts) DLS_VOTE_LAUNCH(true, 1);
@@ -582,16 +561,29 @@ int launch_vote(const uint64_t *planes, int64_t ldp, const int32_t *rows, int K,
     return check_launch("dls_sign_vote");
 }
 
+// The counter width class of K clients: counts reach 8*c + 7 with c <= ceil(K/8) < 2^CB
+// (fewer bits = fewer ops/registers); 0 past 2^20 - 1 clients.
+int vote_counter_bits(int32_t K) {
+    const int64_t c_max = ((int64_t)K + 7) / 8;
+    if (c_max < (1 << 2)) return 2;
+    if (c_max < (1 << 4)) return 4;
+    if (c_max < (1 << 6)) return 6;
+    if (c_max < (1 << 8)) return 8;
+    if (c_max < (1 << 12)) return 12;
+    return K < (1 << 20) ? 16 : 0;
+}
+
 int vote_dispatch(const uint64_t *planes, int64_t ldp, const int32_t *rows, int32_t K, int64_t P,
                   int32_t *counts, float *sign_out, uint64_t *vote_planes, hipStream_t st) {
-    // counts reach 8*c + 7 with c <= ceil(K/8) < 2^CB (fewer bits = fewer ops/registers)
-    const int64_t c_max = (K + 7) / 8;
-    if (c_max < (1 << 2)) return launch_vote<2>(planes, ldp, rows, K, P, counts, sign_out, vote_planes, st);
-    if (c_max < (1 << 4)) return launch_vote<4>(planes, ldp, rows, K, P, counts, sign_out, vote_planes, st);
-    if (c_max < (1 << 6)) return launch_vote<6>(planes, ldp, rows, K, P, counts, sign_out, vote_planes, st);
-    if (c_max < (1 << 8)) return launch_vote<8>(planes, ldp, rows, K, P, counts, sign_out, vote_planes, st);
-    if (c_max < (1 << 12)) return launch_vote<12>(planes, ldp, rows, K, P, counts, sign_out, vote_planes, st);
-    if (K < (1 << 20)) return launch_vote<16>(planes, ldp, rows, K, P, counts, sign_out, vote_planes, st);
+    switch (vote_counter_bits(K)) {
+    case 2: return launch_vote<2>(planes, ldp, rows, K, P, counts, sign_out, vote_planes, st);
+    case 4: return launch_vote<4>(planes, ldp, rows, K, P, counts, sign_out, vote_planes, st);
+    case 6: return launch_vote<6>(planes, ldp, rows, K, P, counts, sign_out, vote_planes, st);
+    case 8: return launch_vote<8>(planes, ldp, rows, K, P, counts, sign_out, vote_planes, st);
+    case 12: return launch_vote<12>(planes, ldp, rows, K, P, counts, sign_out, vote_planes, st);
+    case 16: return launch_vote<16>(planes, ldp, rows, K, P, counts, sign_out, vote_planes, st);
+    default: break;
+    }
     set_error("dls_sign_vote: K=%d exceeds 2^20-1 clients", K);
     return DLS_EINVAL;
 }
@@ -642,6 +634,44 @@ extern "C" int dls_sign_vote(const uint64_t *planes, int64_t ldp, const int32_t 
                 (long long)P);
     return vote_dispatch(planes, ldp, rows, K, P, counts, sign_out, vote_planes,
                          as_stream(stream));
+}
+
+// The geometry of a (P, K) vote on `cus` compute units (<= 0: the current device),
+// through the functions launch_vote and k_sign_vote call.
+static int vote_geometry_of(const char *what, int64_t P, int32_t K, int32_t cus, int64_t &vote_groups,
+                            VoteGeometry &geo) {
+    DLS_REQUIRE(K > 0 && P > 0, DLS_EINVAL, "%s: K=%d P=%lld", what, K, (long long)P);
+    const int cb = vote_counter_bits(K);
+    DLS_REQUIRE(cb != 0, DLS_EINVAL, "%s: K=%d exceeds 2^20-1 clients", what, K);
+    vote_groups = DLS_SIGN_WORDS(P) / 2;
+    geo = vote_geometry(vote_groups, cb <= 12 ? (cus > 0 ? cus : device_cus()) : 0, cb > 12, kVoteWPC,
+                        kVoteWPB);
+    return DLS_OK;
+}
+
+extern "C" int dls_sign_vote_geometry(int64_t P, int32_t K, int32_t cus, int64_t *nwaves, int32_t *G,
+                                      int32_t *waves_per_block) {
+    int64_t vote_groups = 0;
+    VoteGeometry geo;
+    if (const int rc = vote_geometry_of("dls_sign_vote_geometry", P, K, cus, vote_groups, geo)) return rc;
+    if (nwaves) *nwaves = geo.nwaves;
+    if (G) *G = geo.G;
+    if (waves_per_block) *waves_per_block = geo.wpb;
+    return DLS_OK;
+}
+
+extern "C" int dls_sign_vote_wave_ranges(int64_t P, int32_t K, int32_t cus, int64_t first_wave,
+                                         int64_t count, int64_t *wlo, int64_t *whi) {
+    DLS_REQUIRE(wlo && whi, DLS_EINVAL, "dls_sign_vote_wave_ranges: null pointer");
+    int64_t vote_groups = 0;
+    VoteGeometry geo;
+    if (const int rc = vote_geometry_of("dls_sign_vote_wave_ranges", P, K, cus, vote_groups, geo)) return rc;
+    DLS_REQUIRE(first_wave >= 0 && count >= 0 && first_wave <= geo.nwaves - count, DLS_EINVAL,
+                "dls_sign_vote_wave_ranges: waves %lld..+%lld of %lld", (long long)first_wave,
+                (long long)count, (long long)geo.nwaves);
+    for (int64_t i = 0; i < count; ++i)
+        vote_wave_range(first_wave + i, vote_groups, geo.nwaves, geo.G, wlo[i], whi[i]);
+    return DLS_OK;
 }
 
 extern "C" int dls_sign_from_counts(const int32_t *counts, int64_t P, float *sign_out,

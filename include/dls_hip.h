@@ -454,6 +454,23 @@ int dls_sign_from_counts(const int32_t *counts, int64_t P, float *sign_out,
 int dls_sign_vote(const uint64_t *planes, int64_t ldp, const int32_t *rows, int32_t K, int64_t P,
                   int32_t *counts, float *sign_out, uint64_t *vote_planes, dls_stream_t stream);
 
+/* dls_sign_vote_geometry / dls_sign_vote_wave_ranges: host-only queries (no
+ * stream, no launch) of how dls_sign_vote and dls_sign_vote_count split a model
+ * of P parameters and K client rows over waves.  A vote group is 64 parameters;
+ * the vote walks DLS_SIGN_WORDS(P) / 2 of them.  *nwaves waves each own one
+ * contiguous range of groups, a lane owns *G of a range's groups (1..4), and
+ * *waves_per_block waves share a block; every range is at most 64 * *G groups
+ * long.  cus: the compute units to size the launch for; cus <= 0 asks the current
+ * device (the one call here that touches it).  The launch and the queries run
+ * the same functions (csrc/sign_geometry.h).  Null outputs are skipped.
+ * dls_sign_vote_wave_ranges writes the ranges [wlo[i], whi[i]) of the waves
+ * first_wave + i, i < count; together the ranges of waves 0..*nwaves-1 partition
+ * [0, DLS_SIGN_WORDS(P) / 2). */
+int dls_sign_vote_geometry(int64_t P, int32_t K, int32_t cus, int64_t *nwaves, int32_t *G,
+                           int32_t *waves_per_block);
+int dls_sign_vote_wave_ranges(int64_t P, int32_t K, int32_t cus, int64_t first_wave, int64_t count,
+                              int64_t *wlo, int64_t *whi);
+
 /* Worker step, workers/sign_sgd_worker.py:32-44 fused: momentum / dampening /
  * nesterov on grad (buf updated in place; first=1 clones), torch.sign, pack to
  * planes, optional fp32 sign copy.  a = fl32(1 - dampening).  Writes exactly

@@ -441,8 +441,11 @@ def test_vote_balanced_wave_ranges(P):
 def test_vote_wide_layout_very_large_model():
     """past 64 x 4 vote groups per wave (P > ~16.7M parameters on 256
     CUs; here P = 70M, VGG-16-scale) the vote keeps the wide per-wave layout with
-    a multiple of the waves per CU; the signs and packed vote equal torch's vote
-    computed from the same planes (bit unpacking on the GPU), on every parameter."""
+    a multiple m of the waves per CU, the smallest from ceil(r / 256) up for which
+    a range (ceil(groups / waves) + 7 for its aligned start) fits 64 x 4 groups:
+    5,120 waves of 4 groups per lane here on 256 CUs.  The signs and packed vote
+    equal torch's vote computed from the same planes (bit unpacking on the GPU), on
+    every parameter."""
     from distributed_learning_simulator_amd import _native
     K, P = 24, 70_000_000
     W = _native.sign_words(P)
@@ -466,3 +469,303 @@ def test_vote_wide_layout_very_large_model():
     s2 = torch.empty(P, device=dev)
     _native.sign_from_counts(counts.reshape(-1)[:P].contiguous(), P, s2, v2)
     assert torch.equal(vote, v2)
+
+
+# ------------------------------------------------------- the vote's wave ranges
+# launch_vote gives wave w of nwaves a contiguous range of vote groups (64 parameters
+# each) and every lane G of them (csrc/sign_geometry.h): a range longer than 64 G
+# groups leaves its tail unwritten.  Every size below comes from the geometry query on
+# this device's CU count, so the cases sit on the same edges on any part; the
+# outputs start as sentinels no vote can equal and carry a guard past P.
+SENT_SIGN, SENT_VOTE, SENT_COUNT = 7.0, 0x5555555555555555, -2 ** 31 + 1
+GUARD = 256
+EDGE_K = 13
+EDGE_ROWS = [12, 0, 2, 1, 5]  # 5 of the 13 rows, out of order: the tie's clients 0 and 1, the NaN's client 2
+
+
+def device_cus():
+    return torch.cuda.get_device_properties(dev).multi_processor_count
+
+
+def parent_vote_groups_per_lane(vote_groups, cus):
+    """G as launch_vote sized it before vote_geometry (narrow counters, 4 waves per CU,
+    at most 4 groups per lane): 5 in bands of sizes, which ran the G = 4 kernel."""
+    waves = 4 * cus
+    r = (vote_groups + waves - 1) // waves + 7
+    if r > 256:
+        waves *= (r + 255) // 256
+        r = (vote_groups + waves - 1) // waves + 7
+    return ((r + 63) // 64, waves) if r > 64 else (1, (vote_groups + 63) // 64)
+
+
+_edges = {}
+
+
+def vote_edges():
+    """Sizes (in 256-parameter tiles) on this device: the first and the last tile count
+    of the first band in which the old formula asked for G = 5, the tile count in the
+    band whose last range it made longest, and below the band the first tile count of
+    every new (nwaves, G) the geometry query reports."""
+    if _edges:
+        return _edges
+    from distributed_learning_simulator_amd import _native
+    cus = device_cus()
+    t = 1
+    while parent_vote_groups_per_lane(4 * t, cus)[0] != 5:
+        t += 1
+        assert t < 2048 * cus, "no band"
+    first = last = t
+    while parent_vote_groups_per_lane(4 * (last + 1), cus)[0] == 5:
+        last += 1
+
+    def parent_tail(t):  # groups past the 256 the G = 4 kernel's last wave covered
+        vg, nw = 4 * t, parent_vote_groups_per_lane(4 * t, cus)[1]
+        return vg - (((nw - 1) * vg // nw) & ~7) - 256
+
+    longest = max(range(first, last + 1), key=parent_tail)
+    assert parent_tail(longest) >= 4
+    _edges.update(band_first=first, band_last=last, band_longest=longest,
+                  parent_tail=parent_tail(longest), parent_tail_first=parent_tail(first),
+                  parent_tail_last=parent_tail(last))
+    prev, steps = _native.sign_vote_geometry(256, EDGE_K, cus)[:2], []
+    for t in range(2, first):
+        cur = _native.sign_vote_geometry(256 * t, EDGE_K, cus)[:2]
+        if cur != prev and (cur[1] > 1 or prev[1] > 1):  # G = 1: nwaves is ceil(groups / 64)
+            steps.append((t, prev, cur))
+        prev = cur
+    # 1 -> 2, 2 -> 3, 3 -> 4 groups per lane, the multiplier's first step (more waves,
+    # fewer groups per lane) and the next growth of G under it
+    kinds = {"g1_2": lambda p, c: (p[1], c[1]) == (1, 2), "g2_3": lambda p, c: (p[1], c[1]) == (2, 3) and p[0] == c[0],
+             "g3_4": lambda p, c: (p[1], c[1]) == (3, 4) and p[0] == c[0],
+             "multiplier": lambda p, c: c[0] == 2 * p[0] and p[1] == 4 and c[1] < 4}
+    for name, want in kinds.items():
+        _edges[name] = next(t for t, p, c in steps if want(p, c))
+    _edges["g_grows_after_multiplier"] = next(t for t, p, c in steps if t > _edges["multiplier"] and c[1] == p[1] + 1)
+    assert len(steps) == 5, steps  # nothing else changes below the band
+    return _edges
+
+
+def edge_case_inputs(P, K, pitch, seed):
+    """A ternary matrix S [K, P] on the GPU and its planes [K, pitch], with a tie and a
+    NaN code in the last live group, which lies in the last wave's last 64-group chunk:
+    the last parameter gets +1 from client 0, -1 from client 1 and 0 from the others
+    (one vote each way: a tie that is no sum of zeros); client 2 gets a NaN code (both
+    planes, by a plane edit) wherever it is positive in that group, at least on the
+    group's first parameter.  Returns S, planes, the NaN client and group."""
+    from distributed_learning_simulator_amd import _native
+    g = torch.Generator(device=dev).manual_seed(seed)
+    S = torch.randint(-1, 2, (K, P), generator=g, device=dev, dtype=torch.int8).float()
+    ng = (P + 63) // 64
+    S[:, P - 1] = 0
+    S[0, P - 1], S[1, P - 1] = 1, -1
+    S[2, 64 * (ng - 1)] = 1
+    planes = torch.full((K, pitch), SENT_VOTE, dtype=torch.int64, device=dev)
+    _native.sign_pack(S, P, planes)
+    planes[2, 2 * (ng - 1) + 1] |= planes[2, 2 * (ng - 1)]
+    # where they sit: in the last chunk of the last wave's range
+    nw, G, _ = _native.sign_vote_geometry(P, K)
+    wlo, whi = _native.sign_vote_wave_ranges(P, K, first_wave=nw - 1, count=1)
+    chunk = int(wlo[0]) + 64 * ((int(whi[0] - wlo[0]) + 63) // 64 - 1)
+    assert chunk <= ng - 1 < int(whi[0]) == _native.sign_words(P) // 2 and whi[0] - wlo[0] <= 64 * G
+    return S, planes, 2, ng - 1
+
+
+def edge_reference(S, rows, nan_client, nan_group):
+    """(counts, signs) of the vote over S's rows (all, or the list ``rows``) by torch's
+    sum of signs; a NaN code counts once each way and marks the parameter."""
+    from distributed_learning_simulator_amd import _native
+    P = S.shape[1]
+    total = (S if rows is None else S[rows]).sum(0)
+    times = 1 if rows is None else rows.count(nan_client)
+    nan = torch.zeros(P, dtype=torch.bool, device=dev)
+    sl = slice(64 * nan_group, min(64 * nan_group + 64, P))
+    if times:
+        nan[sl] = S[nan_client, sl] > 0
+        total[sl] -= times * nan[sl].float()
+        assert bool(nan.any())
+    counts = total.int() + nan.int() * _native.SIGN_NAN_MARK
+    return counts, torch.where(nan, torch.zeros((), device=dev), torch.sign(total))
+
+
+def check_edge_vote(planes, rows, K, P, ref_counts, ref_sign):
+    """dls_sign_vote_count (<CB, true, G>), the fused dls_sign_vote with counts and the
+    server's form without (<CB, false, G>): every parameter bit for bit, no sentinel left
+    in [0, P), no write into the guards."""
+    from distributed_learning_simulator_amd import _native
+    W = _native.sign_words(P)
+    ref_vote = gpu_pack_reference(ref_sign, W)
+    rows_t = None if rows is None else torch.tensor(rows, dtype=torch.int32, device=dev)
+
+    def outputs():
+        return (torch.full((P + GUARD,), SENT_COUNT, dtype=torch.int32, device=dev),
+                torch.full((P + GUARD,), SENT_SIGN, device=dev),
+                torch.full((W + GUARD,), SENT_VOTE, dtype=torch.int64, device=dev))
+
+    def check(counts=None, sign=None, vote=None):
+        if counts is not None:
+            assert int((counts[:P] == SENT_COUNT).sum()) == 0, "counts never written"
+            assert torch.equal(counts[:P], ref_counts)
+            assert bool((counts[P:] == SENT_COUNT).all()), "counts guard"
+        if sign is not None:
+            assert int((sign[:P] == SENT_SIGN).sum()) == 0, "signs never written"
+            assert torch.equal(sign[:P].view(torch.int32), ref_sign.view(torch.int32))
+            assert bool((sign[P:] == SENT_SIGN).all()), "sign guard"
+        if vote is not None:
+            assert int((vote[:W] == SENT_VOTE).sum()) == 0, "packed vote never written"
+            assert torch.equal(vote[:W], ref_vote)
+            assert bool((vote[W:] == SENT_VOTE).all()), "packed vote guard"
+
+    c, s, v = outputs()
+    _native.sign_vote_count(planes, rows_t, K, P, c[:P])
+    check(counts=c)
+    c, s, v = outputs()
+    _native.sign_vote(planes, rows_t, K, P, s[:P], counts=c[:P], vote_planes=v[:W])
+    check(c, s, v)
+    c, s, v = outputs()
+    _native.sign_vote(planes, rows_t, K, P, s[:P], vote_planes=v[:W])
+    check(None, s, v)
+    assert bool((c == SENT_COUNT).all())
+    return s[:P], v[:W]
+
+
+def run_edge_case(P, pitch=None):
+    from distributed_learning_simulator_amd import _native
+    S, planes, nan_client, nan_group = edge_case_inputs(
+        P, EDGE_K, _native.sign_words(P) if pitch is None else pitch, P % 9973)
+    out = None
+    for rows in (None, EDGE_ROWS):
+        K = EDGE_K if rows is None else len(rows)
+        ref_counts, ref_sign = edge_reference(S, rows, nan_client, nan_group)
+        assert int(ref_counts[P - 1]) == 0 and float(ref_sign[P - 1]) == 0  # the tie
+        got = check_edge_vote(planes, rows, K, P, ref_counts, ref_sign)
+        out = out or got
+    return out
+
+
+@pytest.mark.parametrize("where", ["first", "last", "ragged"])
+def test_vote_wave_ranges_in_the_old_g5_band(where):
+    """The sizes at which the host used to ask for 5 groups per lane and launch 4 (about
+    32.6M-33.1M parameters on 256 CUs): the band's first and last size, and the one
+    whose last range was longest, cut to P % 256 = 68 so that the last wave's last
+    chunk holds live groups, padding groups and groups past the end.  The old launch
+    dropped groups only where its last wave's range, not just the host's bound on it,
+    passed 256 groups: at the "ragged" size (4 groups, asserted; the tie and the NaN
+    code sit in them), but not at the band's first and last size on 64 to 304 CUs,
+    where its last range is 252 and 256 groups (these two pin the fixed geometry at
+    the band's edges; they passed before)."""
+    from distributed_learning_simulator_amd import _native
+    e = vote_edges()
+    P = 256 * {"first": e["band_first"], "last": e["band_last"], "ragged": e["band_longest"]}[where]
+    if e["band_first"] * 256 == 32_637_184:  # 256 CUs: what the docstring says of them
+        assert (e["parent_tail_first"], e["parent_tail_last"]) == (-4, 0)
+    if where == "ragged":
+        P -= 188  # 2 of the last tile's 4 groups are live, the last one 4 parameters long
+        assert e["parent_tail"] >= 4 and (P + 63) // 64 == _native.sign_words(P) // 2 - 2
+    nw, G, wpb = _native.sign_vote_geometry(P, EDGE_K)
+    assert 2 <= G <= 4 and wpb == 4 and nw % (4 * device_cus()) == 0
+    run_edge_case(P)
+
+
+@pytest.mark.parametrize("side", ["below", "at"])
+@pytest.mark.parametrize("edge", ["g1_2", "g2_3", "g3_4", "multiplier", "g_grows_after_multiplier"])
+def test_vote_wave_ranges_at_every_geometry_step(edge, side):
+    """Both sides of every change of (nwaves, G) below the band: the first size of
+    2, 3 and 4 groups per lane, of the doubled wave count, and of the next G under
+    it, each with the size one 256-parameter tile below."""
+    from distributed_learning_simulator_amd import _native
+    t = vote_edges()[edge] - (side == "below")
+    below, at = (_native.sign_vote_geometry(256 * u, EDGE_K)[:2] for u in (vote_edges()[edge] - 1, vote_edges()[edge]))
+    assert below != at
+    run_edge_case(256 * t)
+
+
+def test_vote_wave_ranges_row_pitch():
+    """One band size with the rows at the minimal pitch sign_words(P) and at the
+    server's 128-byte pitch sign_row_pitch(P): the same signs and packed vote."""
+    from distributed_learning_simulator_amd import _native
+    P = 256 * vote_edges()["band_longest"] - 188 - 256  # sign_words(P) % 16 = 8: the pitches differ
+    if _native.sign_words(P) % 16 == 0:
+        P -= 256
+    assert _native.sign_row_pitch(P) == _native.sign_words(P) + 8
+    assert parent_vote_groups_per_lane(_native.sign_words(P) // 2, device_cus())[0] == 5
+    s1, v1 = run_edge_case(P)
+    s2, v2 = run_edge_case(P, pitch=_native.sign_row_pitch(P))
+    assert torch.equal(s1.view(torch.int32), s2.view(torch.int32)) and torch.equal(v1, v2)
+
+
+def test_vote_wave_ranges_wide_counters():
+    """CB = 16 (K = 32,761 client rows): one group per lane, one wave per block, and
+    more blocks than the wide layout launches (4 waves per CU in blocks of 4), the
+    last one partial.  32,761 rows are drawn from 48 base rows, so the sums are 48
+    weighted bit counts; without ``rows`` the matrix is written out."""
+    from distributed_learning_simulator_amd import _native
+    K, B = 32_761, 48
+    cus = device_cus()
+    # cus + 3 one-wave blocks is the smallest grid past the wide layout's cus blocks:
+    # P = 1,058,628 on 256 CUs, and the matrix written out below is K x sign_words(P)
+    # words = 8.7 GB there (a larger P would only add blocks like the middle ones)
+    P = 64 * (64 * (cus + 2) + 24) - 188
+    nw, G, wpb = _native.sign_vote_geometry(P, K)
+    assert (G, wpb) == (1, 1) and nw == cus + 3 and _native.sign_vote_geometry(P, EDGE_K)[1] == 1
+    W, ng = _native.sign_words(P), (P + 63) // 64
+    base = one_sided_planes(B, W, 5, 7)
+    base[:, 2 * ng:] = 0  # past P: zero, as the packer leaves it
+    base[:, 2 * (ng - 1):2 * ng] &= (1 << (P % 64)) - 1
+    base[9, 2 * (ng - 2) + 1] |= base[9, 2 * (ng - 2)]  # NaN codes in the last chunk
+    gen = torch.Generator(device=dev).manual_seed(3)
+    idx = torch.randint(0, B, (K,), generator=gen, device=dev)
+    idx[:B] = torch.arange(B, device=dev)
+    mult = torch.bincount(idx, minlength=B).int()
+    pos, neg = base[:, 0:2 * ng:2], base[:, 1:2 * ng:2]
+    cp = torch.empty((ng, 64), dtype=torch.int32, device=dev)
+    cn, nan = torch.empty_like(cp), torch.empty((ng, 64), dtype=torch.bool, device=dev)
+    for j in range(64):
+        cp[:, j] = (((pos >> j) & 1).int() * mult[:, None]).sum(0, dtype=torch.int32)
+        cn[:, j] = (((neg >> j) & 1).int() * mult[:, None]).sum(0, dtype=torch.int32)
+        nan[:, j] = ((((pos & neg) >> j) & 1) != 0).any(0)
+    cp, cn, nan = cp.reshape(-1)[:P], cn.reshape(-1)[:P], nan.reshape(-1)[:P]
+    assert int((cp - cn)[:64].min()) == K and int((cp - cn)[64:128].max()) == -K and bool(nan[-68:].any())
+    ref_counts = cp - cn + nan.int() * _native.SIGN_NAN_MARK
+    ref_sign = torch.where(nan, torch.zeros((), device=dev), torch.sign((cp - cn).float()))
+    check_edge_vote(base, idx.tolist(), K, P, ref_counts, ref_sign)
+    check_edge_vote(base[idx], None, K, P, ref_counts, ref_sign)
+
+
+def test_sign_server_votes_every_parameter_at_a_band_size(monkeypatch):
+    """SignSGDServer end to end with 8 workers at a band size: the path that hands the
+    kernel uninitialised outputs.  While the last client arrives and the vote runs,
+    torch.empty returns sentinel-filled tensors (its contents are arbitrary by
+    contract), so a parameter the kernel skips keeps a value no vote can have.  The
+    returned vote equals the oracle's majority vote on every parameter."""
+    from distributed_learning_simulator_amd.servers.sign_sgd_server import SignSGDServer
+    from distributed_learning_simulator_amd import _native
+    K = 8
+    P = 256 * vote_edges()["band_longest"]
+    n0 = P - 64 * 1000 - 61  # two tensors; the second starts on the next multiple of 64
+    shapes = [(n0,), (1000, 64)]
+    gen = torch.Generator(device=dev).manual_seed(8)
+    S = torch.randint(-1, 2, (K, P), generator=gen, device=dev, dtype=torch.int8).float()
+    S[:, n0:n0 + 61] = 0  # the layout's padding between the tensors
+    S[2:, P - 1] = 0
+    S[0, P - 1], S[1, P - 1] = 1, -1
+    server = SignSGDServer(tester=None, worker_number=K, synchronous=True, device=dev)
+    tasks = [[S[k, :n0].clone(), S[k, n0 + 61:].reshape(1000, 64).clone()] for k in range(K)]
+    for k in range(K - 1):
+        server.worker_data_queue.add_task(tasks[k])
+    real_empty, poisoned = torch.empty, []
+
+    def empty(*size, **kw):
+        t = real_empty(*size, **kw)
+        poisoned.append((tuple(t.shape), t.dtype))
+        return t.fill_(SENT_VOTE if t.dtype == torch.int64 else SENT_SIGN)
+
+    with monkeypatch.context() as m:
+        m.setattr(torch, "empty", empty)
+        server.worker_data_queue.add_task(tasks[K - 1])
+    assert ((P,), torch.float32) in poisoned and ((_native.sign_words(P),), torch.int64) in poisoned
+    res = server.worker_data_queue.get_result(consumer=0)
+    assert server._layout.P == P and [tuple(t.shape) for t in res] == shapes
+    got = torch.cat([res[0], torch.zeros(61, device=dev), res[1].reshape(-1)]).cpu().numpy()
+    ref = osign.majority_vote(S.cpu().numpy())
+    assert same_bits(got, ref)
+    assert np.array_equal(res.vote_planes.cpu().numpy().view(np.uint64), osign.pack_planes(ref))

@@ -11,8 +11,9 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "distributed_learning_simulator_amd", "csrc")
 OUT = os.path.join(ROOT, "tools", "_variants")
-SRCS = ["dls_runtime.hip", "fedavg.hip", "sign.hip", "quant.hip", "quant_fma.hip", "shapley.hip", "conv.hip",
-        "infer.hip"]
+with open(os.path.join(CSRC, "Makefile")) as _fh:  # the library's own source list
+    SRCS = next(line for line in _fh if line.startswith("SRCS :=")).split()[2:]
+HEADERS = ["dls_common.h", "quant_common.h", "loss_common.h", "sign_geometry.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off"]
 
 
@@ -52,7 +53,7 @@ def main(specs):
             src = os.path.join(tree, "pkg", "csrc")
             os.makedirs(src, exist_ok=True)
             os.makedirs(os.path.join(tree, "include"), exist_ok=True)
-            for f in SRCS + ["dls_common.h", "quant_common.h"]:
+            for f in SRCS + HEADERS:
                 try:
                     blob = subprocess.check_output(
                         ["git", "-C", ROOT, "show",
