@@ -148,57 +148,6 @@ __device__ __forceinline__ void accum16_pk(float (&acc)[16], u32x4 qv, f32x2 sz,
     }
 }
 
-// DLS_FEDAVG_FMA (zero point 0): acc = fma(q, c, acc), c = fl(fl(s * n_i) / N) of
-// the (client, channel): 2 conversions + 1 packed fma per element pair; cz.x
-// holds c (op_sel_hi reads it for both halves).  Two independent pairs per step.
-template <bool SEXT>
-__device__ __forceinline__ void accum16_fma(float (&acc)[16], u32x4 qv, f32x2 cz) {
-#pragma unroll
-    for (int j = 0; j < 8; j += 2) {
-        const int k = j & 3;
-        const f32x2 xa = f32x2{byte_val<SEXT>(qv[j >> 2], k), byte_val<SEXT>(qv[j >> 2], k + 1)};
-        const f32x2 xb = f32x2{byte_val<SEXT>(qv[(j >> 2) + 2], k),
-                               byte_val<SEXT>(qv[(j >> 2) + 2], k + 1)};
-        f32x2 ra = f32x2{acc[j], acc[j + 1]}, rb = f32x2{acc[j + 8], acc[j + 9]};
-        asm volatile(
-            "v_pk_fma_f32 %[ra], %[xa], %[cz], %[ra] op_sel_hi:[1,0,1]\n\t"
-            "v_pk_fma_f32 %[rb], %[xb], %[cz], %[rb] op_sel_hi:[1,0,1]"
-            : [ra] "+v"(ra), [rb] "+v"(rb)
-            : [xa] "v"(xa), [xb] "v"(xb), [cz] "v"(cz));
-        acc[j] = ra.x;
-        acc[j + 1] = ra.y;
-        acc[j + 8] = rb.x;
-        acc[j + 9] = rb.y;
-        // no later conversion is hoisted above this step (hoisting every in-flight
-        // client's conversions costs registers, and with them waves per SIMD)
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
-
-// FMA-mode constant of a (client, channel): fl(fl(s * n_i) / N) (IEEE division,
-// once per chunk and channel)
-__device__ __forceinline__ float fma_coef(float s, float wk, float N) { return (s * wk) / N; }
-
-// FMA mode: every lane-tile width in one launch (k_dequant_lanes_fma_any); 0: one
-// launch per width, the narrower ones on side streams (A/B knob)
-#ifndef DLS_QUANT_FMA_ANY
-#define DLS_QUANT_FMA_ANY 1
-#endif
-constexpr bool kQuantFmaAny = DLS_QUANT_FMA_ANY != 0;
-// FMA mode: groups 0-7 on the one-wave-per-SIMD kernel (quant_fma.hip); 0: the round-4
-// launches (k_dequant_fast_fma pieces + k_dequant_lanes_fma_any), an A/B knob
-#ifndef DLS_QUANT_FMA_STREAM
-#define DLS_QUANT_FMA_STREAM 1
-#endif
-constexpr bool kQuantFmaStream = DLS_QUANT_FMA_STREAM != 0;
-#ifndef DLS_QUANT_PIECE_WPS
-#define DLS_QUANT_PIECE_WPS 0  // > 0: the grouped kernels' launch pieces of this many waves per SIMD
-#endif
-constexpr int kQuantPieceWps = DLS_QUANT_PIECE_WPS;
-#ifndef DLS_QUANT_NTSTORE
-#define DLS_QUANT_NTSTORE 0  // 1: non-temporal output stores in store_tile (A/B knob)
-#endif
-
 template <int U, int GN>
 struct QBatch {
     u32x4 qv[U][GN];
@@ -532,9 +481,33 @@ __device__ __forceinline__ void store16(const WaveTile &wt, float (&acc)[16],
         o[v] = f32x4{acc[4 * v], acc[4 * v + 1], acc[4 * v + 2], acc[4 * v + 3]};
 }
 
-template <int G, bool EXT = false>
+// Write a wave tile's G slices of accumulators, transposed through LDS so that
+// each store instruction writes 1 KiB contiguous.
+template <int G>
 __device__ __forceinline__ void store_tile(const WaveTile &wt, float (&acc)[G][16],
-                                           float *__restrict__ out, float *mine = nullptr);
+                                           float *__restrict__ out) {
+    __shared__ __attribute__((aligned(16))) float xs[kBlock / 64][1024];
+    float *mine = xs[threadIdx.x >> 6];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        const int e0 = 1024 * g + 16 * __lane_id();
+        if (e0 + 16 > wt.t.len) {  // tensor tail: keep the row padding zero
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[g][e] = (e0 + e < wt.t.len) ? acc[g][e] : 0.f;
+        }
+#pragma unroll
+        for (int v = 0; v < 4; ++v)
+            *reinterpret_cast<f32x4 *>(mine + 16 * __lane_id() + 4 * v) =
+                f32x4{acc[g][4 * v], acc[g][4 * v + 1], acc[g][4 * v + 2], acc[g][4 * v + 3]};
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const int e = 256 * v + 4 * __lane_id();
+            const f32x4 x = *reinterpret_cast<const f32x4 *>(mine + e);
+            if (1024 * g + e < wt.lenpad)
+                *reinterpret_cast<f32x4 *>(out + wt.t.dst + 1024 * g + e) = x;
+        }
+    }
+}
 
 // One-channel tiles of up to 4 KiB: slice g of the tile is lanes'
 // 16-element chunks 1024 g + 16 lane; the wave walks the clients once for all
@@ -728,43 +701,6 @@ __device__ __forceinline__ void lane_tile(const WaveTile &wt, const uint8_t *__r
     store_tile<G>(wt, acc, out);
 }
 
-// Write a wave tile's G slices of accumulators, transposed through LDS so that
-// each store instruction writes 1 KiB contiguous.
-// EXT: mine is the wave's 4 KiB of LDS from the caller (a kernel running several
-// tile widths holds ONE buffer); else the function's own
-template <int G, bool EXT>
-__device__ __forceinline__ void store_tile(const WaveTile &wt, float (&acc)[G][16],
-                                           float *__restrict__ out, float *mine) {
-    if constexpr (!EXT) {
-        __shared__ __attribute__((aligned(16))) float xs[kBlock / 64][1024];
-        mine = xs[threadIdx.x >> 6];
-    }
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        const int e0 = 1024 * g + 16 * __lane_id();
-        if (e0 + 16 > wt.t.len) {  // tensor tail: keep the row padding zero
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[g][e] = (e0 + e < wt.t.len) ? acc[g][e] : 0.f;
-        }
-#pragma unroll
-        for (int v = 0; v < 4; ++v)
-            *reinterpret_cast<f32x4 *>(mine + 16 * __lane_id() + 4 * v) =
-                f32x4{acc[g][4 * v], acc[g][4 * v + 1], acc[g][4 * v + 2], acc[g][4 * v + 3]};
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const int e = 256 * v + 4 * __lane_id();
-            const f32x4 x = *reinterpret_cast<const f32x4 *>(mine + e);
-            if (1024 * g + e < wt.lenpad) {
-                f32x4 *o = reinterpret_cast<f32x4 *>(out + wt.t.dst + 1024 * g + e);
-                if constexpr (DLS_QUANT_NTSTORE)
-                    __builtin_nontemporal_store(x, o);
-                else
-                    *o = x;
-            }
-        }
-    }
-}
-
 template <int G, bool TWO>
 __global__ __launch_bounds__(kBlock, 1) void k_dequant_fast(
     const dls_qtile *__restrict__ tiles, int ntiles, const uint8_t *__restrict__ Q, int64_t ldq,
@@ -778,296 +714,6 @@ __global__ __launch_bounds__(kBlock, 1) void k_dequant_fast(
         fast_tile<true, G, TWO>(wt, Q, ldq, sz, L, rows, w, K, d, out);
     else
         fast_tile<false, G, TWO>(wt, Q, ldq, sz, L, rows, w, K, d, out);
-}
-
-// ------------------------------------------------------------ FMA mode
-// DLS_FEDAVG_FMA (north-star FedAvg tolerance, not bit-exact): every int
-// element accumulates fma(q - z, c, acc) with one constant per (client,
-// channel) c = fl(fl(s * n_i) / N) (q - z is exact in fp32).  None of the exact
-// path's rounding sequence, range checks or fallbacks is needed, so these
-// kernels are lean (no rare path in the register budget): more waves per SIMD,
-// more bytes in flight.  Zero points are almost always 0 (symmetric qint8, the
-// QAT worker's format): a chunk whose zero points are all 0 skips the
-// subtraction (one wave-uniform test per 64-client chunk).
-template <bool SEXT>
-__device__ __forceinline__ void accum16_fmaz(float (&acc)[16], u32x4 qv, f32x2 cz) {
-    // cz = (c, -z): x + (-z) exact, then fma(x, c, acc)
-#pragma unroll
-    for (int j = 0; j < 8; j += 2) {
-        const int k = j & 3;
-        f32x2 xa = f32x2{byte_val<SEXT>(qv[j >> 2], k), byte_val<SEXT>(qv[j >> 2], k + 1)};
-        f32x2 xb = f32x2{byte_val<SEXT>(qv[(j >> 2) + 2], k), byte_val<SEXT>(qv[(j >> 2) + 2], k + 1)};
-        f32x2 ra = f32x2{acc[j], acc[j + 1]}, rb = f32x2{acc[j + 8], acc[j + 9]};
-        asm volatile(
-            "v_pk_add_f32 %[xa], %[xa], %[cz] op_sel:[0,1] op_sel_hi:[1,1]\n\t"
-            "v_pk_add_f32 %[xb], %[xb], %[cz] op_sel:[0,1] op_sel_hi:[1,1]\n\t"
-            "v_pk_fma_f32 %[ra], %[xa], %[cz], %[ra] op_sel_hi:[1,0,1]\n\t"
-            "v_pk_fma_f32 %[rb], %[xb], %[cz], %[rb] op_sel_hi:[1,0,1]"
-            : [ra] "+v"(ra), [rb] "+v"(rb), [xa] "+v"(xa), [xb] "+v"(xb)
-            : [cz] "v"(cz));
-        acc[j] = ra.x;
-        acc[j + 1] = ra.y;
-        acc[j + 8] = rb.x;
-        acc[j + 9] = rb.y;
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
-
-template <bool SEXT>
-__device__ __forceinline__ void accum16_fma_any(float (&acc)[16], u32x4 qv, f32x2 cz, bool allz) {
-    if (allz)
-        accum16_fma<SEXT>(acc, qv, cz);
-    else
-        accum16_fmaz<SEXT>(acc, qv, cz);
-}
-
-// One-channel tiles (groups 0-3) in FMA mode: one (c, -z) per client, read back
-// as wave-uniform values; G KiB slices per client.
-template <bool SIGNED, int G>
-__device__ __forceinline__ void fma_one_channel_tile(const WaveTile &wt, const uint8_t *__restrict__ Q,
-                                                     int64_t ldq, const f32x2 *__restrict__ sz,
-                                                     SzLayout L, const int32_t *__restrict__ rows,
-                                                     const float *__restrict__ w, int K, float N,
-                                                     float *__restrict__ out) {
-    float acc[G][16];
-    uint32_t qoff[G];
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[g][e] = 0.f;
-        const int e0 = 1024 * g + 16 * __lane_id();
-        qoff[g] = (uint32_t)(wt.t.src + (e0 < wt.lenpad ? e0 : wt.lenpad - 16));
-    }
-    const f32x2 *szc = sz + wt.t.chan0 * L.chan;
-    ChunkRows cr;
-    cr.init(rows, w, K);
-    f32x2 nsz = szc[(int64_t)cr.r0 * L.row];
-    constexpr int U = G > 1 ? kQuantUG : kQuantU;
-    struct B {
-        u32x4 qv[U][G];
-        float c[U], z[U];
-    };
-    for (int base = 0; base < K; base += 64) {
-        const int tr = cr.r0;
-        const float coef = fma_coef(nsz.x, cr.w0, N), nz = -nsz.y;
-        const bool allz = __ballot(nsz.y != 0.f && __lane_id() < K - base) == 0;
-        nsz = szc[(int64_t)cr.r1 * L.row];  // next chunk (its rows landed a chunk ago)
-        cr.advance(rows, w, K, base);
-        const int n = min(64, K - base);
-        auto fetch = [&](int j, u32x4 (&qv)[G], float &c, float &z) {
-            const int64_t r = readlane_i(tr, j);
-            const auto rs = __builtin_amdgcn_make_buffer_rsrc(
-                const_cast<uint8_t *>(Q + r * ldq), 0, (int)0xffffffffu, 0x00020000);  // 4 GiB
-#pragma unroll
-            for (int g = 0; g < G; ++g)
-                qv[g] = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)qoff[g], 0, 2 /* nt */);
-            c = readlane_f(coef, j);
-            z = readlane_f(nz, j);
-        };
-        auto step = [&](const u32x4 (&qv)[G], float c, float z) {
-#pragma unroll
-            for (int g = 0; g < G; ++g) accum16_fma_any<SIGNED>(acc[g], qv[g], f32x2{c, z}, allz);
-        };
-        chunk_pipeline<U, B>(
-            n,
-            [&](int j0, B &b) {
-#pragma unroll
-                for (int u = 0; u < U; ++u) fetch(j0 + u, b.qv[u], b.c[u], b.z[u]);
-            },
-            [&](const B &b) {
-#pragma unroll
-                for (int u = 0; u < U; ++u) step(b.qv[u], b.c[u], b.z[u]);
-            },
-            [&](int j) {
-                u32x4 qv[G];
-                float c, z;
-                fetch(j, qv, c, z);
-                step(qv, c, z);
-            });
-    }
-    store_tile<G>(wt, acc, out);
-}
-
-// Multi-channel (lane) tiles (groups 4-7) in FMA mode: the channels' (c, -z) of
-// the chunk's 64 clients staged in the wave's LDS table (lane j computes client
-// j's), one broadcast ds_read_b64 per slice and client.  A tile over more than
-// kSpanMax channels is walked in ceil(span / kSpanMax) passes of kSpanMax
-// channels; a lane outside the pass's channels reads the table's zero row
-// (c = 0: fma(x, 0, acc) leaves acc), so there is ONE walk loop.  A second loop
-// (the per-client gather path of round 3), or a per-chunk choice between the
-// zero-point forms, made the register allocator keep two copies of the
-// accumulators: 234 VGPRs at G = 4 (2 waves per SIMD, the group in two launch
-// pieces of 1.2 waves per SIMD) against 156 with one loop (3 waves per SIMD,
-// one piece).  The zero point is always subtracted: x + (-z) is exact and
-// x + (-0) == x, so a chunk of zero points 0 gives the bits of the
-// subtraction-free form.
-template <bool SIGNED, int G, bool EXT = false>
-__device__ __forceinline__ void fma_lane_tile(const WaveTile &wt, const uint8_t *__restrict__ Q,
-                                              int64_t ldq, const f32x2 *__restrict__ sz, SzLayout L,
-                                              const int32_t *__restrict__ rows,
-                                              const float *__restrict__ w, int K, float N,
-                                              float *__restrict__ out,
-                                              f32x2 (*tab)[64] = nullptr, float *xsw = nullptr) {
-    if constexpr (!EXT) {  // else the caller's (k_dequant_lanes_fma_any)
-        __shared__ __attribute__((aligned(16))) f32x2 ftab[kBlock / 64][kSpanMax + 1][64];
-        tab = ftab[threadIdx.x >> 6];
-    }
-    tab[kSpanMax][__lane_id()] = f32x2{0.f, 0.f};  // the zero row
-    float acc[G][16];
-    uint32_t qoff[G];
-    int crel[G];  // the lane's channel in slice g, relative to the tile's first
-    const int span = (wt.t.row_pos + wt.t.len - 1) / wt.t.row_len + 1;  // wave-uniform
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[g][e] = 0.f;
-        const int e0 = 1024 * g + 16 * __lane_id();
-        const int ec = e0 < wt.lenpad ? e0 : wt.lenpad - 16;
-        qoff[g] = (uint32_t)(wt.t.src + ec);
-        crel[g] = min((wt.t.row_pos + ec) / wt.t.row_len, span - 1);
-    }
-    constexpr int US = G > 1 ? kLaneUSG : kLaneUS;
-    struct SOne {
-        u32x4 qv[G];
-        int j;
-    };
-    struct SBatch {
-        SOne c[US];
-    };
-    // passes x chunks as ONE loop (a loop over passes around the chunk loop cost
-    // 24 VGPRs at G = 4); almost every tile has one pass
-    const int npass = (span + kSpanMax - 1) / kSpanMax;
-    const int nch = (K + 63) / 64;
-    int c0 = wt.t.chan0;  // the pass's first channel
-    uint32_t toff[G];     // the lane's table row, in pairs
-    auto pass_rows = [&](int p) {
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            const int c = crel[g] - kSpanMax * p;
-            toff[g] = (uint32_t)(c >= 0 && c < kSpanMax ? c : kSpanMax) * 64;
-        }
-    };
-    auto tab_load = [&](int r, f32x2 (&v)[kSpanMax]) {
-#pragma unroll
-        for (int c = 0; c < kSpanMax; ++c)
-            v[c] = sz[(int64_t)min(c0 + c, wt.t.chan_end - 1) * L.chan + (int64_t)r * L.row];
-    };
-    pass_rows(0);
-    ChunkRows cr;
-    cr.init(rows, w, K);
-    f32x2 nsz[kSpanMax];
-    tab_load(cr.r0, nsz);
-    for (int it = 0, p = 0, base = 0; it < npass * nch; ++it) {
-        const int tr = cr.r0;
-        const float tw = cr.w0;
-        const int n = min(64, K - base);
-#pragma unroll
-        for (int c = 0; c < kSpanMax; ++c)
-            tab[c][__lane_id()] = f32x2{fma_coef(nsz[c].x, tw, N), -nsz[c].y};
-        tab_load(cr.r1, nsz);  // next chunk (its rows landed a chunk ago)
-        cr.advance(rows, w, K, base);
-        auto sfetch = [&](int j, SOne &b) {
-            const int64_t r = readlane_i(tr, j);
-            const auto rs = __builtin_amdgcn_make_buffer_rsrc(
-                const_cast<uint8_t *>(Q + r * ldq), 0, (int)0xffffffffu, 0x00020000);  // 4 GiB
-#pragma unroll
-            for (int g = 0; g < G; ++g)
-                b.qv[g] = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)qoff[g], 0, 2 /* nt */);
-            b.j = j;
-        };
-        auto sstep = [&](const SOne &b) {
-#pragma unroll
-            for (int g = 0; g < G; ++g) accum16_fmaz<SIGNED>(acc[g], b.qv[g], tab[0][toff[g] + b.j]);
-        };
-        chunk_pipeline_1tail<US, SBatch>(
-            n,
-            [&](int j0, SBatch &b) {
-#pragma unroll
-                for (int u = 0; u < US; ++u) sfetch(j0 + u, b.c[u]);
-            },
-            [&](const SBatch &b) {
-#pragma unroll
-                for (int u = 0; u < US; ++u) sstep(b.c[u]);
-            },
-            [&](int j) {
-                SOne b;
-                sfetch(j, b);
-                sstep(b);
-            });
-        base += 64;
-        if (base >= K && p + 1 < npass) {  // the next pass: its channels, the clients again
-            ++p;
-            base = 0;
-            c0 += kSpanMax;
-            pass_rows(p);
-            cr.init(rows, w, K);
-            tab_load(cr.r0, nsz);
-        }
-    }
-    store_tile<G, EXT>(wt, acc, out, xsw);
-}
-
-template <int G>
-__global__ __launch_bounds__(kBlock) void k_dequant_fast_fma(
-    const dls_qtile *__restrict__ tiles, int ntiles, const uint8_t *__restrict__ Q, int64_t ldq,
-    const f32x2 *__restrict__ sz, SzLayout L, const int32_t *__restrict__ rows,
-    const float *__restrict__ w, int K, FastDiv d, float *__restrict__ out) {
-    WaveTile wt;
-    if (!wave_tile(tiles, ntiles, wt)) return;
-    if (wt.t.kind == 1)
-        fma_one_channel_tile<true, G>(wt, Q, ldq, sz, L, rows, w, K, d.b, out);
-    else
-        fma_one_channel_tile<false, G>(wt, Q, ldq, sz, L, rows, w, K, d.b, out);
-}
-
-template <int G>
-__global__ __launch_bounds__(kBlock) void k_dequant_lanes_fma(
-    const dls_qtile *__restrict__ tiles, int ntiles, const uint8_t *__restrict__ Q, int64_t ldq,
-    const f32x2 *__restrict__ sz, SzLayout L, const int32_t *__restrict__ rows,
-    const float *__restrict__ w, int K, FastDiv d, float *__restrict__ out) {
-    WaveTile wt;
-    if (!wave_tile(tiles, ntiles, wt)) return;
-    if (wt.t.kind == 1)
-        fma_lane_tile<true, G>(wt, Q, ldq, sz, L, rows, w, K, d.b, out);
-    else
-        fma_lane_tile<false, G>(wt, Q, ldq, sz, L, rows, w, K, d.b, out);
-}
-
-// Every lane-tile group (4, 3, 2 and 1 KiB tiles, the table's groups 4-7, which
-// are contiguous) in ONE launch: a wave takes its tile's width (wave-uniform),
-// one LDS table and store buffer per wave serve every width, so the kernel's
-// registers and LDS are those of the widest.  The bulk of the FMA call then has
-// no side-stream lane kernels beside it, and no fork / join for them.
-__global__ __launch_bounds__(kBlock) void k_dequant_lanes_fma_any(
-    const dls_qtile *__restrict__ tiles, int ntiles, const uint8_t *__restrict__ Q, int64_t ldq,
-    const f32x2 *__restrict__ sz, SzLayout L, const int32_t *__restrict__ rows,
-    const float *__restrict__ w, int K, FastDiv d, float *__restrict__ out) {
-    __shared__ __attribute__((aligned(16))) f32x2 ftab[kBlock / 64][kSpanMax + 1][64];
-    __shared__ __attribute__((aligned(16))) float xs[kBlock / 64][1024];
-    WaveTile wt;
-    if (!wave_tile(tiles, ntiles, wt)) return;
-    f32x2(*tab)[64] = ftab[threadIdx.x >> 6];
-    float *mine = xs[threadIdx.x >> 6];
-    const int slices = __builtin_amdgcn_readfirstlane((wt.t.len + 1023) >> 10);
-    auto run = [&](auto sgn_c, auto g_c) {
-        constexpr bool SG = decltype(sgn_c)::value;
-        constexpr int G = decltype(g_c)::value;
-        fma_lane_tile<SG, G, true>(wt, Q, ldq, sz, L, rows, w, K, d.b, out, tab, mine);
-    };
-    auto by_width = [&](auto sgn_c) {
-        if (slices >= 4)
-            run(sgn_c, std::integral_constant<int, 4>{});
-        else if (slices == 3)
-            run(sgn_c, std::integral_constant<int, 3>{});
-        else if (slices == 2)
-            run(sgn_c, std::integral_constant<int, 2>{});
-        else
-            run(sgn_c, std::integral_constant<int, 1>{});
-    };
-    if (wt.t.kind == 1)
-        by_width(std::true_type{});
-    else
-        by_width(std::false_type{});
 }
 
 // The fp32 and small-int groups (quant_common.h walks), a wave per tile.  A few
@@ -1370,18 +1016,16 @@ extern "C" int dls_dequant_fedavg_mode(const dls_qtile *tiles, int32_t ntiles,
     DLS_REQUIRE(ldq < ((int64_t)1 << 32), DLS_ELAYOUT,
                 "dls_dequant_fedavg: ldq=%lld must be < 2^32 (32-bit lane offsets)",
                 (long long)ldq);
-    // two-constant division when proven exact for this N, else Markstein (the
-    // FMA-mode bulk kernels divide once per (client, channel) with IEEE '/')
-    const FastDiv d = mode == DLS_FEDAVG_FMA ? make_fastdiv(total) : make_fastdiv2(total);
+    // exact mode: the two-constant division when proven exact for this N, else
+    // Markstein; FMA mode divides once per (client, channel) with IEEE '/'
+    const bool fma = mode == DLS_FEDAVG_FMA;
+    const FastDiv d = fma ? make_fastdiv(total) : make_fastdiv2(total);
     const SzLayout L{sz_row, sz_chan};
     hipStream_t st = as_stream(stream);
     constexpr int wpb = kBlock / 64;
     // Groups: 0-3 one-channel tiles of 4/3/2/1 KiB slices, 4-7 lane-channel tiles
-    // of 4/3/2/1 KiB, 8 fp32 tiles, 9 small int tiles, then the general tiles.  The group with
-    // the most bytes runs on the caller's stream; every other non-empty group on a
-    // side stream of its own, concurrently (their waves walk all K clients, so a
-    // small group is a long latency chain, not a small amount of work), and the
-    // caller's stream joins them all.
+    // of 4/3/2/1 KiB, 8 fp32 tiles, 9 small int tiles, then the general tiles
+    // (channel rows < 4 elements); big: the group with the most bytes.
     const dls_qtile *tg[DLS_QTILE_GROUPS];
     const dls_qtile *t = tiles;
     int big = -1;
@@ -1393,33 +1037,6 @@ extern "C" int dls_dequant_fedavg_mode(const dls_qtile *tiles, int32_t ntiles,
         t += nfast[g];
         if (nfast[g] > 0 && (big < 0 || bytes(g) > bytes(big))) big = g;
     }
-    // FMA mode: the lane groups (4-7, contiguous in the table) as ONE launch of
-    // k_dequant_lanes_fma_any, on the caller's stream when their bytes are the most
-    const bool any = mode == DLS_FEDAVG_FMA && kQuantFmaAny;
-    int lanes_n = 0;
-    int64_t lanes_bytes = 0;
-    bool big_lanes = false;
-    if (any) {
-        for (int g = 4; g < 8; ++g) {
-            lanes_n += nfast[g];
-            lanes_bytes += bytes(g);
-        }
-        big = -1;
-        for (int g = 0; g < DLS_QTILE_GROUPS; ++g)
-            if ((g < 4 || g > 7) && nfast[g] > 0 && (big < 0 || bytes(g) > bytes(big))) big = g;
-        if (lanes_n > 0 && (big < 0 || lanes_bytes >= bytes(big))) {
-            big_lanes = true;
-            big = -1;
-        }
-    }
-    // FMA mode: groups 0-9 on quant_fma.hip's kernel on the caller's stream (the
-    // fp32 and small-int tiles exact, in the first launch piece); only general
-    // tiles (channel rows < 4 elements) still go to a side stream
-    const bool stream_fma = mode == DLS_FEDAVG_FMA && kQuantFmaStream;
-    if (stream_fma) {
-        big = -1;
-        big_lanes = false;
-    }
     const int ngen = ntiles - (int)nf;
     // fork / join events cached per caller stream (dls_runtime.hip call_event):
     // a call creates and destroys nothing
@@ -1427,8 +1044,7 @@ extern "C" int dls_dequant_fedavg_mode(const dls_qtile *tiles, int32_t ntiles,
     hipStream_t sides[DLS_QTILE_GROUPS + 1] = {};
     int nside = 0;
     bool forked = false;
-    auto stream_for = [&](bool empty) -> hipStream_t {  // a fresh side stream, else st
-        if (empty) return st;
+    auto fork_side = [&]() -> hipStream_t {  // a fresh side stream behind the fork, else st
         if (!forked) {
             forked = true;
             fork = call_event(st, 0);
@@ -1442,19 +1058,20 @@ extern "C" int dls_dequant_fedavg_mode(const dls_qtile *tiles, int32_t ntiles,
     };
     using Kfn = void (*)(const dls_qtile *, int, const uint8_t *, int64_t, const f32x2 *, SzLayout,
                          const int32_t *, const float *, int, FastDiv, float *);
-    // [group][0: Markstein, 1: two-constant division, 2: FMA mode]
-    static const Kfn kgroup[8][3] = {
-        {k_dequant_fast<4, false>, k_dequant_fast<4, true>, k_dequant_fast_fma<4>},
-        {k_dequant_fast<3, false>, k_dequant_fast<3, true>, k_dequant_fast_fma<3>},
-        {k_dequant_fast<2, false>, k_dequant_fast<2, true>, k_dequant_fast_fma<2>},
-        {k_dequant_fast<1, false>, k_dequant_fast<1, true>, k_dequant_fast_fma<1>},
-        {k_dequant_lanes<4, false>, k_dequant_lanes<4, true>, k_dequant_lanes_fma<4>},
-        {k_dequant_lanes<3, false>, k_dequant_lanes<3, true>, k_dequant_lanes_fma<3>},
-        {k_dequant_lanes<2, false>, k_dequant_lanes<2, true>, k_dequant_lanes_fma<2>},
-        {k_dequant_lanes<1, false>, k_dequant_lanes<1, true>, k_dequant_lanes_fma<1>}};
-    // A wave walks all K clients, so waves are long and equal: a group is launched
-    // in pieces of at most one generation of resident waves (a last generation of
-    // a few waves would run alone at latency-bound speed; cf. dls_fedavg_f32).
+    // exact mode, [group][0: Markstein, 1: two-constant division]
+    static const Kfn kgroup[8][2] = {
+        {k_dequant_fast<4, false>, k_dequant_fast<4, true>},
+        {k_dequant_fast<3, false>, k_dequant_fast<3, true>},
+        {k_dequant_fast<2, false>, k_dequant_fast<2, true>},
+        {k_dequant_fast<1, false>, k_dequant_fast<1, true>},
+        {k_dequant_lanes<4, false>, k_dequant_lanes<4, true>},
+        {k_dequant_lanes<3, false>, k_dequant_lanes<3, true>},
+        {k_dequant_lanes<2, false>, k_dequant_lanes<2, true>},
+        {k_dequant_lanes<1, false>, k_dequant_lanes<1, true>}};
+    // Exact mode's launch of group g.  A wave walks all K clients, so waves are
+    // long and equal: a group is launched in pieces of at most one generation of
+    // resident waves (a last generation of a few waves would run alone at
+    // latency-bound speed; cf. dls_fedavg_f32).
     auto launch_group = [&](int g, hipStream_t s) {
         const int n = nfast[g];
         if (n == 0) return;
@@ -1470,10 +1087,9 @@ extern "C" int dls_dequant_fedavg_mode(const dls_qtile *tiles, int32_t ntiles,
                                out);
             return;
         }
-        const Kfn kern = kgroup[g][mode == DLS_FEDAVG_FMA ? 2 : (d.two ? 1 : 0)];
-        int64_t slots = (int64_t)resident_blocks(reinterpret_cast<const void *>(kern), kBlock, 0) * wpb;
-        if (kQuantPieceWps > 0)  // pieces of this many waves per SIMD (A/B knob)
-            slots = std::min<int64_t>(slots, (int64_t)device_cus() * 4 * kQuantPieceWps);
+        const Kfn kern = kgroup[g][d.two ? 1 : 0];
+        const int64_t slots =
+            (int64_t)resident_blocks(reinterpret_cast<const void *>(kern), kBlock, 0) * wpb;
         const int64_t np = (n + slots - 1) / slots;
         const int64_t per = (n + np - 1) / np;  // tiles per piece, <= slots
         for (int64_t t0 = 0; t0 < n; t0 += per) {
@@ -1483,38 +1099,31 @@ extern "C" int dls_dequant_fedavg_mode(const dls_qtile *tiles, int32_t ntiles,
                                reinterpret_cast<const f32x2 *>(sz), L, rows, weight, (int)K, d, out);
         }
     };
-    auto launch_lanes_any = [&](hipStream_t s) {  // pieces of at most one generation
-        const void *kern = reinterpret_cast<const void *>(k_dequant_lanes_fma_any);
-        const int64_t slots = (int64_t)resident_blocks(kern, kBlock, 0) * wpb;
-        const int64_t np = (lanes_n + slots - 1) / slots;
-        const int64_t per = (lanes_n + np - 1) / np;
-        for (int64_t t0 = 0; t0 < lanes_n; t0 += per) {
-            const int m = (int)(lanes_n - t0 < per ? lanes_n - t0 : per);
-            hipLaunchKernelGGL(k_dequant_lanes_fma_any, dim3((unsigned)((m + wpb - 1) / wpb)),
-                               dim3(kBlock), 0, s, tg[4] + t0, m,
-                               reinterpret_cast<const uint8_t *>(Q), ldq,
-                               reinterpret_cast<const f32x2 *>(sz), L, rows, weight, (int)K, d, out);
-        }
-    };
-    for (int g = 0; g < DLS_QTILE_GROUPS; ++g) {
-        if ((any || stream_fma) && g >= 4 && g < 8) continue;
-        if (stream_fma && (g < 4 || g == 8 || g == 9)) continue;  // all on the FMA kernel
-        if (g != big && nfast[g] > 0) launch_group(g, stream_for(false));
-    }
-    if (any && !stream_fma && lanes_n > 0 && !big_lanes) launch_lanes_any(stream_for(false));
-    if (ngen > 0)
+    auto launch_general = [&](hipStream_t s) {
         hipLaunchKernelGGL(k_dequant_general, dim3((unsigned)((ngen + wpb - 1) / wpb)),
-                           dim3(kBlock), 0, stream_for(false), t, ngen,
-                           reinterpret_cast<const uint8_t *>(Q), ldq, F, ldf,
-                           reinterpret_cast<const f32x2 *>(sz), L, rows, weight, (int)K, d, out);
+                           dim3(kBlock), 0, s, t, ngen, reinterpret_cast<const uint8_t *>(Q), ldq,
+                           F, ldf, reinterpret_cast<const f32x2 *>(sz), L, rows, weight, (int)K, d,
+                           out);
+    };
     int rc = DLS_OK;
-    if (stream_fma)
+    if (fma) {
+        // groups 0-9 on quant_fma.hip's kernel on the caller's stream (the fp32 and
+        // small-int tiles exact, in its first launch piece); only general tiles go
+        // to a side stream
+        if (ngen > 0) launch_general(fork_side());
         rc = launch_dequant_fma_stream(tiles, nfast, Q, ldq, F, ldf, sz, sz_row, sz_chan, rows,
                                        weight, K, total, out, st);
-    else if (big_lanes)
-        launch_lanes_any(st);
-    else if (big >= 0)
-        launch_group(big, st);
+    } else {
+        // the group with the most bytes on the caller's stream; every other
+        // non-empty group and the general tiles on a side stream of their own,
+        // concurrently (their waves walk all K clients, so a small group is a long
+        // latency chain, not a small amount of work); the caller's stream joins
+        // them all below
+        for (int g = 0; g < DLS_QTILE_GROUPS; ++g)
+            if (g != big && nfast[g] > 0) launch_group(g, fork_side());
+        if (ngen > 0) launch_general(fork_side());
+        if (big >= 0) launch_group(big, st);
+    }
     if (rc == DLS_OK) rc = check_launch("dls_dequant_fedavg");
     for (int i = 0; i < nside; ++i) {
         hipEvent_t join = call_event(st, 1 + i);

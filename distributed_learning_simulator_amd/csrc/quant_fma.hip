@@ -1,14 +1,19 @@
-// FMA mode (DLS_FEDAVG_FMA) of the fused dequant-FedAvg: every int tile of the
-// table's groups 0-7 (one-channel and lane-channel tiles, 1-4 KiB slices) on one
-// kernel, in launch pieces of exactly one wave per SIMD.
+// FMA mode (DLS_FEDAVG_FMA) of the fused dequant-FedAvg: the table's groups 0-9
+// on one kernel.  Every int tile of groups 0-7 (one-channel and lane-channel
+// tiles, 1-4 KiB slices) in launch pieces of exactly one wave per SIMD; the fp32
+// and small-int tiles (groups 8, 9) as side blocks of the first piece, with the
+// exact arithmetic.  This is the only FMA-mode code: quant.hip sends it every
+// grouped tile of an FMA call.
 //
 // Reference: FedQuantServer._process_client_parameter (servers/fed_quant_server.py:25-33)
 // dequantizes each client's int tensors channel by channel, FedServer.get_subset_model
 // (servers/fed_server.py:44-66) averages them.  FMA mode folds the per-(client,
 // channel) constants into one c = fl(fl(scale * n_i) / N) and accumulates
 //     out[e] = fma(q - zp, c, out[e])          (q - zp exact in fp32)
-// which is the north-star's 1e-6 (normwise) FedAvg tolerance, not bit-exact; the
-// bits equal the round-4 FMA kernels' (the same terms in the same client order).
+// which is the north-star's 1e-6 (normwise) FedAvg tolerance, not bit-exact.  (The
+// round-4 FMA kernels this replaced, per-width launches and a one-launch lane
+// kernel in quant.hip, are gone; they gave the same bits, the same terms in the
+// same client order, and their timings below stay as history.)
 // Algorithmic bytes per call: K*(Pq + 8*C) for these tiles + 4*Pq written.
 //
 // What sets the stream rate here (round 5, profiles/r05_quant_fma_ab.txt, the
@@ -391,7 +396,9 @@ __global__ __launch_bounds__(kFmaBlock) void k_dequant_fma_stream(const dls_qtil
 
 }  // namespace
 
-// Groups 0-7 of an FMA-mode call (quant.hip dls_dequant_fedavg_mode).
+// Groups 0-9 of an FMA-mode call (quant.hip dls_dequant_fedavg_mode), on st: the
+// int tiles of groups 0-7 in pieces, the fp32 and small-int tiles (8, 9) as side
+// blocks of the first piece.
 int launch_dequant_fma_stream(const dls_qtile *tiles, const int32_t *nfast, const void *Q,
                               int64_t ldq, const float *F, int64_t ldf, const float *sz,
                               int64_t sz_row, int64_t sz_chan, const int32_t *rows, const float *w,

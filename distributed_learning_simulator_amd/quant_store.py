@@ -71,8 +71,8 @@ def _adaptive_lane_tile(rl, n):
     (tiles start at multiples of the width from the tensor start); ties go to the
     wider.  Whole rows always qualify, so every such tensor gets lane tiles: on
     ResNet-18 the 3x3 convs take 4 KiB / 3,456 / 2,304-element tiles and the 1x1
-    shortcuts 1-4 rows, 2,986 waves in all (one generation of the FMA lane kernel
-    at 3 waves per SIMD)."""
+    shortcuts 1-4 rows, 2,986 tiles in all (three launch pieces of the FMA kernel
+    at one wave per SIMD)."""
     def fits(t):
         return all((e % rl + min(t, n - e) - 1) // rl + 1 <= 4 for e in range(0, n, t))
     best = None

@@ -532,8 +532,8 @@ int dls_dequant_fedavg(const dls_qtile *tiles, int32_t ntiles, const int32_t *nf
  * (q - zp exact) — a conversion and two packed ops per element pair instead of
  * the exact mode's six, a different rounding of each term: within the
  * north-star's 1e-6 FedAvg tolerance (normwise), not bit-exact; groups 8-9 and
- * the general tiles run their exact kernels.  Groups 0-7 run on one kernel in
- * launch pieces of one wave per SIMD, so the one-channel / lane split does not
+ * the general tiles keep the exact arithmetic.  Groups 0-7 run on one kernel in
+ * launch pieces of one wave per SIMD (groups 8-9 beside its first piece), so the one-channel / lane split does not
  * matter here: the store's FMA table lane-tiles every int tensor whose channel
  * rows are a multiple of 16 elements, long rows included). */
 int dls_dequant_fedavg_mode(const dls_qtile *tiles, int32_t ntiles, const int32_t *nfast,

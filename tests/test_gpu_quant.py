@@ -695,6 +695,77 @@ def test_dequant_fedavg_fma_lane_tiles_multipass(monkeypatch):
         assert err <= 1e-6, (name, err)
 
 
+def _one_channel_payloads(K=70, seed=53):
+    """(payloads, n, order) of test_dequant_fedavg_fma_one_channel_tiles."""
+    g = torch.Generator().manual_seed(seed)
+    shapes = {"a": (3, 5120), "b": (2, 3072), "c": (2, 2048), "d": (2, 1040), "e": (2, 5056)}
+    payloads, n = [], []
+    for _ in range(K):
+        p = {}
+        for name, s in shapes.items():
+            C = s[0]
+            if name == "b":  # uint8 with zero points
+                p[name] = (torch.randint(0, 256, s, generator=g, dtype=torch.uint8),
+                           torch.rand(C, generator=g, dtype=torch.float64) * 1e-3 + 1e-5,
+                           torch.randint(0, 256, (C,), generator=g))
+            else:
+                p[name] = (torch.randint(-128, 128, s, generator=g, dtype=torch.int8),
+                           torch.rand(C, generator=g, dtype=torch.float64) * 1e-2 + 1e-4,
+                           torch.zeros(C, dtype=torch.int64))
+        payloads.append(p)
+        n.append(int(torch.randint(1, 1000, (1,), generator=g)))
+    return payloads, n, list(torch.randperm(K, generator=g).tolist())
+
+
+def test_dequant_fedavg_fma_one_channel_tiles(monkeypatch):
+    """FMA mode on one-channel tiles (table groups 0-3), which only a caller's table
+    reaches (the store's FMA table lane-tiles long rows: FMA_ONE_CHANNEL = False)
+    and which k_dequant_fma_stream alone can run.  Rows of 5120 (a 4 KiB and a 1 KiB
+    tile: groups 0 and 3), 3072 (group 1, uint8 with zero points), 2048 (group 2)
+    and 5056 elements (a 4 KiB tile and one of 960 elements: group 3 with idle
+    lanes); rows of 1040 are no multiple of 64, so the store makes "d" one 3 KiB
+    lane tile with a masked tail (group 5) beside them.  K across two 64-client
+    chunks; every tensor within the north-star 1e-6 normwise of the exact oracle,
+    and the same store bit-exact in exact mode (k_dequant_fast<4|3|2|1>).  An fp32
+    multiply-add walk of these inputs in numpy lies at 1.2e-7 to 1.4e-7 of the
+    oracle, tensor by tensor."""
+    from distributed_learning_simulator_amd import _native, quant_store as qs
+    from distributed_learning_simulator_amd.quant_store import QTILE_DTYPE, QuantizedClientStore
+    monkeypatch.setattr(qs, "FMA_ONE_CHANNEL", True)
+    K = 70
+    payloads, n, order = _one_channel_payloads(K)
+    store = QuantizedClientStore(payloads[0], dev, capacity=K)
+    assert all(c > 0 for c in store.nfast_fma[:4]), store.nfast_fma
+    assert all(c > 0 for c in store.nfast[:4]), store.nfast
+    t = store.tiles_fma.cpu().numpy().view(QTILE_DTYPE)
+    g3 = t[sum(store.nfast_fma[:3]):sum(store.nfast_fma[:4])]
+    assert g3["len"].min() < 1024 and store.nfast_fma[5] > 0  # part-filled tile, masked tail
+    rows = []
+    for p in payloads:
+        r = store.acquire()
+        store.write(r, p)
+        rows.append(r)
+    layout = [(k, tuple(v[0].shape)) for k, v in payloads[0].items()]
+    clients = [{k: tuple(t_.numpy() for t_ in v) for k, v in p.items()} for p in payloads]
+    ref = oquant.dequant_fedavg(clients, n, order, layout)
+    for mode in (_native.FEDAVG_EXACT, _native.FEDAVG_FMA):
+        full = torch.full((store.layout.P,), float("nan"), device=dev)
+        out = store.layout.views(store.fedavg([rows[i] for i in order], [n[i] for i in order],
+                                              out=full, mode=mode))
+        assert_padding_zero(store.layout, full)
+        if mode == _native.FEDAVG_EXACT:
+            assert same_bits(flat(out, layout), ref)
+            continue
+        off = 0
+        for name, shape in layout:
+            m = int(np.prod(shape))
+            got, want = out[name].reshape(-1).cpu().numpy(), ref[off:off + m]
+            off += m
+            err = np.linalg.norm(got.astype(np.float64) - want) / np.linalg.norm(want)
+            print(f"fma one-channel {name}: normwise error {err:.3e}")
+            assert err <= 1e-6, (name, err)
+
+
 def test_qat_weight_fake_quant_ste():
     """The fed_quant worker's quantization-aware training (ref
     workers/fed_quant_worker.py:19-20): conv / linear weights enter the forward

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Build libdls_hip.so variants with -D knobs for same-box A/B timing (tools/ab_bench.py).
 
-    python tools/build_variants.py base: qU2:-DDLS_QUANT_U=2 noscalar:-DDLS_QUANT_SCALAR_SZ=0
+    python tools/build_variants.py base: laneus1:-DDLS_LANE_US=1 fmad4:-DDLS_FMA_D=4
 """
 import concurrent.futures as cf
 import os
