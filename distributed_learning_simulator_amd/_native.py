@@ -170,9 +170,30 @@ def _stream(stream=None, like=None):
     return ctypes.c_void_p(stream.cuda_stream)
 
 
-CSRC_HASHED = ["dls_runtime.hip", "fedavg.hip", "sign.hip", "quant.hip", "quant_fma.hip", "shapley.hip",
-               "infer.hip", "conv.hip", "lenet.hip", "loss.hip", "robust.hip", "pairdist.hip", "weiszfeld.hip", "gram.hip", "serveropt.hip", "topk.hip", "dls_common.h", "quant_common.h",
-               "loss_common.h", "sign_geometry.h", os.path.join("..", "..", "include", "dls_hip.h")]
+CSRC_HASHED = [  # the Makefile's HASHED, in its order
+    "dls_runtime.hip",
+    "fedavg.hip",
+    "sign.hip",
+    "quant.hip",
+    "quant_fma.hip",
+    "shapley.hip",
+    "infer.hip",
+    "conv.hip",
+    "lenet.hip",
+    "loss.hip",
+    "robust.hip",
+    "pairdist.hip",
+    "weiszfeld.hip",
+    "gram.hip",
+    "serveropt.hip",
+    "topk.hip",
+    "dls_common.h",
+    "quant_common.h",
+    "loss_common.h",
+    "sign_geometry.h",
+    "rows_common.h",
+    os.path.join("..", "..", "include", "dls_hip.h"),
+]
 
 
 def source_hash():
@@ -209,6 +230,93 @@ def fedavg(U, rows, weight, total, P, out, mode=FEDAVG_EXACT, stream=None):
     return out
 
 
+# ------------------------------------------------- the operand checks, one of each
+# The rows family (trimmed mean .. centered clip) and the vector calls after it state
+# their operand contract with these; the library checks it again (csrc/rows_common.h).
+_DTYPE_NAMES = {torch.float32: "fp32", torch.float64: "fp64", torch.int32: "int32",
+                torch.int64: "int64"}
+
+
+def _check_tensor(fn, name, t, dtype, n, what, exact=True, contiguous=True, device=None):
+    """The one tensor check: ``t`` holds ``dtype`` (on ``device``, if given) and n, a
+    shape tuple: has exactly that shape, contiguous; an int with ``contiguous``: exactly
+    n elements of any shape, contiguous; an int without: is 1-D with unit stride and at
+    least (``exact``: exactly) n elements.  ``what`` ends the message (a string, or a
+    function that makes it: it is only wanted on failure)."""
+    ok = torch.is_tensor(t) and t.dtype == dtype and (device is None or t.device == device)
+    if ok and isinstance(n, tuple):
+        ok = tuple(t.shape) == n and t.is_contiguous()
+    elif ok and contiguous:
+        ok = t.numel() == n and t.is_contiguous()
+    elif ok:
+        ok = (t.dim() == 1 and (t.numel() == n if exact else t.numel() >= n)
+              and (t.numel() <= 1 or t.stride(0) == 1))
+    if not ok:
+        raise RuntimeError(f"{fn}: {name} must be {what() if callable(what) else what}")
+
+
+def _unit_vector(fn, name, t, dtype, n, exact=False, count=None):
+    """t: a ``dtype`` vector with unit stride of at least (``exact``: exactly) n elements
+    (``count``: a (label, n) pair the message writes as label=n)."""
+    _check_tensor(fn, name, t, dtype, n, lambda: f"an {_DTYPE_NAMES[dtype]} vector of "
+                  f"{'exactly' if exact else 'at least'} {n if count is None else '%s=%s' % count} elements "
+                  "with unit stride", exact=exact, contiguous=False)
+
+
+def _f32_vector(fn, name, t, P):
+    _unit_vector(fn, name, t, torch.float32, P, count=("P", P))
+
+
+def _k_tensor(fn, name, t, dtype, shape):
+    """t: a contiguous tensor of ``shape``, (K,) or (K, K), and ``dtype``."""
+    _check_tensor(fn, name, t, dtype, shape, lambda: f"a contiguous {_DTYPE_NAMES[dtype]} "
+                  f"[{', '.join('K' * len(shape))}] = {list(shape)} tensor")
+
+
+def _f64_out(fn, name, t, shape):
+    """An optional output (None: the wrapper allocates it): contiguous fp64 of ``shape``."""
+    if t is not None:
+        _k_tensor(fn, name, t, torch.float64, shape)
+
+
+def _check_same_device(fn, x, /, _anchor="the input", **others):
+    """Every given tensor (None: skipped) is on x's device; the message calls x ``_anchor``."""
+    for name, t in others.items():
+        if t is not None and t.device != x.device:
+            raise RuntimeError(f"{fn}: {name} is on {t.device}, {_anchor} on {x.device}")
+
+
+def _overlaps(a, b):
+    """True if the storage ranges of a and b intersect."""
+    a0 = a.data_ptr()
+    b0 = b.data_ptr()
+    return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+
+
+def _check_disjoint(tensors, message, allowed=None):
+    """No two of the name -> tensor pairs overlap, but for a pair ``allowed(a, b)``
+    exempts; ``message`` is formatted with the two names."""
+    names = list(tensors)
+    for i, a in enumerate(names):
+        for b in names[i + 1:]:
+            if not (allowed and allowed(a, b)) and _overlaps(tensors[a], tensors[b]):
+                raise RuntimeError(message.format(a=a, b=b))
+
+
+def _aligned16(fn, **tensors):
+    """Every given tensor (None: skipped) starts on a 16-byte boundary; the message
+    names all of them."""
+    if any(t is not None and t.data_ptr() % 16 != 0 for t in tensors.values()):
+        *head, last = tensors
+        raise RuntimeError(f"{fn}: {', '.join(head) + ' and ' if head else ''}{last} must be "
+                           "16-byte aligned")
+
+
+def _row_pitch(t):
+    """The element pitch of the rows of a matrix (one row: its width)."""
+    return t.stride(0) if t.shape[0] > 1 else t.shape[1]
+
+
 def _rows_operands(fn, U, rows, P, names=("U", "rows")):
     """The checks every rows-family wrapper makes on a matrix, a row table and P
     (``names``: what the messages call the two tensors): returns (K, P, ldu)."""
@@ -221,9 +329,9 @@ def _rows_table(fn, U, rows, names=("U", "rows")):
             or (U.shape[1] > 1 and U.stride(1) != 1)):
         raise RuntimeError(f"{fn}: {names[0]} must be an fp32 [rows, ld] matrix with unit "
                            "element stride")
-    if not torch.is_tensor(rows) or rows.dtype != torch.int32 or rows.dim() != 1 \
-            or not rows.is_contiguous():
-        raise RuntimeError(f"{fn}: {names[1]} must be a contiguous int32 [K] tensor")
+    # 1-D with unit stride and any length (K is checked below) is "contiguous 1-D"
+    _check_tensor(fn, names[1], rows, torch.int32, 0, "a contiguous int32 [K] tensor",
+                  exact=False, contiguous=False)
     K = rows.numel()
     if not 1 <= K <= ROBUST_MAX_K:
         raise RuntimeError(f"{fn}: K={K} rows (1..ROBUST_MAX_K={ROBUST_MAX_K})")
@@ -237,40 +345,47 @@ def _rows_extent(fn, U, P):
     if P < 0 or P % 4 != 0 or P > U.shape[1]:
         raise RuntimeError(f"{fn}: P={P} must be a multiple of 4 and at most the row "
                            f"length {U.shape[1]}")
-    ldu = U.stride(0) if U.shape[0] > 1 else U.shape[1]
+    ldu = _row_pitch(U)
     if ldu % 4 != 0 or ldu < P:
         raise RuntimeError(f"{fn}: row pitch {ldu} must be a multiple of 4, at least P")
     return P, ldu
 
 
-def _f32_vector(fn, name, t, P):
-    if (not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 1
-            or t.numel() < P or (t.numel() > 1 and t.stride(0) != 1)):
-        raise RuntimeError(f"{fn}: {name} must be an fp32 vector of at least P={P} elements "
-                           "with unit stride")
+def _rows_placement(fn, U, aligned, **others):
+    """The last two checks of a rows-family wrapper: the other operands on U's device, then
+    U and the ``aligned`` ones among them on 16-byte boundaries."""
+    _check_same_device(fn, U, **others)
+    _aligned16(fn, U=U, **{name: others[name] for name in aligned})
 
 
-def _k_tensor(fn, name, t, dtype, shape):
-    """t: a contiguous tensor of ``shape``, (K,) or (K, K), and ``dtype``, fp32 or fp64."""
-    if (not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != shape
-            or not t.is_contiguous()):
-        raise RuntimeError(f"{fn}: {name} must be a contiguous "
-                           f"{'fp32' if dtype == torch.float32 else 'fp64'} "
-                           f"[{', '.join('K' * len(shape))}] = {list(shape)} tensor")
-
-
-def _f64_out(fn, name, t, shape):
-    """An optional output (None: the wrapper allocates it): contiguous fp64 of ``shape``."""
-    if t is not None:
-        _k_tensor(fn, name, t, torch.float64, shape)
-
-
-def _workspace(query_name, K, P, device):
-    """The scratch buffer the library's ``query_name`` asks for (K rows, P elements)."""
-    nbytes = int(getattr(lib(), query_name)(K, P))
+def _workspace_call(entry, query, K, P, head, out, shape, stream):
+    """The tail of the workspace-taking wrappers.  ``head``: the entry point's arguments
+    before (fp64 result, workspace, stream), the matrix U first, tensors as they are;
+    ``out``: the checked result or None (a new fp64 tensor of ``shape``).  Every operand
+    goes through ``_ptr`` before the library is touched (no CPU path); the workspace is
+    what ``query`` asks for, kept alive for a given ``stream``.  Returns out."""
+    U = head[0]
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float64, device=U.device)
+    args = [_ptr(x) if torch.is_tensor(x) else x for x in head] + [_ptr(out)]
+    nbytes = int(getattr(lib(), query)(K, P))
     if nbytes < 0:
-        _check(nbytes, query_name)
-    return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+        _check(nbytes, query)
+    work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=U.device)
+    _check(getattr(lib(), entry)(*args, _ptr(work), _stream(stream, U)), entry)
+    if stream is not None:
+        work.record_stream(stream)
+    return out
+
+
+def _to_one_row(fn, U, ldu, rows, K, param, P, out, stream):
+    """The tail of trimmed_mean and mean_around_median: dls_<fn>_f32 with the rule's ``param``."""
+    _f32_vector(fn, "out", out, P)
+    _rows_placement(fn, U, ("out",), rows=rows, out=out)
+    if P != 0:
+        _check(getattr(lib(), f"dls_{fn}_f32")(_ptr(U), ldu, _ptr(rows), K, param, P, _ptr(out),
+                                               _stream(stream, U)), f"dls_{fn}_f32")
+    return out
 
 
 def trimmed_mean(U, rows, trim, P, out, stream=None):
@@ -286,15 +401,7 @@ def trimmed_mean(U, rows, trim, P, out, stream=None):
     if trim < 0 or 2 * trim >= K:
         raise RuntimeError(f"{fn}: trim={trim} (0 <= 2*trim < K={K})")
     P, ldu = _rows_extent(fn, U, P)
-    _f32_vector(fn, "out", out, P)
-    _check_same_device(fn, U, rows=rows, out=out)
-    if U.data_ptr() % 16 != 0 or out.data_ptr() % 16 != 0:
-        raise RuntimeError(f"{fn}: U and out must be 16-byte aligned")
-    if P == 0:
-        return out
-    _check(lib().dls_trimmed_mean_f32(_ptr(U), ldu, _ptr(rows), K, trim, P, _ptr(out),
-                                      _stream(stream, U)), "dls_trimmed_mean_f32")
-    return out
+    return _to_one_row(fn, U, ldu, rows, K, trim, P, out, stream)
 
 
 def pairwise_sqdist(U, rows, P, out=None, stream=None):
@@ -308,18 +415,9 @@ def pairwise_sqdist(U, rows, P, out=None, stream=None):
     fn = "pairwise_sqdist"
     K, P, ldu = _rows_operands(fn, U, rows, P)
     _f64_out(fn, "out", out, (K, K))
-    _check_same_device(fn, U, rows=rows, out=out)
-    if U.data_ptr() % 16 != 0:
-        raise RuntimeError(f"{fn}: U must be 16-byte aligned")
-    if out is None:
-        out = torch.empty((K, K), dtype=torch.float64, device=U.device)
-    _ptr(U), _ptr(rows), _ptr(out)  # no CPU path
-    work = _workspace("dls_pairwise_sqdist_workspace", K, P, U.device)
-    _check(lib().dls_pairwise_sqdist_f32(_ptr(U), ldu, _ptr(rows), K, P, _ptr(out), _ptr(work),
-                                         _stream(stream, U)), "dls_pairwise_sqdist_f32")
-    if stream is not None:
-        work.record_stream(stream)
-    return out
+    _rows_placement(fn, U, (), rows=rows, out=out)
+    return _workspace_call("dls_pairwise_sqdist_f32", "dls_pairwise_sqdist_workspace", K, P,
+                           (U, ldu, rows, K, P), out, (K, K), stream)
 
 
 def rows_gram(U, rows, P, base=None, out=None, stream=None):
@@ -337,18 +435,9 @@ def rows_gram(U, rows, P, base=None, out=None, stream=None):
     if base is not None:
         _f32_vector(fn, "base", base, P)
     _f64_out(fn, "out", out, (K, K))
-    _check_same_device(fn, U, rows=rows, base=base, out=out)
-    if U.data_ptr() % 16 != 0 or (base is not None and base.data_ptr() % 16 != 0):
-        raise RuntimeError(f"{fn}: U and base must be 16-byte aligned")
-    if out is None:
-        out = torch.empty((K, K), dtype=torch.float64, device=U.device)
-    _ptr(U), _ptr(rows), _ptr(base), _ptr(out)  # no CPU path
-    work = _workspace("dls_rows_gram_workspace", K, P, U.device)
-    _check(lib().dls_rows_gram_f32(_ptr(U), ldu, _ptr(rows), K, P, _ptr(base), _ptr(out),
-                                   _ptr(work), _stream(stream, U)), "dls_rows_gram_f32")
-    if stream is not None:
-        work.record_stream(stream)
-    return out
+    _rows_placement(fn, U, ("base",), rows=rows, base=base, out=out)
+    return _workspace_call("dls_rows_gram_f32", "dls_rows_gram_workspace", K, P,
+                           (U, ldu, rows, K, P, base), out, (K, K), stream)
 
 
 def history_gram(U, rows, H, hrows, P, base=None, out=None, stream=None):
@@ -369,10 +458,7 @@ def history_gram(U, rows, H, hrows, P, base=None, out=None, stream=None):
     if base is not None:
         _f32_vector(fn, "base", base, P)
     _f64_out(fn, "out", out, (K, K))
-    _check_same_device(fn, U, rows=rows, H=H, hrows=hrows, base=base, out=out)
-    if U.data_ptr() % 16 != 0 or H.data_ptr() % 16 != 0 \
-            or (base is not None and base.data_ptr() % 16 != 0):
-        raise RuntimeError(f"{fn}: U, H and base must be 16-byte aligned")
+    _rows_placement(fn, U, ("H", "base"), rows=rows, H=H, hrows=hrows, base=base, out=out)
     if _overlaps(H, U) or (base is not None and _overlaps(H, base)):
         raise RuntimeError(f"{fn}: H must not overlap U or base")
     _ptr(U), _ptr(rows), _ptr(H), _ptr(hrows), _ptr(base)  # no CPU path
@@ -382,15 +468,8 @@ def history_gram(U, rows, H, hrows, P, base=None, out=None, stream=None):
             raise RuntimeError(f"{fn}: {name} {idx} outside the matrix's {n} rows")
         if name == "hrows" and len(set(idx)) != K:
             raise RuntimeError(f"{fn}: hrows must be distinct, not {idx}")
-    if out is None:
-        out = torch.empty((K, K), dtype=torch.float64, device=U.device)
-    work = _workspace("dls_rows_gram_workspace", K, P, U.device)
-    _check(lib().dls_history_gram_f32(_ptr(U), ldu, _ptr(rows), _ptr(H), ldh, _ptr(hrows), K, P,
-                                      _ptr(base), _ptr(out), _ptr(work), _stream(stream, U)),
-           "dls_history_gram_f32")
-    if stream is not None:
-        work.record_stream(stream)
-    return H, out
+    return H, _workspace_call("dls_history_gram_f32", "dls_rows_gram_workspace", K, P,
+                              (U, ldu, rows, H, ldh, hrows, K, P, base), out, (K, K), stream)
 
 
 def mean_around_median(U, rows, keep, P, out, stream=None):
@@ -407,15 +486,7 @@ def mean_around_median(U, rows, keep, P, out, stream=None):
     keep = int(keep)
     if not 1 <= keep <= K:
         raise RuntimeError(f"{fn}: keep={keep} (1 <= keep <= K={K})")
-    _f32_vector(fn, "out", out, P)
-    _check_same_device(fn, U, rows=rows, out=out)
-    if U.data_ptr() % 16 != 0 or out.data_ptr() % 16 != 0:
-        raise RuntimeError(f"{fn}: U and out must be 16-byte aligned")
-    if P == 0:
-        return out
-    _check(lib().dls_mean_around_median_f32(_ptr(U), ldu, _ptr(rows), K, keep, P, _ptr(out),
-                                            _stream(stream, U)), "dls_mean_around_median_f32")
-    return out
+    return _to_one_row(fn, U, ldu, rows, K, keep, P, out, stream)
 
 
 def craft_rows(U, hrows, arows, a, b, P, base=None, stream=None):
@@ -437,9 +508,7 @@ def craft_rows(U, hrows, arows, a, b, P, base=None, stream=None):
         raise RuntimeError(f"{fn}: a={a} and b={b} must be finite")
     if base is not None:
         _f32_vector(fn, "base", base, P)
-    _check_same_device(fn, U, hrows=hrows, arows=arows, base=base)
-    if U.data_ptr() % 16 != 0 or (base is not None and base.data_ptr() % 16 != 0):
-        raise RuntimeError(f"{fn}: U and base must be 16-byte aligned")
+    _rows_placement(fn, U, ("base",), hrows=hrows, arows=arows, base=base)
     _ptr(U), _ptr(hrows), _ptr(arows), _ptr(base)  # no CPU path
     if P == 0:
         return U
@@ -461,18 +530,20 @@ def rows_sqdist_to(U, rows, P, z, out=None, stream=None):
     K, P, ldu = _rows_operands(fn, U, rows, P)
     _f32_vector(fn, "z", z, P)
     _f64_out(fn, "out", out, (K,))
-    _check_same_device(fn, U, rows=rows, z=z, out=out)
-    if U.data_ptr() % 16 != 0 or z.data_ptr() % 16 != 0:
-        raise RuntimeError(f"{fn}: U and z must be 16-byte aligned")
-    if out is None:
-        out = torch.empty((K,), dtype=torch.float64, device=U.device)
-    _ptr(U), _ptr(rows), _ptr(z), _ptr(out)  # no CPU path
-    work = _workspace("dls_weiszfeld_workspace", K, P, U.device)
-    _check(lib().dls_rows_sqdist_to_f32(_ptr(U), ldu, _ptr(rows), K, P, _ptr(z), _ptr(out),
-                                        _ptr(work), _stream(stream, U)), "dls_rows_sqdist_to_f32")
-    if stream is not None:
-        work.record_stream(stream)
-    return out
+    _rows_placement(fn, U, ("z",), rows=rows, z=z, out=out)
+    return _workspace_call("dls_rows_sqdist_to_f32", "dls_weiszfeld_workspace", K, P,
+                           (U, ldu, rows, K, P, z), out, (K,), stream)
+
+
+def _fused_step(fn, cname, U, rows, c, P, z, dist2, stream):
+    """weiszfeld_step and centered_clip_step: dls_<fn>_f32 on the coefficients ``cname``."""
+    K, P, ldu = _rows_operands(fn, U, rows, P)
+    _k_tensor(fn, cname, c, torch.float32, (K,))
+    _f32_vector(fn, "z", z, P)
+    _f64_out(fn, "dist2", dist2, (K,))
+    _rows_placement(fn, U, ("z",), rows=rows, **{cname: c}, z=z, dist2=dist2)
+    return z, _workspace_call(f"dls_{fn}_f32", "dls_weiszfeld_workspace", K, P,
+                              (U, ldu, rows, K, c, P, z), dist2, (K,), stream)
 
 
 def weiszfeld_step(U, rows, w, P, z, dist2=None, stream=None):
@@ -482,24 +553,7 @@ def weiszfeld_step(U, rows, w, P, z, dist2=None, stream=None):
     the rows to that new z (as rows_sqdist_to) from the same read of the rows.  The
     old contents of z are never read.  w: a contiguous fp32 [K] tensor; the rest as in
     rows_sqdist_to.  Returns (z, dist2)."""
-    fn = "weiszfeld_step"
-    K, P, ldu = _rows_operands(fn, U, rows, P)
-    _k_tensor(fn, "w", w, torch.float32, (K,))
-    _f32_vector(fn, "z", z, P)
-    _f64_out(fn, "dist2", dist2, (K,))
-    _check_same_device(fn, U, rows=rows, w=w, z=z, dist2=dist2)
-    if U.data_ptr() % 16 != 0 or z.data_ptr() % 16 != 0:
-        raise RuntimeError(f"{fn}: U and z must be 16-byte aligned")
-    if dist2 is None:
-        dist2 = torch.empty((K,), dtype=torch.float64, device=U.device)
-    _ptr(U), _ptr(rows), _ptr(w), _ptr(z), _ptr(dist2)  # no CPU path
-    work = _workspace("dls_weiszfeld_workspace", K, P, U.device)
-    _check(lib().dls_weiszfeld_step_f32(_ptr(U), ldu, _ptr(rows), K, _ptr(w), P, _ptr(z),
-                                        _ptr(dist2), _ptr(work), _stream(stream, U)),
-           "dls_weiszfeld_step_f32")
-    if stream is not None:
-        work.record_stream(stream)
-    return z, dist2
+    return _fused_step("weiszfeld_step", "w", U, rows, w, P, z, dist2, stream)
 
 
 def centered_clip_step(U, rows, c, P, z, dist2=None, stream=None):
@@ -510,24 +564,7 @@ def centered_clip_step(U, rows, c, P, z, dist2=None, stream=None):
     of the rows to that new z (as rows_sqdist_to) from the same read of the rows.  c: a
     contiguous fp32 [K] tensor (the callers' min(1, tau / distance) / K); the rest as
     in rows_sqdist_to.  Returns (z, dist2)."""
-    fn = "centered_clip_step"
-    K, P, ldu = _rows_operands(fn, U, rows, P)
-    _k_tensor(fn, "c", c, torch.float32, (K,))
-    _f32_vector(fn, "z", z, P)
-    _f64_out(fn, "dist2", dist2, (K,))
-    _check_same_device(fn, U, rows=rows, c=c, z=z, dist2=dist2)
-    if U.data_ptr() % 16 != 0 or z.data_ptr() % 16 != 0:
-        raise RuntimeError(f"{fn}: U and z must be 16-byte aligned")
-    if dist2 is None:
-        dist2 = torch.empty((K,), dtype=torch.float64, device=U.device)
-    _ptr(U), _ptr(rows), _ptr(c), _ptr(z), _ptr(dist2)  # no CPU path
-    work = _workspace("dls_weiszfeld_workspace", K, P, U.device)
-    _check(lib().dls_centered_clip_step_f32(_ptr(U), ldu, _ptr(rows), K, _ptr(c), P, _ptr(z),
-                                            _ptr(dist2), _ptr(work), _stream(stream, U)),
-           "dls_centered_clip_step_f32")
-    if stream is not None:
-        work.record_stream(stream)
-    return z, dist2
+    return _fused_step("centered_clip_step", "c", U, rows, c, P, z, dist2, stream)
 
 
 # DLS_SERVER_OPT_* (include/dls_hip.h): the kinds, and the launch shape of the step
@@ -587,18 +624,10 @@ def server_opt_step(kind, agg, x, m, v, out, P, lr, beta1, beta2, tau, stream=No
     given = {name: t for name, t in ops.items() if not (t is None and name in ("m", "v"))}
     for name, t in given.items():
         _f32_vector(fn, name, t, P)
-    for name, t in given.items():  # (_check_same_device names its first operand x)
-        if t.device != agg.device:
-            raise RuntimeError(f"{fn}: {name} is on {t.device}, agg on {agg.device}")
-    names = list(given)
-    for i, a in enumerate(names):
-        for b in names[i + 1:]:
-            ta, tb = given[a][:P], given[b][:P]
-            if (a, b) == ("x", "out") and ta.data_ptr() == tb.data_ptr():
-                continue
-            if _overlaps(ta, tb):
-                raise RuntimeError(f"{fn}: {a} and {b} overlap (out may be x itself, nothing "
-                                   "else may overlap)")
+    _check_same_device(fn, agg, _anchor="agg", **given)
+    _check_disjoint({name: t[:P] for name, t in given.items()},
+                    f"{fn}: {{a}} and {{b}} overlap (out may be x itself, nothing else may overlap)",
+                    allowed=lambda a, b: (a, b) == ("x", "out") and x.data_ptr() == out.data_ptr())
     for t in given.values():
         _ptr(t)  # no CPU path
     if P == 0:
@@ -611,23 +640,6 @@ def server_opt_step(kind, agg, x, m, v, out, P, lr, beta1, beta2, tau, stream=No
 
 # ------------------------------------------------------- top-k sparsification
 TOPK_MAX_P = (1 << 31) - 1  # idx is int32
-
-
-def _topk_vector(fn, name, t, dtype, n, exact=False):
-    """t: a ``dtype`` vector with unit stride of at least (``exact``: exactly) n elements."""
-    what = {torch.float32: "fp32", torch.int32: "int32", torch.int64: "int64"}[dtype]
-    if (not torch.is_tensor(t) or t.dtype != dtype or t.dim() != 1
-            or (t.numel() != n if exact else t.numel() < n)
-            or (t.numel() > 1 and t.stride(0) != 1)):
-        raise RuntimeError(f"{fn}: {name} must be an {what} vector of "
-                           f"{'exactly' if exact else 'at least'} {n} elements with unit stride")
-
-
-def _topk_one_device(fn, **tensors):
-    (first, t0), *rest = tensors.items()
-    for name, t in rest:
-        if t.device != t0.device:
-            raise RuntimeError(f"{fn}: {name} is on {t.device}, {first} on {t0.device}")
 
 
 def _topk_extent(fn, P):
@@ -663,28 +675,22 @@ def topk_compress(w, base, e, k, P, idx, val, stats, workspace, stream=None):
         raise RuntimeError(f"{fn}: k={k!r} must be an integer in 1..P={P}")
     for name, t in (("w", w), ("base", base), ("e", e)):
         _f32_vector(fn, name, t, P)
-    _topk_vector(fn, "idx", idx, torch.int32, k)
-    _topk_vector(fn, "val", val, torch.float32, k)
-    _topk_vector(fn, "stats", stats, torch.int32, 2)
+    _unit_vector(fn, "idx", idx, torch.int32, k)
+    _unit_vector(fn, "val", val, torch.float32, k)
+    _unit_vector(fn, "stats", stats, torch.int32, 2)
     need = int(lib().dls_topk_workspace(P))
-    if (not torch.is_tensor(workspace) or workspace.dtype != torch.uint8 or workspace.dim() != 1
-            or workspace.numel() < need or (workspace.numel() > 1 and workspace.stride(0) != 1)):
-        raise RuntimeError(f"{fn}: workspace must be a uint8 vector of at least {need} bytes "
-                           "(topk_workspace(P))")
-    _topk_one_device(fn, w=w, base=base, e=e, idx=idx, val=val, stats=stats, workspace=workspace)
+    _check_tensor(fn, "workspace", workspace, torch.uint8, need, lambda: "a uint8 vector of at "
+                  f"least {need} bytes (topk_workspace(P))", exact=False, contiguous=False)
+    _check_same_device(fn, w, _anchor="w", base=base, e=e, idx=idx, val=val, stats=stats,
+                       workspace=workspace)
     for name, other in (("w", w), ("base", base)):
         if _overlaps(e[:P], other[:P]):
             raise RuntimeError(f"{fn}: e and {name} overlap (the residual is updated in place)")
-    outs = {"e": e[:P], "idx": idx[:k], "val": val[:k], "stats": stats[:2], "workspace": workspace}
-    names = list(outs)
-    for i, a in enumerate(names):
-        for b in names[i + 1:]:
-            if _overlaps(outs[a], outs[b]):
-                raise RuntimeError(f"{fn}: {a} and {b} overlap")
+    _check_disjoint({"e": e[:P], "idx": idx[:k], "val": val[:k], "stats": stats[:2],
+                     "workspace": workspace}, f"{fn}: {{a}} and {{b}} overlap")
     for name, t in (("w", w), ("base", base), ("e", e), ("idx", idx), ("val", val),
                     ("workspace", workspace)):
-        if t.data_ptr() % 16 != 0:
-            raise RuntimeError(f"{fn}: {name} must be 16-byte aligned")
+        _aligned16(fn, **{name: t})
     for t in (w, base, e, idx, val, stats, workspace):
         _ptr(t)  # no CPU path
     _check(lib().dls_topk_compress_f32(_ptr(w), _ptr(base), _ptr(e), P, k, _ptr(idx), _ptr(val),
@@ -707,26 +713,25 @@ def sparse_fedavg(base, idx, val, off, weight, total, P, out, stream=None):
     P = _topk_extent(fn, P)
     _f32_vector(fn, "base", base, P)
     _f32_vector(fn, "out", out, P)
-    if not torch.is_tensor(weight) or weight.dtype != torch.float32 or weight.dim() != 1 \
-            or not weight.is_contiguous() or weight.numel() < 1:
-        raise RuntimeError(f"{fn}: weight must be a contiguous fp32 [K] tensor, K >= 1")
+    # 1-D with unit stride and at least one element: contiguous [K], K >= 1
+    _check_tensor(fn, "weight", weight, torch.float32, 1, "a contiguous fp32 [K] tensor, K >= 1",
+                  exact=False, contiguous=False)
     K = weight.numel()
-    _topk_vector(fn, "off", off, torch.int64, K + 1, exact=True)
+    _unit_vector(fn, "off", off, torch.int64, K + 1, exact=True)
     if not torch.is_tensor(idx) or not torch.is_tensor(val):
         raise RuntimeError(f"{fn}: idx and val must be tensors")
-    _topk_vector(fn, "idx", idx, torch.int32, idx.numel() if idx.dim() == 1 else -1, exact=True)
-    _topk_vector(fn, "val", val, torch.float32, idx.numel(), exact=True)
+    _unit_vector(fn, "idx", idx, torch.int32, idx.numel() if idx.dim() == 1 else -1, exact=True)
+    _unit_vector(fn, "val", val, torch.float32, idx.numel(), exact=True)
     total = fl32(total)
     if not math.isfinite(total) or total <= 0.0:
         raise RuntimeError(f"{fn}: total={total} must be a positive finite number")
-    _topk_one_device(fn, base=base, idx=idx, val=val, off=off, weight=weight, out=out)
+    _check_same_device(fn, base, _anchor="base", idx=idx, val=val, off=off, weight=weight, out=out)
     if _overlaps(out[:P], base[:P]):
         raise RuntimeError(f"{fn}: out and base overlap (untouched coordinates are copied)")
     for name, t in (("idx", idx), ("val", val), ("off", off), ("weight", weight)):
         if t.numel() and _overlaps(out[:P], t):
             raise RuntimeError(f"{fn}: out and {name} overlap")
-    if base.data_ptr() % 16 != 0 or out.data_ptr() % 16 != 0:
-        raise RuntimeError(f"{fn}: base and out must be 16-byte aligned")
+    _aligned16(fn, base=base, out=out)
     for t in (base, idx, val, off, weight, out):
         _ptr(t)  # no CPU path
     has = idx.numel() > 0  # an empty tensor's pointer means nothing: hand the library null
@@ -899,9 +904,8 @@ def quantize_u8(x, seg_off, total, scale, zp, q, deq=None, stochastic=False, see
 # whatever would send them out of bounds before any pointer reaches the library.
 
 def _check_f32_vector(fn, name, t, n, device):
-    if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.numel() != n
-            or not t.is_contiguous() or t.device != device):
-        raise RuntimeError(f"{fn}: {name} must be a contiguous fp32 tensor of {n} elements on {device}")
+    _check_tensor(fn, name, t, torch.float32, n,
+                  lambda: f"a contiguous fp32 tensor of {n} elements on {device}", device=device)
 
 
 def _check_bn_module(fn, bn, device):
@@ -1017,12 +1021,6 @@ def bn_act_exact(x, consts, residual=None, relu=True, out=None, inplace=False, s
 # as int16 — activations [B, H, W, 2C] (per pixel C hi then C lo), weights
 # [Cout, 2K] (K hi then K lo, k = (ky*KW + kx)*Cp + ci).
 
-def _check_same_device(fn, x, **others):
-    for name, t in others.items():
-        if t is not None and t.device != x.device:
-            raise RuntimeError(f"{fn}: {name} is on {t.device}, the input on {x.device}")
-
-
 def _check_consts(fn, consts, cout, device):
     """Eval batch-norm constants [mean | iv | w | b] x Cout: the kernels read them as
     16-byte vectors at consts + t * Cout + co."""
@@ -1034,11 +1032,17 @@ def _check_consts(fn, consts, cout, device):
                            f"elements on {device}")
 
 
-def _overlaps(a, b):
-    """True if the storage ranges of a and b intersect."""
-    a0 = a.data_ptr()
-    b0 = b.data_ptr()
-    return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+def _check_nchw(fn, x, what="x must be a contiguous NCHW fp32 tensor"):
+    if x.dtype != torch.float32 or x.dim() != 4 or not x.is_contiguous():
+        raise RuntimeError(f"{fn}: {what}")
+    return x.shape
+
+
+_WEIGHTS_4D = "w must be a contiguous fp32 [Cout, Cin, KH, KW]"
+
+
+def _conv_out_hw(H, W, ksize, stride, pad):
+    return (H + 2 * pad - ksize[0]) // stride + 1, (W + 2 * pad - ksize[1]) // stride + 1
 
 
 def split_channels(c):
@@ -1098,9 +1102,7 @@ def sign_vote_wave_ranges(P, K, cus=0, first_wave=0, count=None):
 
 def conv_pack_input(x, stream=None):
     """NCHW fp32 [B, C, H, W] -> split NHWC [B, H, W, 2 Cp] (zeros beyond C)."""
-    if x.dtype != torch.float32 or x.dim() != 4 or not x.is_contiguous():
-        raise RuntimeError("conv_pack_input: x must be a contiguous NCHW fp32 tensor")
-    B, C, H, W = x.shape
+    B, C, H, W = _check_nchw("conv_pack_input", x)
     cp = split_channels(C)
     out = torch.empty((B, H, W, 2 * cp), dtype=torch.int16, device=x.device)
     _check(lib().dls_conv_pack_input_f32(_ptr(x), B, C, H, W, cp, _ptr(out), _stream(stream, x)),
@@ -1111,9 +1113,7 @@ def conv_pack_input(x, stream=None):
 def conv_pack_weights(w, stream=None):
     """fp32 [Cout, Cin, KH, KW] -> split weights [Cout, 2K] with K = KH*KW*Cp."""
     w = w.detach()
-    if w.dtype != torch.float32 or w.dim() != 4 or not w.is_contiguous():
-        raise RuntimeError("conv_pack_weights: w must be a contiguous fp32 [Cout, Cin, KH, KW]")
-    co, ci, kh, kw = w.shape
+    co, ci, kh, kw = _check_nchw("conv_pack_weights", w, _WEIGHTS_4D)
     cp = split_channels(ci)
     out = torch.empty((co, 2 * kh * kw * cp), dtype=torch.int16, device=w.device)
     _check(lib().dls_conv_pack_weights_f32(_ptr(w), co, ci, kh, kw, cp, _ptr(out),
@@ -1125,12 +1125,10 @@ def conv_pack_im2col(x, ksize, stride, pad, stream=None):
     """NCHW fp32 [B, C, H, W] -> the split NHWC im2col [B, Ho, Wo, 2 Kp] of a
     (KH, KW) convolution, Kp = KH*KW*C rounded up to 32: the operand of a 1x1
     conv_bn_act with conv_pack_weights_im2col weights (few-channel first layers)."""
-    if x.dtype != torch.float32 or x.dim() != 4 or not x.is_contiguous():
-        raise RuntimeError("conv_pack_im2col: x must be a contiguous NCHW fp32 tensor")
-    B, C, H, W = x.shape
+    B, C, H, W = _check_nchw("conv_pack_im2col", x)
     kh, kw = ksize
     kp = split_channels(kh * kw * C)
-    ho, wo = (H + 2 * pad - kh) // stride + 1, (W + 2 * pad - kw) // stride + 1
+    ho, wo = _conv_out_hw(H, W, ksize, stride, pad)
     out = torch.empty((B, ho, wo, 2 * kp), dtype=torch.int16, device=x.device)
     _check(lib().dls_conv_pack_im2col_f32(_ptr(x), B, C, H, W, kh, kw, stride, pad, kp, _ptr(out),
                                           _stream(stream, x)), "dls_conv_pack_im2col_f32")
@@ -1140,9 +1138,7 @@ def conv_pack_im2col(x, ksize, stride, pad, stream=None):
 def conv_pack_weights_im2col(w, stream=None):
     """fp32 [Cout, Cin, KH, KW] -> split weights [Cout, 2 Kp] in conv_pack_im2col's k order."""
     w = w.detach()
-    if w.dtype != torch.float32 or w.dim() != 4 or not w.is_contiguous():
-        raise RuntimeError("conv_pack_weights_im2col: w must be a contiguous fp32 [Cout, Cin, KH, KW]")
-    co, ci, kh, kw = w.shape
+    co, ci, kh, kw = _check_nchw("conv_pack_weights_im2col", w, _WEIGHTS_4D)
     kp = split_channels(kh * kw * ci)
     out = torch.empty((co, 2 * kp), dtype=torch.int16, device=w.device)
     _check(lib().dls_conv_pack_weights_im2col_f32(_ptr(w), co, ci, kh, kw, kp, _ptr(out),
@@ -1157,7 +1153,7 @@ def conv_bn_act(x, w, ksize, stride, pad, consts=None, residual=None, relu=True,
     B, H, W, c2 = x.shape
     kh, kw = ksize
     cout = w.shape[0]
-    ho, wo = (H + 2 * pad - kh) // stride + 1, (W + 2 * pad - kw) // stride + 1
+    ho, wo = _conv_out_hw(H, W, ksize, stride, pad)
     if x.dtype != torch.int16 or w.dtype != torch.int16 or not (x.is_contiguous() and w.is_contiguous()):
         raise RuntimeError("conv_bn_act: split int16 contiguous operands expected")
     if w.shape[1] != kh * kw * c2:
@@ -1190,16 +1186,14 @@ def conv_stem_bn_act(x, w, ksize, stride, pad, consts=None, relu=True, stream=No
     """A few-channel first layer straight from the NCHW fp32 batch x (the im2col
     fused; KH*KW*C <= 32): y = act(bn(conv(x))) split NHWC
     (dls_conv_stem_bn_act_f32); w from conv_pack_weights_im2col."""
-    if x.dtype != torch.float32 or x.dim() != 4 or not x.is_contiguous():
-        raise RuntimeError("conv_stem_bn_act: x must be a contiguous NCHW fp32 tensor")
-    B, C, H, W = x.shape
+    B, C, H, W = _check_nchw("conv_stem_bn_act", x)
     kh, kw = ksize
     cout = w.shape[0]
     if w.dtype != torch.int16 or w.shape[1] != 2 * 32 or not w.is_contiguous():
         raise RuntimeError("conv_stem_bn_act: w must be conv_pack_weights_im2col output with Kp = 32")
     _check_same_device("conv_stem_bn_act", x, w=w)
     _check_consts("conv_stem_bn_act", consts, cout, x.device)
-    ho, wo = (H + 2 * pad - kh) // stride + 1, (W + 2 * pad - kw) // stride + 1
+    ho, wo = _conv_out_hw(H, W, ksize, stride, pad)
     out = torch.empty((B, ho, wo, 2 * cout), dtype=torch.int16, device=x.device)
     _check(lib().dls_conv_stem_bn_act_f32(_ptr(x), B, C, H, W, _ptr(w), cout, kh, kw, stride, pad,
                                           _ptr(consts), int(bool(relu)), _ptr(out),
@@ -1240,6 +1234,11 @@ def lenet5_shapes(num_out):
             (num_out, 84), (num_out,))
 
 
+def _check_labels(fn, labels, B):
+    if labels.dtype != torch.int64 or tuple(labels.shape) != (B,) or not labels.is_contiguous():
+        raise RuntimeError(f"{fn}: labels must be a contiguous int64 [B] tensor")
+
+
 def _loss_rows(fn, loss, S, B):
     """The row pitch of a per-image loss output: fp32 [S, B] with unit element
     stride, rows at any pitch >= B (a column window of a wider [S, n] buffer)."""
@@ -1247,7 +1246,7 @@ def _loss_rows(fn, loss, S, B):
             or (B > 1 and loss.stride(1) != 1) or (S > 1 and loss.stride(0) < B)):
         raise RuntimeError(f"{fn}: loss must be fp32 [S, B] with unit element stride and a row "
                            "pitch of at least B")
-    return loss.stride(0) if S > 1 else B
+    return _row_pitch(loss)
 
 
 def softmax_ce(logits, labels, loss=None, stream=None):
@@ -1260,8 +1259,7 @@ def softmax_ce(logits, labels, loss=None, stream=None):
     if logits.dtype != torch.float32 or logits.dim() != 3 or not logits.is_contiguous():
         raise RuntimeError(f"{fn}: logits must be a contiguous fp32 [S, B, O] tensor")
     S, B, O = logits.shape
-    if labels.dtype != torch.int64 or tuple(labels.shape) != (B,) or not labels.is_contiguous():
-        raise RuntimeError(f"{fn}: labels must be a contiguous int64 [B] tensor")
+    _check_labels(fn, labels, B)
     if loss is None:
         loss = torch.empty((S, B), dtype=torch.float32, device=logits.device)
     _check_same_device(fn, logits, labels=labels, loss=loss)
@@ -1286,7 +1284,7 @@ def sum_rows_f64(v, out=None, stream=None):
     elif out.dtype != torch.float64 or tuple(out.shape) != (S,) or not out.is_contiguous():
         raise RuntimeError(f"{fn}: out must be a contiguous fp64 [S] tensor")
     _check_same_device(fn, v, out=out)
-    ldn = v.stride(0) if S > 1 else n
+    ldn = _row_pitch(v)
     # an empty tensor may have no storage: nothing of v is read when n == 0, so any
     # valid device address serves
     vp = _ptr(v) if n > 0 or v.data_ptr() else _ptr(out)
@@ -1325,9 +1323,8 @@ def lenet5_eval(models, offsets, x, labels=None, logits=None, correct=None, stre
                            " and / or loss [S, B]")
     _check_same_device(fn, x, models=models, labels=labels, logits=logits, correct=correct,
                        loss=loss)
-    if labels is not None and (labels.dtype != torch.int64 or tuple(labels.shape) != (B,)
-                               or not labels.is_contiguous()):
-        raise RuntimeError(f"{fn}: labels must be a contiguous int64 [B] tensor")
+    if labels is not None:
+        _check_labels(fn, labels, B)
     if correct is not None:
         if labels is None:
             raise RuntimeError(f"{fn}: correct needs labels")
@@ -1343,7 +1340,7 @@ def lenet5_eval(models, offsets, x, labels=None, logits=None, correct=None, stre
         num_out = logits.shape[2]
     elif num_out is None:
         raise RuntimeError(f"{fn}: num_out is needed without logits")
-    ldm = models.stride(0) if S > 1 else models.shape[1]
+    ldm = _row_pitch(models)
     if loss is not None:
         if labels is None:
             raise RuntimeError(f"{fn}: loss needs labels")

@@ -41,7 +41,7 @@
 // ceil(periods / kMaxWaves)): pairdist.hip's plan with half its waves.  The kernels
 // take 256 VGPRs, so one wave per SIMD is resident: 1024 waves fill the device in one
 // round, and every wave costs 32 KiB of partials written and read back.
-#include "dls_common.h"
+#include "rows_common.h"
 
 namespace dls {
 namespace {
@@ -316,26 +316,20 @@ void launch(const float *U, int64_t ldu, const int32_t *rows, float *H, int64_t 
                        (const double *)part, pl.nW, K, Gm);
 }
 
-// The checks both entry points share (H == nullptr: the read-only call), then the
-// launches.
-int run_gram(const char *fn, const float *U, int64_t ldu, const int32_t *rows, float *H,
-             int64_t ldh, const int32_t *hrows, int32_t K, int64_t P, const float *base, double *Gm,
-             void *workspace, dls_stream_t stream) {
-    DLS_REQUIRE(K >= 1 && K <= DLS_ROBUST_MAX_K, DLS_EINVAL, "%s: K=%d (1..DLS_ROBUST_MAX_K=%d)",
-                fn, K, DLS_ROBUST_MAX_K);
-    DLS_REQUIRE(P >= 0, DLS_EINVAL, "%s: P=%lld", fn, (long long)P);
-    DLS_REQUIRE(P % 4 == 0 && ldu % 4 == 0 && ldu >= P && ldh % 4 == 0 && ldh >= P, DLS_ELAYOUT,
-                "%s: P=%lld, ldu=%lld and ldh=%lld must be multiples of 4, ldu and ldh >= P", fn,
-                (long long)P, (long long)ldu, (long long)ldh);
-    DLS_REQUIRE(aligned16(U) && aligned16(H) && aligned16(base) && aligned16(workspace) &&
-                    (reinterpret_cast<uintptr_t>(Gm) & 7u) == 0,
-                DLS_ELAYOUT, "%s: 16-byte alignment (U, H, base, workspace), 8-byte (G)", fn);
+// The checks both entry points share (rows_common.h; nonnull: the entry point's own
+// pointers; H == nullptr: the read-only call), then the launches.
+int run_gram(const char *fn, bool nonnull, const float *U, int64_t ldu, const int32_t *rows,
+             float *H, int64_t ldh, const int32_t *hrows, int32_t K, int64_t P, const float *base,
+             double *Gm, void *workspace, dls_stream_t stream) {
+    int rc = check_head(fn, nonnull, "K", K);
+    if (rc == DLS_OK)
+        rc = check_layout(fn, ldu, P,
+                          aligned16(U) && aligned16(H) && aligned16(base) &&
+                              aligned16(workspace) && aligned_to(Gm, 8),
+                          " (U, H, base, workspace), 8-byte (G)", &ldh);
+    if (rc != DLS_OK) return rc;
     hipStream_t st = as_stream(stream);
-    if (P == 0) {
-        const hipError_t e = hipMemsetAsync(Gm, 0, (size_t)K * K * sizeof(double), st);
-        DLS_REQUIRE(e == hipSuccess, (int)e, "%s: %s", fn, hipGetErrorString(e));
-        return DLS_OK;
-    }
+    if (P == 0) return zero_f64(fn, Gm, (size_t)K * K, st);
     double *part = static_cast<double *>(workspace);
     switch (grid_of(K)) {
         case 1: launch<1>(U, ldu, rows, H, ldh, hrows, K, P, base, Gm, part, st); break;
@@ -352,26 +346,21 @@ int run_gram(const char *fn, const float *U, int64_t ldu, const int32_t *rows, f
 using namespace dls;
 
 extern "C" int64_t dls_rows_gram_workspace(int32_t K, int64_t P) {
-    DLS_REQUIRE(K >= 1 && K <= DLS_ROBUST_MAX_K, DLS_EINVAL,
-                "dls_rows_gram_workspace: K=%d (1..DLS_ROBUST_MAX_K=%d)", K, DLS_ROBUST_MAX_K);
-    DLS_REQUIRE(P >= 0, DLS_EINVAL, "dls_rows_gram_workspace: P=%lld", (long long)P);
-    return (int64_t)plan_for(K, P).nW * kPartDoubles * (int64_t)sizeof(double);
+    return workspace_query("dls_rows_gram_workspace", K, P, [&] { return plan_for(K, P).nW; },
+                           kPartDoubles);
 }
 
 extern "C" int dls_rows_gram_f32(const float *U, int64_t ldu, const int32_t *rows, int32_t K,
                                  int64_t P, const float *base, double *G, void *workspace,
                                  dls_stream_t stream) {
-    DLS_REQUIRE(U && rows && G && workspace, DLS_EINVAL, "dls_rows_gram_f32: null pointer");
-    return run_gram("dls_rows_gram_f32", U, ldu, rows, nullptr, ldu, nullptr, K, P, base, G,
-                    workspace, stream);
+    return run_gram("dls_rows_gram_f32", U && rows && G && workspace, U, ldu, rows, nullptr, ldu,
+                    nullptr, K, P, base, G, workspace, stream);
 }
 
 extern "C" int dls_history_gram_f32(const float *U, int64_t ldu, const int32_t *rows, float *H,
                                     int64_t ldh, const int32_t *hrows, int32_t K, int64_t P,
                                     const float *base, double *G, void *workspace,
                                     dls_stream_t stream) {
-    DLS_REQUIRE(U && rows && H && hrows && G && workspace, DLS_EINVAL,
-                "dls_history_gram_f32: null pointer");
-    return run_gram("dls_history_gram_f32", U, ldu, rows, H, ldh, hrows, K, P, base, G, workspace,
-                    stream);
+    return run_gram("dls_history_gram_f32", U && rows && H && hrows && G && workspace, U, ldu,
+                    rows, H, ldh, hrows, K, P, base, G, workspace, stream);
 }

@@ -27,7 +27,7 @@
 // Work split (a function of P and K alone, not of the device): a period is FLT
 // tiles (one flush: <= 120 steps); period n belongs to wave n % nW, nW =
 // ceil(periods / ceil(periods / kMaxWaves)).
-#include "dls_common.h"
+#include "rows_common.h"
 
 namespace dls {
 namespace {
@@ -275,33 +275,21 @@ void launch(const float *U, int64_t ldu, const int32_t *rows, int K, int64_t P, 
 using namespace dls;
 
 extern "C" int64_t dls_pairwise_sqdist_workspace(int32_t K, int64_t P) {
-    DLS_REQUIRE(K >= 1 && K <= DLS_ROBUST_MAX_K, DLS_EINVAL,
-                "dls_pairwise_sqdist_workspace: K=%d (1..DLS_ROBUST_MAX_K=%d)", K,
-                DLS_ROBUST_MAX_K);
-    DLS_REQUIRE(P >= 0, DLS_EINVAL, "dls_pairwise_sqdist_workspace: P=%lld", (long long)P);
-    return (int64_t)plan_for(K, P).nW * kPartDoubles * (int64_t)sizeof(double);
+    return workspace_query("dls_pairwise_sqdist_workspace", K, P,
+                           [&] { return plan_for(K, P).nW; }, kPartDoubles);
 }
 
 extern "C" int dls_pairwise_sqdist_f32(const float *U, int64_t ldu, const int32_t *rows, int32_t K,
                                        int64_t P, double *D, void *workspace,
                                        dls_stream_t stream) {
-    DLS_REQUIRE(U && rows && D && workspace, DLS_EINVAL, "dls_pairwise_sqdist_f32: null pointer");
-    DLS_REQUIRE(K >= 1 && K <= DLS_ROBUST_MAX_K, DLS_EINVAL,
-                "dls_pairwise_sqdist_f32: K=%d (1..DLS_ROBUST_MAX_K=%d)", K, DLS_ROBUST_MAX_K);
-    DLS_REQUIRE(P >= 0, DLS_EINVAL, "dls_pairwise_sqdist_f32: P=%lld", (long long)P);
-    DLS_REQUIRE(P % 4 == 0 && ldu % 4 == 0 && ldu >= P, DLS_ELAYOUT,
-                "dls_pairwise_sqdist_f32: P=%lld and ldu=%lld must be multiples of 4, ldu >= P",
-                (long long)P, (long long)ldu);
-    DLS_REQUIRE(aligned16(U) && aligned16(workspace) &&
-                    (reinterpret_cast<uintptr_t>(D) & 7u) == 0,
-                DLS_ELAYOUT,
-                "dls_pairwise_sqdist_f32: 16-byte alignment (U, workspace), 8-byte (D)");
+    const char *fn = "dls_pairwise_sqdist_f32";
+    int rc = check_head(fn, U && rows && D && workspace, "K", K);
+    if (rc == DLS_OK)
+        rc = check_layout(fn, ldu, P, aligned16(U) && aligned16(workspace) && aligned_to(D, 8),
+                          " (U, workspace), 8-byte (D)");
+    if (rc != DLS_OK) return rc;
     hipStream_t st = as_stream(stream);
-    if (P == 0) {
-        const hipError_t e = hipMemsetAsync(D, 0, (size_t)K * K * sizeof(double), st);
-        DLS_REQUIRE(e == hipSuccess, (int)e, "dls_pairwise_sqdist_f32: %s", hipGetErrorString(e));
-        return DLS_OK;
-    }
+    if (P == 0) return zero_f64(fn, D, (size_t)K * K, st);
     double *part = static_cast<double *>(workspace);
     switch (grid_of(K)) {
         case 1: launch<1>(U, ldu, rows, K, P, D, part, st); break;
@@ -309,5 +297,5 @@ extern "C" int dls_pairwise_sqdist_f32(const float *U, int64_t ldu, const int32_
         case 4: launch<4>(U, ldu, rows, K, P, D, part, st); break;
         default: launch<8>(U, ldu, rows, K, P, D, part, st); break;
     }
-    return check_launch("dls_pairwise_sqdist_f32");
+    return check_launch(fn);
 }

@@ -23,7 +23,7 @@
 #include <cmath>
 #include <utility>
 
-#include "dls_common.h"
+#include "rows_common.h"
 
 namespace dls {
 namespace {
@@ -208,7 +208,7 @@ void launch(typename Rule::Rows Uv, int64_t ldu4, const int32_t *rows, int K, co
 inline const f32x4 *vec4(const float *p) { return reinterpret_cast<const f32x4 *>(p); }
 inline f32x4 *vec4(float *p) { return reinterpret_cast<f32x4 *>(p); }
 
-// The operands are checked (below); `fn` names the entry point.
+// The operands are checked (rows_common.h); `fn` names the entry point.
 template <typename Rule>
 int dispatch(const char *fn, typename Rule::Rows Uv, int64_t ldu, const int32_t *rows, int K,
              const Rule &rule, int64_t P, typename Rule::Out out, hipStream_t st) {
@@ -231,28 +231,6 @@ int dispatch(const char *fn, typename Rule::Rows Uv, int64_t ldu, const int32_t 
     else
         launch<Rule, 64, Rule::kW64>(Uv, ldu4, rows, K, rule, P4, out, st);
     return check_launch(fn);
-}
-
-// The operand checks the entry points share, in the order they are made: the head,
-// the rule's own parameter (at the entry point), the layout.
-int check_count(const char *fn, const char *name, int32_t K) {
-    DLS_REQUIRE(K >= 1 && K <= DLS_ROBUST_MAX_K, DLS_EINVAL, "%s: %s=%d (1..DLS_ROBUST_MAX_K=%d)",
-                fn, name, K, DLS_ROBUST_MAX_K);
-    return DLS_OK;
-}
-
-int check_head(const char *fn, bool nonnull, const char *name, int32_t K) {
-    DLS_REQUIRE(nonnull, DLS_EINVAL, "%s: null pointer", fn);
-    return check_count(fn, name, K);
-}
-
-int check_layout(const char *fn, int64_t ldu, int64_t P, bool aligned) {
-    DLS_REQUIRE(P >= 0, DLS_EINVAL, "%s: P=%lld", fn, (long long)P);
-    DLS_REQUIRE(P % 4 == 0 && ldu % 4 == 0 && ldu >= P, DLS_ELAYOUT,
-                "%s: P=%lld and ldu=%lld must be multiples of 4, ldu >= P", fn, (long long)P,
-                (long long)ldu);
-    DLS_REQUIRE(aligned, DLS_ELAYOUT, "%s: 16-byte alignment", fn);
-    return DLS_OK;
 }
 
 // ---------------------------------------------------------------- the rules

@@ -30,7 +30,7 @@
 // n % nW as its visit n / nW, nW = ceil(tiles / ceil(tiles / kMaxWaves)).
 #include <type_traits>
 
-#include "dls_common.h"
+#include "rows_common.h"
 
 namespace dls {
 namespace {
@@ -240,29 +240,23 @@ void dispatch(const float *U, int64_t ldu, const int32_t *rows, int K, const flo
         launch<64, 2, MODE>(U, ldu, rows, K, w, P, z, dist2, part, st);
 }
 
-// The operand checks the entry points share; `fn` names the caller.
-int check_operands(const char *fn, const float *U, int64_t ldu, const int32_t *rows, int32_t K,
-                   int64_t P, const float *z, const double *dist2, const void *workspace,
-                   const float *w, bool step) {
-    DLS_REQUIRE(U && rows && z && dist2 && workspace && (w || !step), DLS_EINVAL,
-                "%s: null pointer", fn);
-    DLS_REQUIRE(K >= 1 && K <= DLS_ROBUST_MAX_K, DLS_EINVAL, "%s: K=%d (1..DLS_ROBUST_MAX_K=%d)",
-                fn, K, DLS_ROBUST_MAX_K);
-    DLS_REQUIRE(P >= 0, DLS_EINVAL, "%s: P=%lld", fn, (long long)P);
-    DLS_REQUIRE(P % 4 == 0 && ldu % 4 == 0 && ldu >= P, DLS_ELAYOUT,
-                "%s: P=%lld and ldu=%lld must be multiples of 4, ldu >= P", fn, (long long)P,
-                (long long)ldu);
-    DLS_REQUIRE(aligned16(U) && aligned16(z) && aligned16(workspace) &&
-                    (reinterpret_cast<uintptr_t>(dist2) & 7u) == 0 &&
-                    (reinterpret_cast<uintptr_t>(w) & 3u) == 0,
-                DLS_ELAYOUT, "%s: 16-byte alignment (U, z, workspace), 8-byte (dist2)", fn);
-    return DLS_OK;
-}
-
-int zero_dist2(const char *fn, double *dist2, int K, hipStream_t st) {
-    const hipError_t e = hipMemsetAsync(dist2, 0, (size_t)K * sizeof(double), st);
-    DLS_REQUIRE(e == hipSuccess, (int)e, "%s: %s", fn, hipGetErrorString(e));
-    return DLS_OK;
+// The checks the entry points share (rows_common.h; nonnull: the entry point's own
+// pointers; w: the step's coefficients, null for the read-only call), then the launches.
+template <Mode MODE>
+int run_step(const char *fn, bool nonnull, const float *U, int64_t ldu, const int32_t *rows,
+             int32_t K, const float *w, int64_t P, float *z, double *dist2, void *workspace,
+             dls_stream_t stream) {
+    int rc = check_head(fn, nonnull, "K", K);
+    if (rc == DLS_OK)
+        rc = check_layout(fn, ldu, P,
+                          aligned16(U) && aligned16(z) && aligned16(workspace) &&
+                              aligned_to(dist2, 8) && aligned_to(w, 4),
+                          " (U, z, workspace), 8-byte (dist2)");
+    if (rc != DLS_OK) return rc;
+    hipStream_t st = as_stream(stream);
+    if (P == 0) return zero_f64(fn, dist2, K, st);
+    dispatch<MODE>(U, ldu, rows, K, w, P, z, dist2, static_cast<double *>(workspace), st);
+    return check_launch(fn);
 }
 
 }  // namespace
@@ -271,45 +265,27 @@ int zero_dist2(const char *fn, double *dist2, int K, hipStream_t st) {
 using namespace dls;
 
 extern "C" int64_t dls_weiszfeld_workspace(int32_t K, int64_t P) {
-    DLS_REQUIRE(K >= 1 && K <= DLS_ROBUST_MAX_K, DLS_EINVAL,
-                "dls_weiszfeld_workspace: K=%d (1..DLS_ROBUST_MAX_K=%d)", K, DLS_ROBUST_MAX_K);
-    DLS_REQUIRE(P >= 0, DLS_EINVAL, "dls_weiszfeld_workspace: P=%lld", (long long)P);
-    return (int64_t)make_plan(K, P).nW * kPartDoubles * (int64_t)sizeof(double);
+    return workspace_query("dls_weiszfeld_workspace", K, P, [&] { return make_plan(K, P).nW; },
+                           kPartDoubles);
 }
 
 extern "C" int dls_rows_sqdist_to_f32(const float *U, int64_t ldu, const int32_t *rows, int32_t K,
                                       int64_t P, const float *z, double *dist2, void *workspace,
                                       dls_stream_t stream) {
-    const char *fn = "dls_rows_sqdist_to_f32";
-    const int rc = check_operands(fn, U, ldu, rows, K, P, z, dist2, workspace, nullptr, false);
-    if (rc != DLS_OK) return rc;
-    hipStream_t st = as_stream(stream);
-    if (P == 0) return zero_dist2(fn, dist2, K, st);
-    dispatch<kRead>(U, ldu, rows, K, nullptr, P, const_cast<float *>(z), dist2,
-                    static_cast<double *>(workspace), st);
-    return check_launch(fn);
+    return run_step<kRead>("dls_rows_sqdist_to_f32", U && rows && z && dist2 && workspace, U, ldu,
+                           rows, K, nullptr, P, const_cast<float *>(z), dist2, workspace, stream);
 }
 
 extern "C" int dls_weiszfeld_step_f32(const float *U, int64_t ldu, const int32_t *rows, int32_t K,
                                       const float *w, int64_t P, float *z, double *dist2,
                                       void *workspace, dls_stream_t stream) {
-    const char *fn = "dls_weiszfeld_step_f32";
-    const int rc = check_operands(fn, U, ldu, rows, K, P, z, dist2, workspace, w, true);
-    if (rc != DLS_OK) return rc;
-    hipStream_t st = as_stream(stream);
-    if (P == 0) return zero_dist2(fn, dist2, K, st);
-    dispatch<kStep>(U, ldu, rows, K, w, P, z, dist2, static_cast<double *>(workspace), st);
-    return check_launch(fn);
+    return run_step<kStep>("dls_weiszfeld_step_f32", U && rows && z && dist2 && workspace && w, U,
+                           ldu, rows, K, w, P, z, dist2, workspace, stream);
 }
 
 extern "C" int dls_centered_clip_step_f32(const float *U, int64_t ldu, const int32_t *rows,
                                           int32_t K, const float *c, int64_t P, float *z,
                                           double *dist2, void *workspace, dls_stream_t stream) {
-    const char *fn = "dls_centered_clip_step_f32";
-    const int rc = check_operands(fn, U, ldu, rows, K, P, z, dist2, workspace, c, true);
-    if (rc != DLS_OK) return rc;
-    hipStream_t st = as_stream(stream);
-    if (P == 0) return zero_dist2(fn, dist2, K, st);
-    dispatch<kClip>(U, ldu, rows, K, c, P, z, dist2, static_cast<double *>(workspace), st);
-    return check_launch(fn);
+    return run_step<kClip>("dls_centered_clip_step_f32", U && rows && z && dist2 && workspace && c,
+                           U, ldu, rows, K, c, P, z, dist2, workspace, stream);
 }

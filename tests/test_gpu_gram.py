@@ -170,6 +170,24 @@ def test_permuting_rows_and_hrows_permutes_the_fold():
     assert np.array_equal(G1, G0[np.ix_(perm, perm)]) and np.array_equal(Ha, Hb)
 
 
+def test_history_gram_on_a_side_stream_gives_the_current_stream_bits():
+    from distributed_learning_simulator_amd import _native
+    K, P = 3, 8
+    g = torch.Generator().manual_seed(11)
+    U, H0 = torch.randn(8, 16, generator=g).to(DEV), torch.randn(8, 16, generator=g).to(DEV)
+    base = torch.randn(16, generator=g).to(DEV)
+    r, hr = dev_rows([5, 0, 2]), dev_rows([1, 7, 4])
+    Ha, Ga = _native.history_gram(U, r, H0.clone(), hr, P, base=base)
+    side, Hb = torch.cuda.Stream(DEV), H0.clone()
+    side.wait_stream(torch.cuda.current_stream(DEV))
+    with torch.cuda.stream(side):
+        _, Gb = _native.history_gram(U, r, Hb, hr, P, base=base, stream=side)
+    side.synchronize()
+    assert torch.equal(Ha.view(torch.int32), Hb.view(torch.int32))
+    assert torch.equal(Ga.view(torch.int64), Gb.view(torch.int64))
+    assert not torch.equal(Ha, H0)  # the fold happened
+
+
 @pytest.mark.parametrize("K, P", [(5, 1088), (9, 484), (40, 2052)])
 def test_equal_rows_give_equal_diagonal_and_off_diagonal_bits(K, P):
     X = rows_for(K, P, K + 3)

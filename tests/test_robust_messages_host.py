@@ -46,8 +46,15 @@ LAST = ("last_selection", "last_scores", "last_distances", "last_rejected", "las
         "last_weights", "last_similarity")
 
 
+TOPK_BYTES = 32  # what the stub's dls_topk_workspace asks for, for every P
+
+
 class _StubLibrary:
-    """Stands in for the loaded library: nothing recorded here reaches an entry point."""
+    """Stands in for the loaded library: nothing recorded here reaches an entry point
+    (but for the host-only size query of the top-k workspace, answered with TOPK_BYTES)."""
+
+    def dls_topk_workspace(self, P):
+        return TOPK_BYTES
 
     def __getattr__(self, name):
         def entry(*args):
@@ -189,10 +196,12 @@ def _table(defects):
     return t[None] if "rank" in defects else t
 
 
-def _vector(n, dtype, wrong):
+def _vector(n, dtype, wrong, short=4):
     def make(defects):
-        m = 4 if "short" in defects else n + 1 if "shape" in defects else n
-        t = _strided(torch.zeros(2 * m + 1, dtype=wrong if "dtype" in defects else dtype), defects)
+        m = (short if "short" in defects else n + 1 if "shape" in defects
+             else 0 if "empty" in defects else n)
+        t = _strided(torch.zeros(2 * m + 1, dtype=wrong if "dtype" in defects else dtype,
+                                 device="meta" if "device" in defects else None), defects)
         return t[None] if "rank" in defects else t
     return make
 
@@ -294,10 +303,155 @@ def _wrapper_cases(name):
         yield "+".join(f"{op}:{kind}" for op, kind in case) or "well-formed", run(case)
 
 
+# ------------------------------------- the vector wrappers: server optimizer and top-k
+VEC_KINDS = ("dtype", "rank", "stride", "misaligned", "short", "device")
+EXACT_KINDS = ("dtype", "rank", "stride", "misaligned", "shape", "device")
+TK = 6  # k of a well-formed topk_compress call (P = 8)
+NNZ = 16  # pairs of a well-formed sparse_fedavg call
+
+
+def _vec(n, dtype, wrong, kinds=VEC_KINDS, short=4):
+    return _vector(n, dtype, wrong, short), kinds
+
+
+P_VEC = _vec(16, torch.float32, torch.float64)  # an fp32 vector of at least P = 8 elements
+
+# wrapper -> (tensor operands in call order, scalars {name: (good, bad values)}, the
+# overlaps it names as (a, b, how), the call on the built operands o and P)
+VECTOR_WRAPPERS = {
+    "server_opt_step": (
+        {name: P_VEC for name in ("agg", "x", "m", "v", "out")},
+        {"kind": (2, (True, -1, 4, 1.5, "adam", 0, 1)), "lr": (0.5, (NAN, INF, 1e39)),
+         "beta1": (0.9, (NAN, -INF, 0.0)), "beta2": (0.99, (NAN, 1e39)), "tau": (1e-3, (NAN, INF))},
+        [(a, b, "alias") for a, b in itertools.combinations(("agg", "x", "m", "v", "out"), 2)]
+        + [("x", "out", "shifted")],
+        lambda n, o, P: n.server_opt_step(o["kind"], o["agg"], o["x"], o["m"], o["v"], o["out"], P,
+                                          o["lr"], o["beta1"], o["beta2"], o["tau"])),
+    "topk_compress": (
+        {"w": P_VEC, "base": P_VEC, "e": P_VEC, "idx": _vec(8, torch.int32, torch.int64),
+         "val": _vec(8, torch.float32, torch.float64),
+         "stats": _vec(2, torch.int32, torch.int64, short=1),
+         "workspace": _vec(TOPK_BYTES, torch.uint8, torch.int8)},
+        {"k": (TK, (True, 0, 9, 1.5, "2"))},
+        [("e", "w", "alias"), ("e", "base", "alias")]
+        + [(a, b, "alias") for a, b in
+           itertools.combinations(("e", "idx", "val", "stats", "workspace"), 2)],
+        lambda n, o, P: n.topk_compress(o["w"], o["base"], o["e"], o["k"], P, o["idx"], o["val"],
+                                        o["stats"], o["workspace"])),
+    "sparse_fedavg": (
+        {"base": P_VEC, "idx": _vec(NNZ, torch.int32, torch.int64, EXACT_KINDS + ("empty", "list")),
+         "val": _vec(NNZ, torch.float32, torch.float64, EXACT_KINDS + ("empty", "list")),
+         "off": _vec(K0 + 1, torch.int64, torch.int32, EXACT_KINDS),
+         "weight": _vec(K0, torch.float32, torch.float64, EXACT_KINDS + ("empty",)),
+         "out": P_VEC},
+        {"total": (6.0, (0.0, -1.0, NAN, INF, 1e39))},
+        [("out", b, "alias") for b in ("base", "idx", "val", "off", "weight")],
+        lambda n, o, P: n.sparse_fedavg(o["base"], o["idx"], o["val"], o["off"], o["weight"],
+                                        o["total"], P, o["out"])),
+}
+OPTIONAL_VEC = {"server_opt_step": ("m", "v")}  # operands that may be None
+
+
+def _alias(o, a, b, how):
+    """Make o[a] and o[b] share storage: the smaller becomes a view of the larger's first
+    bytes with its own dtype and length (``shifted``: b starts 16 bytes into a's buffer)."""
+    if how == "shifted":
+        buf = torch.zeros(o[a].numel() + 4, dtype=o[a].dtype)
+        o[a], o[b] = buf[:-4], buf[4:]
+        return
+    if o[a].numel() * o[a].element_size() < o[b].numel() * o[b].element_size():
+        a, b = b, a
+    nbytes = o[b].numel() * o[b].element_size()
+    o[b] = o[a].view(torch.uint8)[:nbytes].view(o[b].dtype)
+
+
+def _vector_wrapper_cases(name):
+    from distributed_learning_simulator_amd import _native
+    operands, scalars, overlaps, call = VECTOR_WRAPPERS[name]
+    defects = [(op, kind) for op, (_, kinds) in operands.items() for kind in kinds]
+    defects += [(op, "none") for op in OPTIONAL_VEC.get(name, ())]
+    defects += [("P", p) for p in (-4, 0, 2, 20, 1 << 31)]
+    defects += [(s, v) for s, (_, bad) in scalars.items() for v in bad]
+    defects += [(a, f"{how}:{b}") for a, b, how in overlaps]
+
+    def touched(d):  # the operands a defect rebuilds
+        return {d[0], d[1].split(":")[1]} if isinstance(d[1], str) and ":" in d[1] else {d[0]}
+
+    def compatible(a, b):
+        if a[0] == b[0] and (a[0] == "P" or a[0] in scalars or {a[1], b[1]} in EXCLUSIVE
+                             or "none" in (a[1], b[1]) or "list" in (a[1], b[1])
+                             or "empty" in (a[1], b[1])):
+            return False
+        aliasing = [d for d in (a, b) if len(touched(d)) == 2]
+        return not (aliasing and touched(a) & touched(b))
+
+    pairs = [(a, b) for a, b in itertools.combinations(defects, 2) if compatible(a, b)]
+
+    def run(case):
+        P = 8
+        asked = {op: set() for op in operands}
+        o = {s: good for s, (good, _) in scalars.items()}
+        for op, kind in case:
+            if op == "P":
+                P = kind
+            elif op in scalars:
+                o[op] = kind
+            else:
+                asked[op].add(kind)
+        for op, (make, _) in operands.items():
+            kinds = asked[op]
+            plain = {k for k in kinds if ":" not in k and k not in ("none", "list")}
+            o[op] = None if "none" in kinds else [0] * NNZ if "list" in kinds else make(plain)
+        for op, kinds in asked.items():
+            for k in kinds:
+                if ":" in k:
+                    _alias(o, op, k.split(":")[1], k.split(":")[0])
+
+        def invoke():
+            result = call(_native, o, P)
+            return "ok" if torch.is_tensor(result) or isinstance(result, tuple) else result
+        return _outcome(invoke)
+
+    for case in [()] + [(d,) for d in defects] + pairs:
+        yield "+".join(f"{op}:{kind}" for op, kind in case) or "well-formed", run(case)
+
+
+def topk_workspace_cases():
+    from distributed_learning_simulator_amd import _native
+    for P in (-4, 0, 2, 3, 4, 8, 10, (1 << 31) - 4, (1 << 31) - 1, 1 << 31, 8.0, "8", None):
+        def call():
+            t = _native.topk_workspace(P, CPU)
+            return repr((t.dtype, tuple(t.shape), str(t.device)))
+        yield f"P={P!r}", _outcome(call)
+
+
+def required_none_cases():
+    """Every wrapper with each of its tensor operands None in turn, the others well formed
+    (the optional ones, where None is the default, included: they end in "not on the GPU")."""
+    from distributed_learning_simulator_amd import _native
+    for name, (operands, call) in WRAPPERS.items():
+        scalar = {"trimmed_mean": "trim", "mean_around_median": "keep", "craft_rows": "a"}.get(name)
+        for missing in operands:
+            o = {scalar: SCALARS[scalar][0]} if scalar else {}
+            o.update({op: make(set()) for op, (make, _) in operands.items()})
+            o[missing] = None
+            yield f"{name}:{missing}", _outcome(lambda: call(_native, o, 8) and "ok")
+    for name, (operands, scalars, _, call) in VECTOR_WRAPPERS.items():
+        for missing in operands:
+            o = {s: good for s, (good, _) in scalars.items()}
+            o.update({op: make(set()) for op, (make, _) in operands.items()})
+            o[missing] = None
+            yield f"{name}:{missing}", _outcome(lambda: call(_native, o, 8) and "ok")
+
+
 SECTIONS = {"constructor_grid": constructor_grid, "constructor_values": constructor_values,
             "constructor_pairs": constructor_pairs, "constructor_attacks": constructor_attacks,
             "subclasses": subclasses, "subset_models": subset_models}
 SECTIONS.update({f"native_{name}": (lambda name=name: _wrapper_cases(name)) for name in WRAPPERS})
+SECTIONS.update({f"native_{name}": (lambda name=name: _vector_wrapper_cases(name))
+                 for name in VECTOR_WRAPPERS})
+SECTIONS["native_topk_workspace"] = topk_workspace_cases
+SECTIONS["native_required_none"] = required_none_cases
 
 
 def enumerate_section(section):

@@ -13,7 +13,8 @@ CSRC = os.path.join(ROOT, "distributed_learning_simulator_amd", "csrc")
 OUT = os.path.join(ROOT, "tools", "_variants")
 with open(os.path.join(CSRC, "Makefile")) as _fh:  # the library's own source list
     SRCS = next(line for line in _fh if line.startswith("SRCS :=")).split()[2:]
-HEADERS = ["dls_common.h", "quant_common.h", "loss_common.h", "sign_geometry.h"]
+HEADERS = ["dls_common.h", "quant_common.h", "loss_common.h", "sign_geometry.h",
+           "rows_common.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off"]
 
 
