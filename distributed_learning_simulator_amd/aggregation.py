@@ -408,6 +408,14 @@ class ClientUpdateStore:
         """``out``, or a new fp32 device vector of n elements."""
         return torch.empty(n, dtype=torch.float32, device=self.device) if out is None else out
 
+    def _flat_operand(self, noun, t):
+        """P; ValueError unless ``t`` is an fp32 vector of P elements on the store's device."""
+        P = self.layout.P
+        if (not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 1
+                or t.numel() != P or t.device != self.U.device):
+            raise ValueError(f"{noun} must be an fp32 vector of P={P} elements on {self.U.device}")
+        return P
+
     def trimmed_mean(self, rows, trim, out=None, cols=None):
         """Coordinate-wise trimmed mean of the given rows (dls_trimmed_mean_f32): per
         flat element the ``trim`` lowest and highest of the K values are dropped and
@@ -633,10 +641,7 @@ class ClientUpdateStore:
         fp64, is copied to the host once at the end) and, with ``trace``, per pass the
         (ids, fp32 coefficients or None, dist2) the pass ran on and gave."""
         iters, active = self._in_id_order("centered_clip", rows, ids, iters)
-        P = self.layout.P
-        if (not torch.is_tensor(start) or start.dtype != torch.float32 or start.dim() != 1
-                or start.numel() != P or start.device != self.U.device):
-            raise ValueError(f"start must be an fp32 vector of P={P} elements on {self.U.device}")
+        P = self._flat_operand("start", start)
         flat = self._vector(P, out)
         flat.copy_(start)
         prev = torch.empty_like(flat)
@@ -732,10 +737,7 @@ class ClientUpdateStore:
         rows = [int(r) for r in rows]
         if len(set(ids)) != len(ids) or len(ids) != len(rows):
             raise ValueError("foolsgold needs one distinct id per row")
-        P = self.layout.P
-        if (not torch.is_tensor(base) or base.dtype != torch.float32 or base.dim() != 1
-                or base.numel() != P or base.device != self.U.device):
-            raise ValueError(f"base must be an fp32 vector of P={P} elements on {self.U.device}")
+        P = self._flat_operand("base", base)
         M = G.cpu().tolist() if torch.is_tensor(G) else [list(r) for r in G]
         order = sorted(range(len(ids)), key=lambda i: ids[i])
         alpha, winfo = foolsgold_weights([[M[i][j] for j in order] for i in order], kappa)
@@ -763,11 +765,7 @@ class ClientUpdateStore:
     def set_model(self, flat):
         """Hold ``flat`` (an fp32 device vector of ``layout.P`` elements, padding zero) as
         the current global model: what the next ``server_opt_step`` steps from."""
-        P = self.layout.P
-        if (not torch.is_tensor(flat) or flat.dtype != torch.float32 or flat.dim() != 1
-                or flat.numel() != P or flat.device != self.U.device):
-            raise ValueError(f"the model must be an fp32 vector of P={P} elements on "
-                             f"{self.U.device}")
+        self._flat_operand("the model", flat)
         self.model = flat
 
     def reset_server_opt(self, kind=None, coeffs=None):

@@ -4,6 +4,7 @@ Same hooks, same round protocol, same return objects; ``get_subset_model`` is
 one ``dls_fedavg_f32`` launch over the clients' HBM rows instead of a Python
 loop of K x (#tensors) torch ops, bit-exact with the reference's op order.
 """
+import collections
 import copy
 import logging
 
@@ -20,53 +21,64 @@ from .server import Server
 log = logging.getLogger("distributed_learning_simulator_amd")
 
 _MODES = {"exact": _native.FEDAVG_EXACT, "fma": _native.FEDAVG_FMA}
-# The rules' constructor parameters and their defaults (gm_*: RFA's, Pillutla et al.;
-# fg_kappa: the paper's confidence), in the order they are checked.
-DEFAULTS = {"trim": 0, "byzantine": 0, "krum_select": None, "gm_iters": 3, "gm_nu": 1e-6,
-            "cc_iters": 3, "cc_tau": 10.0, "fg_kappa": 1.0}
-_AT_LEAST = {"trim": 0, "byzantine": 0, "gm_iters": 1, "cc_iters": 1}  # the integer ones
-ATTACK_DEFAULTS = {"attack_z": None, "attack_eps": 0.1, "attack_scale": 1.0}
-_ATTACK_OF = {"attack_z": "alie", "attack_eps": "ipm", "attack_scale": "sign_flip"}
-# What a parameter set under a rule that does not own it is told: the parameters the
-# message lists and the rule it names.
-_GROUPS = ((("trim",), "trimmed_mean"), (("byzantine", "krum_select"), "multi_krum"),
-           (("gm_iters", "gm_nu"), "geometric_median"), (("cc_tau", "cc_iters"), "centered_clip"),
-           (("fg_kappa",), "foolsgold"))
-# The server optimizers (FedAvgM: Hsu et al. 2019; FedAdagrad / FedAdam / FedYogi: Reddi et al.
-# 2021), their constructor parameters with the defaults that mean "not set", and the
-# optimizers that own each parameter.
-SERVER_OPTIMIZERS = tuple(_native.SERVER_OPT_KINDS)
-_ADAPTIVE = ("adagrad", "adam", "yogi")
-SERVER_OPT_DEFAULTS = {"server_lr": None, "server_momentum": None, "server_beta2": 0.99,
-                       "server_tau": 1e-3}
-_SERVER_OPT_OWNERS = {"server_lr": SERVER_OPTIMIZERS, "server_momentum": SERVER_OPTIMIZERS,
-                      "server_beta2": ("adam", "yogi"), "server_tau": _ADAPTIVE}
+SERVER_OPTIMIZERS = tuple(_native.SERVER_OPT_KINDS)  # sgd: FedAvgM; the others: Reddi et al.
+
+
+# Every constructor option, declared once, in the order a feature's options are checked:
+# its default (gm_*: RFA's, Pillutla et al.; fg_kappa: the paper's confidence; None is
+# resolved later), its kind (_check_kinds: the type it is held as, and an integer's minimum
+# or which reals), its feature and who takes it (a misplaced option is told the first).
+_Option = collections.namedtuple("_Option", "default kind feature owners")
+OPTIONS = {
+    "trim": _Option(0, (int, 0), "rule", ("trimmed_mean",)),
+    "byzantine": _Option(0, (int, 0), "rule", ("multi_krum", "mean_around_median", "bulyan")),
+    "krum_select": _Option(None, (int, None), "rule", ("multi_krum",)),
+    "gm_iters": _Option(3, (int, 1), "rule", ("geometric_median",)),
+    "gm_nu": _Option(1e-6, (float, "positive"), "rule", ("geometric_median",)),
+    "cc_iters": _Option(3, (int, 1), "rule", ("centered_clip",)),
+    "cc_tau": _Option(10.0, (float, "positive"), "rule", ("centered_clip",)),
+    "fg_kappa": _Option(1.0, (float, "positive"), "rule", ("foolsgold",)),
+    "attack_z": _Option(None, (float, "finite"), "attack", ("alie",)),
+    "attack_eps": _Option(0.1, (float, "finite"), "attack", ("ipm",)),
+    "attack_scale": _Option(1.0, (float, "finite"), "attack", ("sign_flip",)),
+    "server_lr": _Option(None, (float, "positive"), "server_opt", SERVER_OPTIMIZERS),
+    "server_momentum": _Option(None, (float, "in [0, 1)"), "server_opt", SERVER_OPTIMIZERS),
+    "server_beta2": _Option(0.99, (float, "in [0, 1)"), "server_opt", ("adam", "yogi")),
+    "server_tau": _Option(1e-3, (float, "positive"), "server_opt", ("adagrad", "adam", "yogi")),
+}
+DEFAULTS, ATTACK_DEFAULTS, SERVER_OPT_DEFAULTS = (
+    {name: o.default for name, o in OPTIONS.items() if o.feature == feature}
+    for feature in ("rule", "attack", "server_opt"))
 # Every robust rule needs 2*trim < K (trim is 0 under all but the trimmed mean).
 _TRIM_FITS = (lambda K, p: 2 * p["trim"] < K,
               "trim={trim} leaves nothing of {clients} (2*trim < {n} is needed)")
-# The rules, in the order they are listed to the user.  owns: the constructor parameters
-# the rule takes; ids: whether get_subset_model hands it the worker ids (it reports,
-# breaks ties and orders by them); count: its condition on the number of clients K, a
-# predicate of (K, parameters) and the message when it fails (_count_error fills in
-# {group}, {clients} and {n}); run: the FedServer method (store, rows, ids) -> flat.
+# The rules, in the order they are listed to the user.  ids: whether get_subset_model
+# hands the rule the worker ids (it reports, breaks ties and orders by them); count: its
+# condition on the number of clients K, a predicate of (K, parameters) and the message
+# when it fails (_count_error fills in {group}, {clients} and {n}); run: the FedServer
+# method (store, rows, ids) -> flat; owns: the options of OPTIONS the rule takes.
 RULES = {
-    "mean": dict(owns=(), ids=False, count=None, run=None),  # store.fedavg, with the n_i
-    "median": dict(owns=(), ids=False, count=None, run="_median"),
-    "trimmed_mean": dict(owns=("trim",), ids=False, count=None, run="_trimmed_mean"),
-    "multi_krum": dict(owns=("byzantine", "krum_select"), ids=True, run="_multi_krum", count=(
+    "mean": dict(ids=False, count=None, run=None),  # store.fedavg, with the n_i
+    "median": dict(ids=False, count=None, run="_median"),
+    "trimmed_mean": dict(ids=False, count=None, run="_trimmed_mean"),
+    "multi_krum": dict(ids=True, run="_multi_krum", count=(
         lambda K, p: 2 * p["byzantine"] + 3 <= K,
         "byzantine={byzantine} is too many for {group} (2*byzantine + 3 <= {n} is needed)")),
-    "geometric_median": dict(owns=("gm_iters", "gm_nu"), ids=True, count=None,
-                             run="_geometric_median"),
-    "centered_clip": dict(owns=("cc_tau", "cc_iters"), ids=True, count=None, run="_centered_clip"),
-    "mean_around_median": dict(owns=("byzantine",), ids=False, run="_mean_around_median", count=(
+    "geometric_median": dict(ids=True, count=None, run="_geometric_median"),
+    "centered_clip": dict(ids=True, count=None, run="_centered_clip"),
+    "mean_around_median": dict(ids=False, run="_mean_around_median", count=(
         lambda K, p: 2 * p["byzantine"] < K,
         "byzantine={byzantine} leaves no majority of {clients} (2*byzantine < {n} is needed)")),
-    "bulyan": dict(owns=("byzantine",), ids=True, run="_bulyan", count=(
+    "bulyan": dict(ids=True, run="_bulyan", count=(
         lambda K, p: 4 * p["byzantine"] + 3 <= K,
         "byzantine={byzantine} is too many for {group} (4*byzantine + 3 <= {n} is needed)")),
-    "foolsgold": dict(owns=("fg_kappa",), ids=True, count=None, run="_foolsgold"),
+    "foolsgold": dict(ids=True, count=None, run="_foolsgold"),
 }
+# The rule options that are checked, and listed to a rule that takes none of them, together.
+_LISTED = (("trim",), ("byzantine", "krum_select"), ("gm_iters", "gm_nu"), ("cc_tau", "cc_iters"),
+           ("fg_kappa",))
+for _rule, _row in RULES.items():
+    _row["owns"] = tuple(n for names in _LISTED for n in names if _rule in OPTIONS[n].owners)
 
 
 def _count_error(rule, K, p, subset):
@@ -199,12 +211,10 @@ class FedServer(Server):
     any arrival order.  Hooks, ``prev_model``, ``get_metric`` and the round protocol
     are the same for every rule."""
 
-    # why a subclass cannot run the robust rules (None: it can)
-    _robust_unsupported = None
-    # why a subclass cannot run the Byzantine client attacks (None: it can)
-    _attack_unsupported = None
-    # why a subclass cannot run a server optimizer (None: it can)
-    _server_opt_unsupported = None
+    # why a subclass cannot run a feature (None: it can); _check_runs words the refusal
+    _robust_unsupported = None  # the robust rules
+    _attack_unsupported = None  # the Byzantine client attacks
+    _server_opt_unsupported = None  # a server optimizer
 
     def __init__(self, aggregation_mode="exact", aggregation_rule="mean",
                  trim=DEFAULTS["trim"], byzantine=DEFAULTS["byzantine"],
@@ -217,16 +227,17 @@ class FedServer(Server):
                  server_momentum=SERVER_OPT_DEFAULTS["server_momentum"],
                  server_beta2=SERVER_OPT_DEFAULTS["server_beta2"],
                  server_tau=SERVER_OPT_DEFAULTS["server_tau"], **kwargs):
+        # the options by name (the first statement: only the arguments are bound yet)
+        given = {name: v for name, v in locals().items() if name in OPTIONS}
         if aggregation_mode not in _MODES:
             raise ValueError(f"aggregation_mode must be one of {sorted(_MODES)}, not {aggregation_mode!r}")
-        self._check_rule(aggregation_rule, aggregation_mode, kwargs.get("worker_number"),
-                         trim=trim, byzantine=byzantine, krum_select=krum_select,
-                         gm_iters=gm_iters, gm_nu=gm_nu, cc_iters=cc_iters, cc_tau=cc_tau,
-                         fg_kappa=fg_kappa)
-        attackers = self._check_attack(attack, attackers, attack_z, attack_eps, attack_scale,
-                                       kwargs.get("worker_number"))
-        server_opt = self._check_server_opt(server_optimizer, server_lr, server_momentum,
-                                            server_beta2, server_tau)
+        workers = kwargs.get("worker_number")
+        self._check_rule(aggregation_rule, aggregation_mode, workers,
+                         **{name: given[name] for name in DEFAULTS})
+        attackers = self._check_attack(attack, attackers, worker_number=workers,
+                                       **{name: given[name] for name in ATTACK_DEFAULTS})
+        server_opt = self._check_server_opt(
+            server_optimizer, **{name: given[name] for name in SERVER_OPT_DEFAULTS})
         super().__init__(**kwargs)
         _native.require_gpu()
         self.round = 0
@@ -239,32 +250,48 @@ class FedServer(Server):
         self._server_opt_adopted = False  # "no previous model" is logged once
         self.aggregation_mode = aggregation_mode
         self.aggregation_rule = aggregation_rule
-        self.trim = int(trim)
-        self.byzantine = int(byzantine)
-        self.krum_select = None if krum_select is None else int(krum_select)
+        self.attack = attack
+        self.attackers = attackers
+        for name in (*DEFAULTS, *ATTACK_DEFAULTS):  # held as the type of their kind
+            v, o = given[name], OPTIONS[name]
+            setattr(self, name, v if v is None and o.default is None else o.kind[0](v))
         self.last_selection = ()
         self.last_scores = {}
-        self.gm_iters = gm_iters
-        self.gm_nu = float(gm_nu)
         self.last_distances = {}
         self.last_rejected = ()
-        self.cc_tau = float(cc_tau)
-        self.cc_iters = cc_iters
         self.last_clip_scales = {}
-        self.fg_kappa = float(fg_kappa)
         self.last_weights = {}
         self.last_similarity = {}
         self._fg_round = None  # the folded round: its worker ids, their G and the base
-        self.attack = attack
-        self.attackers = attackers
-        self.attack_z = None if attack_z is None else float(attack_z)
-        self.attack_eps = float(attack_eps)
-        self.attack_scale = float(attack_scale)
         self.last_attack = {}
         self.parameters: ClientParameters = ClientParameters(self._make_store)
         self.__prev_model = self._initial_model()
         self.worker_data_queue.put_result(
             RepeatedResult(data=self.prev_model, num=self.clients_per_round))
+
+    @staticmethod
+    def _check_kinds(p):
+        """ValueError for an option in ``p`` that is not of its kind; a default None passes."""
+        for name, v in p.items():
+            default, (held, which) = OPTIONS[name][:2]
+            if v is None and default is None:
+                continue
+            if held is float:
+                finite_number(name, v, positive=which == "positive")
+                if which == "in [0, 1)" and not 0.0 <= v < 1.0:
+                    raise ValueError(f"{name} must be {which}, not {v!r}")
+            elif isinstance(v, bool) or not isinstance(v, int) or (which is not None and v < which):
+                what = ("an integer or None" if which is None
+                        else f"a {'positive' if which else 'non-negative'} integer")
+                raise ValueError(f"{name} must be {what}, not {v!r}")
+
+    @classmethod
+    def _check_runs(cls, what, reason, runs):
+        """ValueError if ``reason``, a ``_*_unsupported`` of this class, says it cannot run the
+        feature ``what``; ``runs`` names the servers that do."""
+        if reason is not None:
+            raise ValueError(f"{cls.__name__} does not support {what} ({reason}); the one-process "
+                             f"FedServer (factory.get_server('fed', ...)) {runs}")
 
     @classmethod
     def _check_rule(cls, rule, mode, worker_number, **parameters):
@@ -273,29 +300,15 @@ class FedServer(Server):
         if rule not in RULES:
             raise ValueError(f"aggregation_rule must be one of {list(RULES)}, not {rule!r}")
         p = {**DEFAULTS, **parameters}
-        for names, owner in _GROUPS:
-            for name in (n for n in DEFAULTS if n in names):
-                v = p[name]
-                if name in _AT_LEAST:
-                    if isinstance(v, bool) or not isinstance(v, int) or v < _AT_LEAST[name]:
-                        raise ValueError(f"{name} must be a "
-                                         f"{'positive' if _AT_LEAST[name] else 'non-negative'} "
-                                         f"integer, not {v!r}")
-                elif name != "krum_select":
-                    finite_number(name, v, positive=True)
-                elif v is not None and (isinstance(v, bool) or not isinstance(v, int)):
-                    raise ValueError(f"krum_select must be an integer or None, not {v!r}")
-            if any(p[n] != DEFAULTS[n] and n not in RULES[rule]["owns"] for n in names):
-                raise ValueError(" / ".join(f"{n}={p[n]}" for n in names)
-                                 + f" needs aggregation_rule={owner!r}, not {rule!r}")
+        for names in _LISTED:
+            cls._check_kinds({n: p[n] for n in DEFAULTS if n in names})
+            if any(p[n] != DEFAULTS[n] and rule not in OPTIONS[n].owners for n in names):
+                raise ValueError(" / ".join(f"{n}={p[n]}" for n in names) + " needs "
+                                 f"aggregation_rule={OPTIONS[names[0]].owners[0]!r}, not {rule!r}")
         if rule == "mean":
             return
-        if cls._robust_unsupported is not None:
-            raise ValueError(
-                f"{cls.__name__} does not support aggregation_rule={rule!r} "
-                f"({cls._robust_unsupported}); the one-process FedServer "
-                "(factory.get_server('fed', ...)) is the server that runs the median and "
-                "trimmed-mean rules")
+        cls._check_runs(f"aggregation_rule={rule!r}", cls._robust_unsupported,
+                        "is the server that runs the median and trimmed-mean rules")
         if mode != "exact":
             raise ValueError(f"aggregation_mode={mode!r} applies to aggregation_rule='mean' only; "
                              f"{rule!r} has one arithmetic")
@@ -327,23 +340,20 @@ class FedServer(Server):
             raise ValueError(f"attackers must be non-negative integer worker ids, not {ids!r}")
         if len(set(ids)) != len(ids):
             raise ValueError(f"attackers must be distinct worker ids, not {ids!r}")
-        given = {"attack_z": attack_z, "attack_eps": attack_eps, "attack_scale": attack_scale}
-        for name, v in given.items():
-            if v is not None:
-                finite_number(name, v)
+        p = {"attack_z": attack_z, "attack_eps": attack_eps, "attack_scale": attack_scale}
+        # a None that is not the default passes here too: float() refuses it in __init__
+        cls._check_kinds({name: v for name, v in p.items() if v is not None})
         if attack is None and ids:
             raise ValueError(f"attackers={ids} needs an attack, one of {list(ATTACKS)}")
-        for name, v in given.items():
-            if attack != _ATTACK_OF[name] and v != ATTACK_DEFAULTS[name]:
-                raise ValueError(f"{name}={v} needs attack={_ATTACK_OF[name]!r}, not {attack!r}")
+        for name, v in p.items():
+            if v != ATTACK_DEFAULTS[name] and attack not in OPTIONS[name].owners:
+                raise ValueError(f"{name}={v} needs attack={OPTIONS[name].owners[0]!r}, "
+                                 f"not {attack!r}")
         if attack is None:
             return ()
-        if cls._attack_unsupported is not None:
-            raise ValueError(
-                f"{cls.__name__} does not support attack={attack!r} "
-                f"({cls._attack_unsupported}); the one-process FedServer "
-                "(factory.get_server('fed', ...)) and the one-process Shapley servers are the "
-                "servers that run the Byzantine client attacks")
+        cls._check_runs(f"attack={attack!r}", cls._attack_unsupported,
+                        "and the one-process Shapley servers are the servers that run the "
+                        "Byzantine client attacks")
         if not ids:
             raise ValueError(f"attack={attack!r} needs attackers, a non-empty collection of "
                              "worker ids")
@@ -377,28 +387,19 @@ class FedServer(Server):
         if optimizer is not None and optimizer not in SERVER_OPTIMIZERS:
             raise ValueError(f"server_optimizer must be None or one of {list(SERVER_OPTIMIZERS)}, "
                              f"not {optimizer!r}")
-        given = {"server_lr": server_lr, "server_momentum": server_momentum,
-                 "server_beta2": server_beta2, "server_tau": server_tau}
-        for name, v in given.items():
-            if v is None and SERVER_OPT_DEFAULTS[name] is None:
-                continue
-            if name in ("server_lr", "server_tau"):
-                finite_number(name, v, positive=True)
-            elif finite_number(name, v) < 0.0 or v >= 1.0:
-                raise ValueError(f"{name} must be in [0, 1), not {v!r}")
-        for name, v in given.items():
-            if v != SERVER_OPT_DEFAULTS[name] and optimizer not in _SERVER_OPT_OWNERS[name]:
-                owners = _SERVER_OPT_OWNERS[name]
+        p = {"server_lr": server_lr, "server_momentum": server_momentum,
+             "server_beta2": server_beta2, "server_tau": server_tau}
+        cls._check_kinds(p)
+        for name, v in p.items():
+            owners = OPTIONS[name].owners
+            if v != SERVER_OPT_DEFAULTS[name] and optimizer not in owners:
                 raise ValueError(f"{name}={v} needs server_optimizer "
                                  + (f"in {list(owners)}" if len(owners) < len(SERVER_OPTIMIZERS)
                                     else f"set, one of {list(owners)}") + f", not {optimizer!r}")
         if optimizer is None:
             return None
-        if cls._server_opt_unsupported is not None:
-            raise ValueError(
-                f"{cls.__name__} does not support server_optimizer={optimizer!r} "
-                f"({cls._server_opt_unsupported}); the one-process FedServer "
-                "(factory.get_server('fed', ...)) is the server that runs the server optimizers")
+        cls._check_runs(f"server_optimizer={optimizer!r}", cls._server_opt_unsupported,
+                        "is the server that runs the server optimizers")
         sgd = optimizer == "sgd"
         lr = float(server_lr) if server_lr is not None else (1.0 if sgd else 0.01)
         beta1 = float(server_momentum) if server_momentum is not None else (0.0 if sgd else 0.9)
@@ -509,22 +510,21 @@ class FedServer(Server):
         if select > K - f:
             raise ValueError(f"krum_select={select} exceeds len(subset) - byzantine = {K - f}")
         flat, selected, scores = store.multi_krum(rows, ids, f, select)
-        self.last_selection = tuple(selected)
-        self.last_scores = dict(zip(ids, scores))
-        chosen = set(selected)
-        log.info("multi_krum: kept %s of %s clients, rejected workers %s", len(selected), K,
-                 [i for i in ids if i not in chosen])
+        self._keep_selection("multi_krum", ids, selected, dict(zip(ids, scores)))
         return flat
 
     def _bulyan(self, store, rows, ids):
-        K, f = len(rows), self.byzantine
-        flat, selected, scores = store.bulyan(rows, ids, f)
+        flat, selected, scores = store.bulyan(rows, ids, self.byzantine)
+        self._keep_selection("bulyan", ids, selected, scores)
+        return flat
+
+    def _keep_selection(self, rule, ids, selected, scores):
+        """Record and log what a selecting rule chose of the clients ``ids``."""
         self.last_selection = tuple(selected)
         self.last_scores = scores
         chosen = set(selected)
-        log.info("bulyan: kept %s of %s clients, rejected workers %s", len(selected), K,
+        log.info("%s: kept %s of %s clients, rejected workers %s", rule, len(selected), len(ids),
                  [i for i in ids if i not in chosen])
-        return flat
 
     def _geometric_median(self, store, rows, ids):
         flat, info = store.geometric_median(rows, ids, self.gm_iters, self.gm_nu)
@@ -535,12 +535,14 @@ class FedServer(Server):
                  info["objective"][0], info["objective"][-1])
         return flat
 
+    def _start_flat(self, store, rows):
+        """(The model the clients started from, flat, True); while there is none (round 1 of a
+        server without a tester), (the coordinate-wise median of ``rows``, False)."""
+        prev = self._prev_flat(store)
+        return (store.median(rows), False) if prev is None else (prev, True)
+
     def _centered_clip(self, store, rows, ids):
-        # from the model the clients started from; the coordinate-wise median of the
-        # subset while there is none (round 1 of a server without a tester)
-        start = self._prev_flat(store)
-        if start is None:
-            start = store.median(rows)
+        start, _ = self._start_flat(store, rows)
         flat, info = store.centered_clip(rows, ids, start, self.cc_tau, self.cc_iters)
         self.last_distances = info["distances"]
         self.last_rejected = tuple(info["rejected"])
@@ -565,11 +567,8 @@ class FedServer(Server):
             raise ValueError("aggregation_rule='foolsgold' keeps one history row per worker id: "
                              f"the ids must be non-negative integers, not {ids!r}")
         rows = [self.parameters.row_of(w) for w in ids]
-        # updates are taken from the model the clients started from; from the round's
-        # coordinate-wise median while there is none
-        base = self._prev_flat(store)
-        if base is None:
-            base = store.median(rows)
+        base, previous = self._start_flat(store, rows)  # what the updates are taken from
+        if not previous:
             log.info("foolsgold: no previous model in round %s, updates are taken from the "
                      "coordinate-wise median of the round's %s rows", self.round, len(rows))
         G = store.fold_history(rows, ids, base).cpu().tolist()

@@ -444,6 +444,244 @@ def required_none_cases():
             yield f"{name}:{missing}", _outcome(lambda: call(_native, o, 8) and "ok")
 
 
+# ------------------------------------- every option, every feature, every server class
+SERVER_OPTIMIZERS = ("sgd", "adagrad", "adam", "yogi")
+OPT_OWNERS = {"server_lr": SERVER_OPTIMIZERS, "server_momentum": SERVER_OPTIMIZERS,
+              "server_beta2": ("adam", "yogi"), "server_tau": ("adagrad", "adam", "yogi")}
+KIND_VALUES = BAD_VALUES + (None, 1, 2, -0.5, 0.5, 1.0, 1e-3, -INF)
+# what switches an option's feature on with a value that owns the option
+ATTACKED = dict(attackers=(1,))
+
+
+def _owned(name, owner):
+    """The keywords under which ``owner`` (a rule, an attack or an optimizer) is on."""
+    if name in OPT_OWNERS:
+        return dict(server_optimizer=owner)
+    if name.startswith("attack"):
+        return dict(attack=owner, **ATTACKED)
+    return dict(aggregation_rule=owner)
+
+
+def constructor_kinds():
+    """Every option at every kind of value, under its first owner and with its feature
+    off (a wrong kind is told before a wrong place), and the selectors' own values."""
+    for name, owners in {**OWNERS, **OPT_OWNERS}.items():
+        for value, on in itertools.product(KIND_VALUES, (True, False)):
+            kw = dict(worker_number=10, **(_owned(name, owners[0]) if on else {}), **{name: value})
+            yield _kw(kw), _construct(_fed, **kw)
+    selectors = {"aggregation_mode": (None, "EXACT", 1, ""), "aggregation_rule": (None, "krum", 1),
+                 "attack": ("ALIE", 1, ""), "server_optimizer": ("SGD", 1, "", "adamw"),
+                 "attackers": (None, "12", [1.5], ((1,),), [1, True], range(3), range(10))}
+    for name, values in selectors.items():
+        for value in values:
+            kw = dict(worker_number=10, **{name: value})
+            yield _kw(kw), _construct(_fed, **kw)
+            kw = dict(worker_number=10, aggregation_rule="median", attack="ipm", attackers=(1,),
+                      server_optimizer="adam")
+            kw[name] = value
+            yield _kw(kw), _construct(_fed, **kw)
+
+
+def constructor_owners():
+    """Every option at a value of its own under every rule, attack and optimizer, the
+    feature off included."""
+    values = dict(ONE_SET, attack_z=1.0, attack_eps=0.2, attack_scale=2.0, server_lr=0.5,
+                  server_momentum=0.5, server_beta2=0.9, server_tau=0.01)
+    for name, value in values.items():
+        feature = (SERVER_OPTIMIZERS if name in OPT_OWNERS else ATTACKS
+                   if name.startswith("attack") else RULES)
+        for chosen in (None,) + feature:
+            kw = dict(worker_number=10, **({} if chosen is None else _owned(name, chosen)),
+                      **{name: value})
+            yield _kw(kw), _construct(_fed, **kw)
+
+
+def constructor_attributes():
+    """What an accepted construction holds of every option: value and type."""
+    names = tuple(OWNERS) + tuple(OPT_OWNERS)
+    for kw in (dict(), dict(aggregation_rule="trimmed_mean", trim=2),
+               dict(aggregation_rule="multi_krum", byzantine=2, krum_select=3),
+               dict(aggregation_rule="geometric_median", gm_iters=5, gm_nu=1),
+               dict(aggregation_rule="centered_clip", cc_tau=2, cc_iters=4),
+               dict(aggregation_rule="foolsgold", fg_kappa=3),
+               dict(attack="alie", attackers=(2, 1), attack_z=1),
+               dict(attack="ipm", attackers=(1,), attack_eps=1),
+               dict(attack="sign_flip", attackers=(1,), attack_scale=3),
+               dict(server_optimizer="sgd"), dict(server_optimizer="sgd", server_lr=1),
+               dict(server_optimizer="adam", server_momentum=0, server_beta2=0, server_tau=1)):
+        def call():
+            s = _fed(worker_number=10, **kw)
+            s.stop()
+            return repr({n: getattr(s, n) for n in names + ("attackers",)})
+        yield _kw(kw), _outcome(call)
+
+
+def checker_misuse():
+    """The three checkers called with arguments their signatures do not take."""
+    from distributed_learning_simulator_amd.servers.fed_server import FedServer as F
+    calls = {
+        "_check_server_opt('sgd',0.5,server_lr=0.7)":
+            lambda: F._check_server_opt("sgd", 0.5, server_lr=0.7),
+        "_check_server_opt('sgd',0.5,0.5,0.9,0.01,1)":
+            lambda: F._check_server_opt("sgd", 0.5, 0.5, 0.9, 0.01, 1),
+        "_check_server_opt('sgd',bogus=1)": lambda: F._check_server_opt("sgd", bogus=1),
+        "_check_server_opt()": lambda: F._check_server_opt(),
+        "_check_attack('alie',(1,),bogus=1)": lambda: F._check_attack("alie", (1,), bogus=1),
+        "_check_attack('alie')": lambda: F._check_attack("alie"),
+        "_check_attack('alie',(1,),1.0,attack_z=2.0)":
+            lambda: F._check_attack("alie", (1,), 1.0, attack_z=2.0),
+        "_check_attack('alie',(1,),1.0,0.1,1.0,8,9)":
+            lambda: F._check_attack("alie", (1,), 1.0, 0.1, 1.0, 8, 9),
+        "_check_rule('median')": lambda: F._check_rule("median"),
+        "_check_rule('median','exact',5,bogus=1)":
+            lambda: F._check_rule("median", "exact", 5, bogus=1),
+        "_check_rule('median','exact',5,6)": lambda: F._check_rule("median", "exact", 5, 6),
+    }
+    for key, call in calls.items():
+        yield key, _outcome(lambda: repr(call()))
+
+
+# one fault each: (what is wrong, the keywords that make it so on any of BASES)
+FAULTS = (
+    [("mode", dict(aggregation_mode="fast")), ("rule", dict(aggregation_rule="krum")),
+     ("attack", dict(attack="ALIE")), ("attackers", dict(attackers=5)),
+     ("attackers twice", dict(attackers=(1, 1))), ("optimizer", dict(server_optimizer="SGD")),
+     ("no attack", dict(attack=None, attackers=(1,))),
+     ("no attackers", dict(attack="sign_flip", attackers=())),
+     ("fma", dict(aggregation_mode="fma", aggregation_rule="median")),
+     ("count", dict(aggregation_rule="bulyan", byzantine=2)),
+     ("select", dict(aggregation_rule="multi_krum", byzantine=1, krum_select=10)),
+     ("beyond", dict(attack="ipm", attackers=(10,))),
+     ("fp32", dict(server_optimizer="adam", server_lr=1e-46))]
+    + [(f"kind {n}", {n: v}) for n, v in dict(
+        trim=-1, byzantine=True, krum_select=1.5, gm_iters=0, gm_nu=0.0, cc_tau=NAN, cc_iters=1.5,
+        fg_kappa=-1.0, attack_z="1", attack_eps=INF, attack_scale=NAN, server_lr=0.0,
+        server_momentum=1.0, server_beta2=-0.1, server_tau=INF).items()]
+    + [(f"place {n}", {n: v}) for n, v in dict(
+        trim=1, byzantine=1, krum_select=2, gm_iters=2, gm_nu=1e-3, cc_tau=1.0, cc_iters=2,
+        fg_kappa=2.0, attack_z=1.0, attack_eps=0.2, attack_scale=2.0, server_lr=0.5,
+        server_momentum=0.5, server_beta2=0.9, server_tau=0.01).items()])
+BASES = (dict(worker_number=10),
+         dict(worker_number=10, aggregation_rule="median", attack="ipm", attackers=(1,),
+              server_optimizer="sgd"))
+
+
+def constructor_precedence():
+    """Two faults at once, every pair that can be set together: which one is told."""
+    for base, ((a, fa), (b, fb)) in itertools.product(BASES, itertools.combinations(FAULTS, 2)):
+        if set(fa) & set(fb):
+            continue
+        kw = {**base, **fa, **fb}
+        yield f"{a}+{b}:{_kw(kw)}", _construct(_fed, **kw)
+
+
+def _server_classes():
+    from distributed_learning_simulator_amd import distributed as d
+    from distributed_learning_simulator_amd.servers.fed_quant_server import FedQuantServer
+    from distributed_learning_simulator_amd.servers.fed_server import FedServer
+    from distributed_learning_simulator_amd.servers.fed_topk_server import FedTopKServer
+    from distributed_learning_simulator_amd.servers.GTG_shapley_value_server import \
+        GTGShapleyValueServer
+    from distributed_learning_simulator_amd.servers.multiround_shapley_value_server import \
+        MultiRoundShapleyValueServer
+    return (FedServer, FedQuantServer, FedTopKServer, GTGShapleyValueServer,
+            MultiRoundShapleyValueServer, d.ShardedFedServer, d.ShardedFedQuantServer,
+            d.ShardedGTGShapleyValueServer, d.ShardedMultiRoundShapleyValueServer)
+
+
+FEATURES_ON = (
+    dict(aggregation_rule="median"), dict(aggregation_rule="trimmed_mean", trim=1),
+    dict(aggregation_rule="median", aggregation_mode="fma"), dict(trim=1), dict(fg_kappa=0.0),
+    dict(attack="alie", attackers=(1,)), dict(attack="sign_flip", attackers=()),
+    dict(attack_eps=0.5), dict(attack="ipm", attackers=(1,), attack_eps=NAN),
+    dict(server_optimizer="sgd"), dict(server_optimizer="adam", server_beta2=0.9),
+    dict(server_optimizer="adam", server_lr=1e-46), dict(server_lr=0.5),
+    dict(server_optimizer="yogi", server_tau=0.0),
+    dict(aggregation_rule="median", attack="alie", attackers=(1,), server_optimizer="sgd"),
+    dict(attack="alie", attackers=(1,), server_optimizer="sgd"))
+
+
+def subclass_features():
+    """Every feature on every server class: through the constructor, and through the
+    three checkers as the callers outside the class call them."""
+    for cls in _server_classes():
+        extra = dict(initial_model={"w": torch.zeros(4)}) if cls.__name__ == "FedTopKServer" else {}
+        for kw in FEATURES_ON:
+            def make(**kw):
+                return cls(tester=None, worker_number=5, synchronous=True, device=CPU, **extra,
+                           **kw)
+            yield f"{cls.__name__}({_kw(kw)})", _construct(make, **kw)
+        calls = {
+            "_check_rule('median','exact',5)": lambda: cls._check_rule("median", "exact", 5),
+            "_check_rule('mean','fma',None,trim=0)":
+                lambda: cls._check_rule("mean", "fma", None, trim=0),
+            "_check_rule('bulyan','exact',6,byzantine=1)":
+                lambda: cls._check_rule("bulyan", "exact", 6, byzantine=1),
+            "_check_attack(None,())": lambda: cls._check_attack(None, ()),
+            "_check_attack('ipm',(1,),worker_number=8)":
+                lambda: cls._check_attack("ipm", (1,), worker_number=8),
+            "_check_attack('alie',[7,3],1.0,0.1,1.0,11)":
+                lambda: cls._check_attack("alie", [7, 3], 1.0, 0.1, 1.0, 11),
+            "_check_attack('alie',[7,3],None,0.1,2.0,11)":
+                lambda: cls._check_attack("alie", [7, 3], None, 0.1, 2.0, 11),
+            "_check_server_opt(None)": lambda: cls._check_server_opt(None),
+            "_check_server_opt('adam')": lambda: cls._check_server_opt("adam"),
+            "_check_server_opt('sgd',0.5,0.5)": lambda: cls._check_server_opt("sgd", 0.5, 0.5),
+            "_check_server_opt('sgd',server_tau=0.01)":
+                lambda: cls._check_server_opt("sgd", server_tau=0.01),
+        }
+        for key, call in calls.items():
+            yield f"{cls.__name__}.{key}", _outcome(lambda: repr(call()))
+
+
+# ---------------------------------------------------------------- ClientUpdateStore
+def store_calls():
+    """What ``ClientUpdateStore`` refuses before a launch, on a store of 4 CPU rows (a
+    well-formed call ends in the wrapper's "not on the GPU")."""
+    from distributed_learning_simulator_amd.aggregation import ClientUpdateStore
+    from distributed_learning_simulator_amd.layout import ParameterLayout
+    st = ClientUpdateStore(ParameterLayout.from_dict({"w": torch.zeros(2, 4)}), CPU, capacity=4)
+    P = st.layout.P
+    vectors = {"good": torch.zeros(P), "None": None, "list": [0.0] * P,
+               "fp64": torch.zeros(P, dtype=torch.float64), "2-D": torch.zeros(1, P),
+               "short": torch.zeros(P - 1), "long": torch.zeros(P + 1),
+               "meta": torch.zeros(P, device="meta")}
+    many = list(range(65))
+    G2 = [[1.0, 0.0], [0.0, 1.0]]
+    row_lists = {"[]": [], "[0,0]": [0, 0], "[-1]": [-1], "[4]": [4], "65": many, "[0,1]": [0, 1],
+                 "[1,2]": [1, 2]}
+    cases = {}
+    for (h, honest), (a, bad) in itertools.product(row_lists.items(), repeat=2):
+        cases[f"craft({h},{a})"] = lambda honest=honest, bad=bad: st.craft(honest, bad, 1.0, 0.0)
+    pairs = {"[0,1]": [0, 1], "[0]": [0], "[]": [], "[0,0]": [0, 0], "[-1,0]": [-1, 0],
+             "[3,4]": [3, 4], "65": many}
+    for (r, rows), (h, hrows) in itertools.product(pairs.items(), repeat=2):
+        cases[f"fold_history({r},{h})"] = lambda rows=rows, hrows=hrows: st.fold_history(rows, hrows)
+    id_lists = {"[5,3]": [5, 3], "[5,5]": [5, 5], "[5]": [5], "[5,'a']": [5, "a"]}
+    for (i, ids), (v, vec) in itertools.product(id_lists.items(), vectors.items()):
+        cases[f"foolsgold([0,1],{i},G,{v})"] = lambda ids=ids, vec=vec: st.foolsgold(
+            [0, 1], ids, G2, vec)
+        cases[f"centered_clip([0,1],{i},{v},1.0,2)"] = lambda ids=ids, vec=vec: st.centered_clip(
+            [0, 1], ids, vec, 1.0, 2)
+        cases[f"centered_clip([0,1],{i},{v},1.0,0)"] = lambda ids=ids, vec=vec: st.centered_clip(
+            [0, 1], ids, vec, 1.0, 0)
+    for kappa in (0.0, NAN, "1"):
+        cases[f"foolsgold(kappa={kappa!r})"] = lambda kappa=kappa: st.foolsgold(
+            [0, 1], [5, 3], G2, vectors["good"], kappa)
+    cases["foolsgold(G 1x1)"] = lambda: st.foolsgold([0, 1], [5, 3], [[1.0]], vectors["good"])
+    for (i, ids), f in itertools.product({**id_lists, "[1,2,3]": [1, 2, 3]}.items(), (-1, 0, 1)):
+        cases[f"bulyan([0,1,2],{i},{f})"] = lambda ids=ids, f=f: st.bulyan([0, 1, 2], ids, f)
+    for (i, ids), iters in itertools.product(id_lists.items(), (0, -1, 1, 1.5, "x")):
+        cases[f"geometric_median([0,1],{i},{iters!r})"] = lambda ids=ids, iters=iters: \
+            st.geometric_median([0, 1], ids, iters, 1e-6)
+    for v, vec in vectors.items():
+        cases[f"set_model({v})"] = lambda vec=vec: st.set_model(vec)
+    cases["server_opt_step without a model"] = lambda: (
+        setattr(st, "model", None), st.server_opt_step(vectors["good"], 0, (1.0,) * 6))[1]
+    for key, call in cases.items():
+        yield key, _outcome(lambda: (call(), "ok")[1])
+
+
 SECTIONS = {"constructor_grid": constructor_grid, "constructor_values": constructor_values,
             "constructor_pairs": constructor_pairs, "constructor_attacks": constructor_attacks,
             "subclasses": subclasses, "subset_models": subset_models}
@@ -452,6 +690,11 @@ SECTIONS.update({f"native_{name}": (lambda name=name: _vector_wrapper_cases(name
                  for name in VECTOR_WRAPPERS})
 SECTIONS["native_topk_workspace"] = topk_workspace_cases
 SECTIONS["native_required_none"] = required_none_cases
+SECTIONS.update({"constructor_kinds": constructor_kinds, "constructor_owners": constructor_owners,
+                 "constructor_precedence": constructor_precedence,
+                 "subclass_features": subclass_features, "store_calls": store_calls})
+SECTIONS["constructor_attributes"] = constructor_attributes
+SECTIONS["checker_misuse"] = checker_misuse
 
 
 def enumerate_section(section):
