@@ -404,6 +404,10 @@ def trimmed_mean(U, rows, trim, P, out, stream=None):
     return _to_one_row(fn, U, ldu, rows, K, trim, P, out, stream)
 
 
+# DLS_PAIRDIST_MAX_WAVES (include/dls_hip.h): past it a wave takes several periods
+PAIRDIST_MAX_WAVES = 2048
+
+
 def pairwise_sqdist(U, rows, P, out=None, stream=None):
     """Squared Euclidean distances between the K = rows.numel() selected rows of U over
     their first P elements (dls_pairwise_sqdist_f32): an fp64 [K, K] device tensor,
@@ -640,6 +644,10 @@ def server_opt_step(kind, agg, x, m, v, out, P, lr, beta1, beta2, tau, stream=No
 
 # ------------------------------------------------------- top-k sparsification
 TOPK_MAX_P = (1 << 31) - 1  # idx is int32
+# DLS_TOPK_* (include/dls_hip.h): the launch shape of dls_topk_compress_f32
+TOPK_CHUNK = 4096  # coordinates per chunk (one block and trip)
+TOPK_HIST_BLOCKS = 2048  # the histogram passes' grid cap: further chunks are grid-strided
+TOPK_SCAN_BLOCK = 1024  # threads of the one scan block, ceil(chunks / it) chunks each
 
 
 def _topk_extent(fn, P):

@@ -32,7 +32,7 @@
 namespace dls {
 namespace {
 
-constexpr int kMaxWaves = 2048;    // 256 CUs x 8 resident waves
+constexpr int kMaxWaves = DLS_PAIRDIST_MAX_WAVES;  // 256 CUs x 8 resident waves
 constexpr int kPartDoubles = 4096; // per wave: 64 pairs x 64 lanes
 constexpr int kFinishPhases = 16;
 

@@ -42,10 +42,11 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr int kVecs = 4;                          // 16-byte vectors per thread and chunk
-constexpr int kChunk = kBlock * kVecs * 4;        // 4096 coordinates
-constexpr int kHistBlocks = 2048;                 // grid-strided histogram passes
+constexpr int kChunk = DLS_TOPK_CHUNK;            // 4096 coordinates
+constexpr int kHistBlocks = DLS_TOPK_HIST_BLOCKS; // grid-strided histogram passes
 constexpr int kBins = 2048;                       // 11-bit first digit; the others use 1024
-constexpr int kScanBlock = 1024;
+constexpr int kScanBlock = DLS_TOPK_SCAN_BLOCK;
+static_assert(kChunk == kBlock * kVecs * 4, "a block covers one chunk per trip");
 constexpr uint32_t kAbs = 0x7fffffffu;
 constexpr uint32_t kInfKey = 0x7f800000u;
 

@@ -233,7 +233,13 @@ int dls_craft_rows_f32(float *U, int64_t ldu, const int32_t *hrows, int32_t Kh,
  * `workspace` in ascending order.
  * If a row of the pair holds an inf or NaN, or a chain overflows, D[a][b]
  * (a != b) is +inf or NaN; callers treat both as +inf.  Pairs of clean rows are
- * unaffected. */
+ * unaffected.
+ * Launch shape: a period is the longest run of coordinates one fp32 chain covers
+ * (7680, 1920, 448 or 96 for K <= 8, 16, 32, 64); with periods = ceil(P / period),
+ * ppw = ceil(periods / DLS_PAIRDIST_MAX_WAVES) and nW = ceil(periods / ppw), wave w of
+ * the nW waves takes the periods w, w + nW, ..., at most ppw of them; the workspace
+ * holds nW * 4096 doubles. */
+#define DLS_PAIRDIST_MAX_WAVES 2048
 int64_t dls_pairwise_sqdist_workspace(int32_t K, int64_t P);
 int dls_pairwise_sqdist_f32(const float *U, int64_t ldu, const int32_t *rows, int32_t K, int64_t P,
                             double *D, void *workspace, dls_stream_t stream);
@@ -813,7 +819,14 @@ int dls_sum_rows_f64(const float *v, int64_t ldn, int32_t S, int64_t n, double *
  * arrays, nothing synchronised inside the call.  Integer histogram counts use LDS and
  * global integer atomics (order-independent sums); every output position comes from
  * the scans; there are no floating-point atomics: the outputs do not depend on the
- * stream, the grid or the scheduling. */
+ * stream, the grid or the scheduling.
+ * Launch shape: chunks of DLS_TOPK_CHUNK coordinates; the histogram passes run at most
+ * DLS_TOPK_HIST_BLOCKS blocks, block b taking the chunks b, b + DLS_TOPK_HIST_BLOCKS,
+ * ...; the scan is one block of DLS_TOPK_SCAN_BLOCK threads, each owning ceil(chunks /
+ * DLS_TOPK_SCAN_BLOCK) consecutive chunks. */
+#define DLS_TOPK_CHUNK 4096
+#define DLS_TOPK_HIST_BLOCKS 2048
+#define DLS_TOPK_SCAN_BLOCK 1024
 int64_t dls_topk_workspace(int64_t P);
 int dls_topk_compress_f32(const float *w, const float *base, float *e, int64_t P, int64_t k,
                           int32_t *idx, float *val, int32_t *stats, void *workspace,

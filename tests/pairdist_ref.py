@@ -6,6 +6,7 @@ package has no CPU path).  Written independently of
 """
 import numpy as np
 
+from distributed_learning_simulator_amd import _native
 from tests import robust_ref
 
 TOL = 2.0 ** -17  # the contract's bound: (120 + 8) * 2^-24 relative
@@ -23,6 +24,81 @@ def sqdist(X):
             D[a] = np.einsum("kp,kp->k", d, d) if np.isfinite(d).all() else (d * d).sum(axis=1)
     D[np.arange(K), np.arange(K)] = 0.0
     return D
+
+
+def int_rows(K, P, seed):
+    """int8 [K, P] in [-8, 8]; row 0 all even and row 1 all odd, so that pair has no
+    coordinate with d = 0."""
+    rng = np.random.default_rng(seed)
+    X = rng.integers(-8, 9, (K, P), dtype=np.int8)
+    X[0] = 2 * rng.integers(-4, 5, P, dtype=np.int8)
+    if K > 1:
+        X[1] = 2 * rng.integers(-4, 4, P, dtype=np.int8) + 1
+    return X
+
+
+def sqdist_int(X, block=1 << 21):
+    """The exact fp64 [K, K] squared distances of integer rows with |x| <= 8, as
+    n_a + n_b - 2 x_a.x_b from fp64 Gram blocks: every partial sum is an integer of at
+    most 256 P < 2^53, so BLAS is exact in any order.  The kernel's result is exact for
+    such rows too (|d| <= 16, an fp32 chain of at most 120 d^2 is an integer <= 30720 <
+    2^24, the fp64 sums are integers), whatever its work split: its bits must be these."""
+    X = np.asarray(X)
+    K, P = X.shape
+    assert np.abs(X).max(initial=0) <= 8 and 256 * P < 2 ** 53
+    G = np.zeros((K, K), np.float64)
+    for c in range(0, P, block):
+        B = X[:, c:c + block].astype(np.float64)
+        G += B @ B.T
+    n = np.diag(G)
+    return n[:, None] + n[None, :] - 2.0 * G
+
+
+# ------------------------------------------------------------------ the launch plan
+# A model of csrc/pairdist.hip's work split, from DLS_PAIRDIST_MAX_WAVES and the tile
+# geometry alone (tests/test_pairdist_host.py holds it against the workspace query).
+PART_DOUBLES = 4096  # per wave: 64 pairs x 64 lanes
+
+
+def block_grid(K):
+    """G: the K rows, padded to 8 G, form a G x G grid of 8 x 8 blocks of pairs."""
+    return 1 if K <= 8 else 2 if K <= 16 else 4 if K <= 32 else 8
+
+
+def tile(K):
+    """Coordinates per tile: eight 16-byte loads per lane over 8 G rows."""
+    return 2048 // (8 * block_grid(K))
+
+
+def period(K):
+    """Coordinates per flush: as many tiles as keep an fp32 chain at 120 terms or fewer."""
+    G = block_grid(K)
+    steps = tile(K) // (64 // (G * G))  # chain terms per tile
+    return (120 // steps) * tile(K)
+
+
+def plan(K, P):
+    """(period, periods, ppw, nW): wave w of nW takes the periods w, w + nW, ..., ppw at most."""
+    per = period(K)
+    periods = -(-P // per) if P > 0 else 1
+    ppw = -(-periods // _native.PAIRDIST_MAX_WAVES)
+    return per, periods, ppw, -(-periods // ppw)
+
+
+def workspace_bytes(K, P):
+    return plan(K, P)[3] * PART_DOUBLES * 8
+
+
+def _past_cap(K, rounds):
+    """The shortest rows with more than ``rounds`` periods per wave on K's grid, ending
+    half-way into the second tile of the last period."""
+    return rounds * _native.PAIRDIST_MAX_WAVES * period(K) + tile(K) + tile(K) // 2 + 4
+
+
+# (K, P) past the launch cap, one per block grid: ppw = 2, 3 (the workload's size:
+# ResNet-18 after padding), 3, 2
+SCALE_SHAPES = ((2, _past_cap(2, 1)), (9, 11_173_964), (17, _past_cap(17, 2)), (33, _past_cap(33, 1)))
+SCALE_PPW = (2, 3, 3, 2)
 
 
 def krum_scores(D, f):

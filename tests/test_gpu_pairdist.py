@@ -2,7 +2,10 @@
 multi-Krum layers above it.  Distances are compared with the fp64 numpy reference
 tests/pairdist_ref.py at the contract's relative tolerance 2^-17; the exact
 properties (diagonal, symmetry, repeatability, layout and permutation independence)
-and every aggregate are compared bit for bit."""
+and every aggregate are compared bit for bit.  Rows of small integers, whose distances
+the kernel's arithmetic gives exactly, are compared bit for bit with the exact integer
+sums, at the usual lengths and on every block grid past the wave cap."""
+import ctypes
 import functools
 
 import numpy as np
@@ -97,6 +100,72 @@ def test_accuracy_more_than_one_period_per_wave(K, P):
     check_exact_properties(D)
     check_close(D, PR.sqdist(X), f"K={K} P={P}")
     assert np.array_equal(bits(gpu_D(X)), bits(D))
+
+
+# ------------------------------------------------------------- exact integer rows
+# Rows of integers in [-8, 8]: every difference, every fp32 chain (at most 120 squares of
+# at most 256: below 2^24) and every fp64 sum is an integer, so D is exact whatever the
+# work split, and a coordinate dropped or counted twice changes its bits
+# (PR.sqdist_int).  Row 0 is even and row 1 odd: no coordinate of that pair adds 0.
+@functools.lru_cache(maxsize=None)
+def _int_case(K, P):
+    """int8 rows and their exact D, made once (the fp32 rows are 4 x larger: per use)."""
+    X = PR.int_rows(K, P, seed=K + P % 1009)
+    D = PR.sqdist_int(X)
+    X.setflags(write=False)
+    D.setflags(write=False)
+    return X, D
+
+
+def check_exact_integer(K, P):
+    X, want = _int_case(K, P)
+    D = run(X.astype(np.float32).view(np.uint32), range(K), P)
+    check_exact_properties(D)
+    assert np.array_equal(bits(D), bits(want)), (K, P, float(np.abs(D - want).max()))
+    assert K < 2 or want[0, 1] >= P
+
+
+@pytest.mark.parametrize("P", [4, 64, 1088, 70004])
+@pytest.mark.parametrize("K", [5, 16, 17, 64])
+def test_exact_on_integer_rows(K, P):
+    """One K per block grid at the accuracy test's lengths."""
+    check_exact_integer(K, P)
+
+
+@pytest.mark.parametrize("K, P", PR.SCALE_SHAPES)
+def test_exact_on_integer_rows_past_the_wave_cap(K, P):
+    """Every block grid with two or three periods per wave and a tail that ends inside a
+    tile; K = 9 at the length of ResNet-18."""
+    assert PR.plan(K, P)[2] >= 2
+    check_exact_integer(K, P)
+
+
+@pytest.mark.parametrize("K, P", PR.SCALE_SHAPES)
+def test_workspace_of_exactly_the_queried_size(K, P):
+    """The library's entry point on a workspace slice of dls_pairwise_sqdist_workspace(K, P)
+    bytes inside a sentinel-filled buffer: the exact D, and no byte outside the slice or
+    outside D changed."""
+    from distributed_learning_simulator_amd import _native
+    L = _native.lib()
+    X, want = _int_case(K, P)
+    need = int(L.dls_pairwise_sqdist_workspace(K, P))
+    assert need == PR.workspace_bytes(K, P)
+    pad = 4096
+    U = torch.from_numpy(X.astype(np.float32)).to(DEV)
+    rows = torch.arange(K, dtype=torch.int32, device=DEV)
+    work = torch.full((need + 2 * pad,), 0xA5, dtype=torch.uint8, device=DEV)
+    out = torch.full((K * K + 2 * pad,), -7.0, dtype=torch.float64, device=DEV)
+    p = lambda t, off=0: ctypes.c_void_p(t.data_ptr() + off)
+    torch.cuda.synchronize()
+    rc = L.dls_pairwise_sqdist_f32(p(U), P, p(rows), K, P, p(out, 8 * pad), p(work, pad),
+                                   ctypes.c_void_p(torch.cuda.current_stream(DEV).cuda_stream))
+    assert rc == 0, L.dls_last_error()
+    torch.cuda.synchronize()
+    for name, buf, n, fill in (("workspace", work, need, 0xA5), ("D", out, K * K, -7.0)):
+        assert bool((buf[:pad] == fill).all()), f"{name}: written before its first element"
+        assert bool((buf[pad + n:] == fill).all()), f"{name}: written past its last element"
+    D = out[pad:pad + K * K].cpu().numpy().reshape(K, K)
+    assert np.array_equal(bits(D), bits(want))
 
 
 def test_zero_length_rows_give_zero():

@@ -21,15 +21,15 @@ def _dev():
     return torch.device("cuda", 0)
 
 
-def run_compress(w, base, e, k, stream=None):
+def run_compress(w, base, e, k, stream=None, ws_fill=0xFF):
     """The device outputs of one call as numpy: idx, val, e_new, stats.  The workspace is
-    filled with 0xFF first: it may hold garbage on entry."""
+    filled with ``ws_fill`` bytes first: it may hold garbage on entry."""
     from distributed_learning_simulator_amd import _native
     dev = _dev()
     P = w.size
     tw, tb, te = (torch.from_numpy(np.ascontiguousarray(a, dtype=F32)).to(dev) for a in (w, base, e))
     ws = _native.topk_workspace(P, dev)
-    ws.fill_(0xFF)
+    ws.fill_(ws_fill)
     idx = torch.full((k,), -1, dtype=torch.int32, device=dev)
     val = torch.full((k,), 123.0, dtype=torch.float32, device=dev)
     stats = torch.full((2,), -1, dtype=torch.int32, device=dev)

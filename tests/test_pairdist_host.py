@@ -324,3 +324,63 @@ def test_source_plumbing():
         assert name in _native.SIGNATURES
     with open(os.path.join(csrc, "pairdist.hip")) as fh:
         assert "getenv" not in fh.read()
+
+
+# ------------------------------------------------------------------ the launch plan
+def test_launch_shape_constant_matches_the_header():
+    import re
+    from distributed_learning_simulator_amd import _native
+    with open(os.path.join(ROOT, "include", "dls_hip.h")) as fh:
+        macros = dict(re.findall(r"#define DLS_PAIRDIST_(\w+) (\d+)", fh.read()))
+    assert {k: int(v) for k, v in macros.items()} == {"MAX_WAVES": _native.PAIRDIST_MAX_WAVES}
+
+
+def test_reference_integer_rows_are_exact():
+    """sqdist_int against the term-by-term sum in Python integers, and against sqdist."""
+    X = PR.int_rows(5, 1000, seed=0)
+    assert X.dtype == np.int8 and X.min() == -8 and X.max() == 8
+    assert (X[0] % 2 == 0).all() and (X[1] % 2 != 0).all()
+    want = [[sum((int(x) - int(y)) ** 2 for x, y in zip(a, b)) for b in X] for a in X]
+    D = PR.sqdist_int(X, block=300)  # several blocks, a ragged last one
+    assert D.dtype == np.float64 and D.tolist() == want
+    assert np.array_equal(D, PR.sqdist(X.astype(np.float32))) and D[0, 1] >= 1000
+
+
+def test_plan_model_matches_the_workspace_query():
+    """pairdist_ref.plan against dls_pairwise_sqdist_workspace (a host function) for every
+    grid, on both sides of each multiple of the wave cap."""
+    from distributed_learning_simulator_amd import _native
+    ws = _native.lib().dls_pairwise_sqdist_workspace
+    W = _native.PAIRDIST_MAX_WAVES
+    assert [PR.period(K) for K in (1, 8, 9, 16, 17, 32, 33, 64)] == \
+        [7680, 7680, 1920, 1920, 448, 448, 96, 96]
+    for K in (1, 2, 8, 9, 16, 17, 32, 33, 64):
+        per = PR.period(K)
+        sizes = {0, 4, per - 4, per, per + 4, 70004, 11_173_964}
+        for n in (W - 1, W, W + 1, 2 * W - 1, 2 * W, 2 * W + 1, 3 * W, 3 * W + 1):
+            sizes |= {n * per - 4, n * per, n * per + 4}
+        for P in sorted(sizes):
+            assert ws(K, P) == PR.workspace_bytes(K, P), (K, P)
+            _, periods, ppw, nW = PR.plan(K, P)
+            assert nW <= W and ppw * nW >= periods and (ppw - 1) * nW < periods
+        assert [PR.plan(K, W * per + d)[2] for d in (0, 4)] == [1, 2]
+        assert [PR.plan(K, 2 * W * per + d)[2] for d in (0, 4)] == [2, 3]
+    assert PR.plan(9, 11_173_964) == (1920, 5820, 3, 1940)
+    assert PR.plan(17, 920004)[1:3] == (2054, 2) and PR.plan(64, 200004)[1:3] == (2084, 2)
+
+
+def test_scale_shapes_reach_the_paths_they_are_named_for():
+    """One shape per block grid with several periods per wave and a tail that ends inside
+    a tile: a change to the cap or the tile geometry fails here, not by silently
+    un-testing the GPU path."""
+    assert [PR.block_grid(K) for K, _ in PR.SCALE_SHAPES] == [1, 2, 4, 8]
+    for (K, P), ppw in zip(PR.SCALE_SHAPES, PR.SCALE_PPW):
+        per, periods, got, nW = PR.plan(K, P)
+        assert got == ppw >= 2 and P % 4 == 0 and P % PR.tile(K) != 0
+        assert nW < periods  # some wave does take a second period
+    assert sorted(PR.SCALE_PPW) == [2, 2, 3, 3]
+    assert PR.SCALE_SHAPES[1] == (9, 11_173_964)
+    # "just over": one period less and the wave count is back under the cap's multiple
+    for (K, P), ppw in zip(PR.SCALE_SHAPES, PR.SCALE_PPW):
+        if K != 9:
+            assert PR.plan(K, P - PR.period(K))[2] == ppw - 1

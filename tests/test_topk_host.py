@@ -533,3 +533,55 @@ def test_padding_slots_are_only_ever_sent_as_zeros(monkeypatch):
     real = list(range(15)) + [64, 65, 66]
     assert p.idx.tolist() == real and len(p) == 18 and p.nbytes == 144
     assert float(w.residual.abs().max()) == 0.0
+
+
+# ------------------------------------------------------------------ the launch plan
+def test_launch_shape_constants_match_the_header():
+    import os
+    import re
+    from distributed_learning_simulator_amd import _native
+    text = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                             "include", "dls_hip.h")).read()
+    macros = dict(re.findall(r"#define DLS_TOPK_(\w+) (\d+)", text))
+    assert {k: int(v) for k, v in macros.items()} == {
+        "CHUNK": _native.TOPK_CHUNK, "HIST_BLOCKS": _native.TOPK_HIST_BLOCKS,
+        "SCAN_BLOCK": _native.TOPK_SCAN_BLOCK}
+
+
+def test_plan_model_matches_the_workspace_query():
+    """topk_ref's chunk count against dls_topk_workspace (a host function) on both sides
+    of every chunk edge near each launch cap, and at the ends of the range."""
+    from distributed_learning_simulator_amd import _native
+    L = _native.lib()
+    C, H, S = _native.TOPK_CHUNK, _native.TOPK_HIST_BLOCKS, _native.TOPK_SCAN_BLOCK
+    sizes = {4, 64, C - 4, C, C + 4, 65540, topk_ref.P_SCAN2, topk_ref.P_STRIDE, topk_ref.P_RESNET,
+             _native.TOPK_MAX_P - 3}
+    for cap in (S, 2 * S, H, 2 * H):
+        for n in (cap - 1, cap, cap + 1):
+            sizes |= {n * C - 4, n * C, n * C + 4}
+    for P in sorted(sizes):
+        assert L.dls_topk_workspace(P) == topk_ref.workspace_bytes(P), P
+        assert topk_ref.nchunks(P) == (P + C - 1) // C
+    # the trips and the chunks per scan thread step exactly past a full grid / block
+    assert [topk_ref.hist_trips(n * C) for n in (1, H, H + 1, 2 * H, 2 * H + 1)] == [1, 1, 2, 2, 3]
+    assert [topk_ref.hist_trips(H * C + d) for d in (0, 4)] == [1, 2]
+    assert [topk_ref.scan_per(n * C) for n in (1, S, S + 1, 2 * S, 2 * S + 1)] == [1, 1, 2, 2, 3]
+    assert [topk_ref.scan_per(S * C + d) for d in (0, 4)] == [1, 2]
+
+
+def test_scale_shapes_reach_the_paths_they_are_named_for():
+    """A change to a launch cap fails here, not by silently un-testing the GPU path."""
+    from distributed_learning_simulator_amd import _native
+    C, H, S = _native.TOPK_CHUNK, _native.TOPK_HIST_BLOCKS, _native.TOPK_SCAN_BLOCK
+    R = topk_ref
+    # P_SCAN2: two chunks per scan thread, the upper threads own nothing, one ragged vector
+    assert R.scan_per(R.P_SCAN2) == 2 and R.scan_per(R.P_SCAN2 - 2 * C) == 1
+    assert R.nchunks(R.P_SCAN2) < 2 * (S - 1) and R.P_SCAN2 % C == 4
+    # P_STRIDE: a second histogram trip that holds the ragged chunk; three chunks per scan thread
+    assert R.hist_trips(R.P_STRIDE) == 2 and R.hist_trips(R.P_STRIDE - 2 * C) == 1
+    assert R.nchunks(R.P_STRIDE) == H + 2 and 0 < R.P_STRIDE % C < C
+    assert R.scan_per(R.P_STRIDE) >= 3
+    assert R.hist_trips(R.P_RESNET) >= 2 and R.scan_per(R.P_RESNET) >= 3
+    assert R.nchunks(R.P_RESNET) == 2729 and R.nchunks(R.P_RESNET) - H == 681
+    for P in (R.P_SCAN2, R.P_STRIDE, R.P_RESNET):
+        assert P % 4 == 0 and P <= _native.TOPK_MAX_P

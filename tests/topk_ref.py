@@ -61,6 +61,38 @@ def sparse_fedavg(base, payloads, ns):
     return out
 
 
+# ------------------------------------------------------------------ the launch plan
+# A model of csrc/topk.hip's work split, from the DLS_TOPK_* constants alone
+# (tests/test_topk_host.py holds it against dls_topk_workspace).
+WS_HEAD_WORDS = 3 * 2048 + 16  # the three digit histograms (2048 words each) and the state
+
+
+def nchunks(P):
+    return -(-int(P) // _native.TOPK_CHUNK)
+
+
+def hist_trips(P):
+    """Chunks the busiest block of the histogram passes (form, refine) walks."""
+    return -(-nchunks(P) // _native.TOPK_HIST_BLOCKS)
+
+
+def scan_per(P):
+    """Consecutive chunks per thread of the scan block."""
+    return -(-nchunks(P) // _native.TOPK_SCAN_BLOCK)
+
+
+def workspace_bytes(P):
+    """Histograms and state, then two count arrays of nchunks + 1 words."""
+    return 4 * (WS_HEAD_WORDS + 2 * (nchunks(P) + 1))
+
+
+# The smallest rows that reach each path past a launch cap, and the workload's own size
+# (ResNet-18 after padding); tests/test_gpu_topk_scale.py runs them.
+P_SCAN2 = (_native.TOPK_SCAN_BLOCK + 1) * _native.TOPK_CHUNK + 4    # two chunks per scan thread
+P_STRIDE = (_native.TOPK_HIST_BLOCKS + 1) * _native.TOPK_CHUNK + 68  # a second histogram trip
+P_RESNET = 11_173_964
+
+
 # ------------------------------------------------------------------ CPU doubles
 def _np(t):
     return t.detach().cpu().numpy()
