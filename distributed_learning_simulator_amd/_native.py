@@ -82,6 +82,11 @@ SIGNATURES = {
     "dls_topk_workspace": ([_i64], _i64),
     "dls_topk_compress_f32": ([_p, _p, _p, _i64, _i64, _p, _p, _p, _p, _p], _i32),
     "dls_sparse_fedavg_f32": ([_p, _p, _p, _p, _p, _i32, _f32, _i64, _p, _p], _i32),
+    "dls_philox_u32": ([_p, _i64, _u64, _u64, _i64, _p], _i32),
+    "dls_philox_normal_f32": ([_p, _i64, _u64, _u64, _i64, _p], _i32),
+    "dls_normal_from_bits_f32": ([_p, _i64, _p, _p], _i32),
+    "dls_dp_clip_noise_step_f32": ([_p, _i64, _p, _i32, _p, _i64, _p, _f32, _u64, _u64, _p],
+                                   _i32),
     "dls_subset_gemm_f32": ([_p, _i32, _i32, _p, _i64, _p, _i64, _p, _i64, _p], _i32),
     "dls_sign_pack_f32": ([_p, _i64, _i32, _i64, _p, _i64, _p, _p], _i32),
     "dls_sign_vote_count": ([_p, _i64, _p, _i32, _i64, _p, _p], _i32),
@@ -187,6 +192,7 @@ CSRC_HASHED = [  # the Makefile's HASHED, in its order
     "gram.hip",
     "serveropt.hip",
     "topk.hip",
+    "dpnoise.hip",
     "dls_common.h",
     "quant_common.h",
     "loss_common.h",
@@ -569,6 +575,105 @@ def centered_clip_step(U, rows, c, P, z, dist2=None, stream=None):
     contiguous fp32 [K] tensor (the callers' min(1, tau / distance) / K); the rest as
     in rows_sqdist_to.  Returns (z, dist2)."""
     return _fused_step("centered_clip_step", "c", U, rows, c, P, z, dist2, stream)
+
+
+# ------------------------------------------- the random stream and the DP-FedAvg step
+NORMAL_MAX = math.sqrt(48.0 * math.log(2.0))  # |g| of the stream's normals never exceeds it
+
+
+def _uint64(fn, name, v):
+    """int(v); RuntimeError unless v is an integer in 0..2^64 - 1."""
+    if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < 1 << 64:
+        raise RuntimeError(f"{fn}: {name}={v!r} must be an integer in 0..2^64 - 1")
+    return v
+
+
+def _stream_range(fn, n, first):
+    n, first = int(n), int(first)
+    if n < 0 or first < 0 or first + n > (1 << 63) - 1:
+        raise RuntimeError(f"{fn}: n={n} and first={first} must be non-negative, "
+                           "first + n <= 2^63 - 1")
+    return n, first
+
+
+def _philox(fn, dtype, n, seed, stream_id, first, out, device, stream):
+    n, first = _stream_range(fn, n, first)
+    seed, stream_id = _uint64(fn, "seed", seed), _uint64(fn, "stream_id", stream_id)
+    if out is None:
+        if device is None:
+            raise RuntimeError(f"{fn}: out or device is needed")
+        out = torch.empty(n, dtype=dtype, device=device)
+    _unit_vector(fn, "out", out, dtype, n, count=("n", n))
+    _ptr(out)  # no CPU path
+    if n != 0:
+        _check(getattr(lib(), f"dls_{fn}")(_ptr(out), n, seed, stream_id, first,
+                                           _stream(stream, out)), f"dls_{fn}")
+    return out
+
+
+def philox_u32(n, seed, stream_id, first=0, out=None, device=None, stream=None):
+    """The words of the library's random stream (dls_philox_u32): out[i] is the Philox4x32-10
+    word of coordinate first + i under (seed, stream_id), i < n; exact, a function of (seed,
+    stream_id, coordinate) alone.  The bit pattern is held as int32 (torch has no arithmetic
+    on uint32): view the numpy array as uint32.  seed, stream_id: integers in 0..2^64 - 1;
+    out: an int32 vector of at least n elements (default: a new one on ``device``)."""
+    return _philox("philox_u32", torch.int32, n, seed, stream_id, first, out, device, stream)
+
+
+def philox_normal(n, seed, stream_id, first=0, out=None, device=None, stream=None):
+    """The standard normals of the same coordinates (dls_philox_normal_f32): Box-Muller on
+    the word pairs of a block, |g| <= NORMAL_MAX = sqrt(48 ln 2) ~ 5.768 (the tail is
+    truncated there).  out: an fp32 vector of at least n elements (default: a new one on
+    ``device``)."""
+    return _philox("philox_normal_f32", torch.float32, n, seed, stream_id, first, out, device,
+                   stream)
+
+
+def normal_from_bits(bits, out=None, stream=None):
+    """The Box-Muller transform alone (dls_normal_from_bits_f32) on caller-chosen words:
+    (out[2j], out[2j+1]) from the word pair (bits[2j], bits[2j+1]).  bits: an int32 vector
+    (the words' bit patterns) of an even number of elements; out: an fp32 vector of at least
+    as many (default: a new one)."""
+    fn = "normal_from_bits"
+    _check_tensor(fn, "bits", bits, torch.int32, 0, "an int32 vector with unit stride",
+                  exact=False, contiguous=False)
+    n = bits.numel()
+    if n % 2 != 0:
+        raise RuntimeError(f"{fn}: bits holds n={n} words, not word pairs")
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=bits.device)
+    _unit_vector(fn, "out", out, torch.float32, n, count=("n", n))
+    _check_same_device(fn, bits, _anchor="bits", out=out)
+    _ptr(bits), _ptr(out)  # no CPU path
+    if n != 0:
+        _check(lib().dls_normal_from_bits_f32(_ptr(bits), n, _ptr(out), _stream(stream, bits)),
+               "dls_normal_from_bits_f32")
+    return out
+
+
+def dp_clip_noise_step(U, rows, c, P, z, sigma, seed, stream_id, stream=None):
+    """One fused DP-FedAvg step (dls_dp_clip_noise_step_f32), in place: z[:P] = fl32(y +
+    fl32(sigma * g)) with y the new z of ``centered_clip_step`` from the same operands, bit
+    for bit, and g[p] the normal ``philox_normal`` gives coordinate p under (seed,
+    stream_id); sigma == 0 draws nothing and stores y.  sigma: finite, >= 0 (used as its
+    fp32 value); seed, stream_id: integers in 0..2^64 - 1; the rest as in
+    centered_clip_step, without distances.  Returns z."""
+    fn = "dp_clip_noise_step"
+    K, P, ldu = _rows_operands(fn, U, rows, P)
+    _k_tensor(fn, "c", c, torch.float32, (K,))
+    _f32_vector(fn, "z", z, P)
+    if isinstance(sigma, bool) or not isinstance(sigma, (int, float)) \
+            or not math.isfinite(fl32(sigma)) or sigma < 0:
+        raise RuntimeError(f"{fn}: sigma={sigma!r} must be finite in fp32 and >= 0")
+    seed, stream_id = _uint64(fn, "seed", seed), _uint64(fn, "stream_id", stream_id)
+    _rows_placement(fn, U, ("z",), rows=rows, c=c, z=z)
+    _check_disjoint({"U": U, "z": z[:P]}, f"{fn}: {{a}} and {{b}} overlap")
+    _ptr(U), _ptr(rows), _ptr(c), _ptr(z)  # no CPU path
+    if P != 0:
+        _check(lib().dls_dp_clip_noise_step_f32(_ptr(U), ldu, _ptr(rows), K, _ptr(c), P, _ptr(z),
+                                                fl32(sigma), seed, stream_id, _stream(stream, U)),
+               "dls_dp_clip_noise_step_f32")
+    return z
 
 
 # DLS_SERVER_OPT_* (include/dls_hip.h): the kinds, and the launch shape of the step

@@ -220,6 +220,36 @@ def clip_scales(dist2, tau):
                                       dtype=torch.float64).float().tolist()
 
 
+def dp_epsilon(noise_multiplier, rounds, delta):
+    """The epsilon of the (epsilon, delta) differential-privacy guarantee of ``rounds``
+    Gaussian releases, each of L2 sensitivity C with noise of standard deviation
+    ``noise_multiplier`` * C (z * C): what ``ClientUpdateStore.dp_mean`` releases per round.
+
+    Adjacency: two rounds' inputs are neighbours when one client's clipped update is
+    replaced by zero, the denominator K (the number of clients averaged) staying fixed,
+    with every client taking part in every round (no subsampling, so no amplification).
+    The sum of the clipped updates then moves by at most C and its mean, with noise of
+    standard deviation z * C / K, is the Gaussian mechanism with multiplier z.  One release
+    is (alpha, alpha / (2 z^2))-Renyi DP for every order alpha > 1; T releases compose to
+    alpha T / (2 z^2), and Mironov 2017, Prop. 3 converts that to (alpha T / (2 z^2) +
+    ln(1 / delta) / (alpha - 1), delta)-DP.  The best order has a closed form and gives
+        epsilon = T / (2 z^2) + sqrt(2 T ln(1 / delta)) / z.
+    Returns ``inf`` for noise_multiplier == 0 (no noise, no guarantee) and otherwise 0.0 for
+    rounds == 0.
+    ValueError: delta outside (0, 1), rounds not a non-negative integer, or a
+    noise_multiplier that is not a finite number >= 0."""
+    z = finite_number("noise_multiplier", noise_multiplier)
+    if z < 0:
+        raise ValueError(f"noise_multiplier must be >= 0, not {noise_multiplier!r}")
+    if isinstance(rounds, bool) or not isinstance(rounds, int) or rounds < 0:
+        raise ValueError(f"rounds must be a non-negative integer, not {rounds!r}")
+    if isinstance(delta, bool) or not isinstance(delta, (int, float)) or not 0.0 < delta < 1.0:
+        raise ValueError(f"delta must be in (0, 1), not {delta!r}")
+    if z == 0.0:
+        return math.inf
+    return rounds / (2.0 * z * z) + math.sqrt(2.0 * rounds * math.log(1.0 / delta)) / z
+
+
 def foolsgold_weights(G, kappa=1.0):
     """The FoolsGold weights (Fung, Yoon & Beschastnikh, RAID 2020) from the [K, K] Gram
     matrix of the clients' accumulated updates, on the host in fp64: (alpha, info).
@@ -660,6 +690,51 @@ class ClientUpdateStore:
 
         self._iterate("centered_clip", active, iters, flat, step, info, trace)
         info["moved"] = moved.cpu().tolist()
+        return flat, info
+
+    def dp_mean(self, rows, ids, start, clip, noise_multiplier, seed, stream_id, out=None):
+        """One release of client-level DP-FedAvg (McMahan et al. 2018) over the given rows
+        (client ``ids[i]`` in ``rows[i]``): every client's update U_k - ``start`` is clipped
+        to the norm ``clip`` (C), the clipped updates are averaged and Gaussian noise of
+        standard deviation sigma = fl32(noise_multiplier * C / n_kept) is added to every
+        coordinate: start + (1 / n) sum_k min(1, C / |U_k - start|) (U_k - start) + N(0,
+        sigma^2).  The clients are taken in id order (distinct, sortable ids), so the result
+        is the same bits for any arrival order; the sample counts play no part.  One
+        distance pass against ``start`` (dls_rows_sqdist_to_f32), one copy of K doubles to
+        the host, ``clip_scales``, then one fused launch (dls_dp_clip_noise_step_f32) that
+        reads the rows once.  A client whose distance is not finite is rejected (ValueError
+        when none is left) and n_kept counts the others.  The noise is the library's
+        Philox stream under (``seed``, ``stream_id``), coordinate p of the flat layout
+        drawing value p: the caller gives every release a ``stream_id`` of its own (the
+        same pair draws the same noise again), and |noise| <= 5.768 sigma (the stream's
+        normals are truncated at sqrt(48 ln 2)).  noise_multiplier == 0 draws nothing: the
+        result is then ``centered_clip`` with one step and tau = clip, bit for bit.
+        ``start`` is an fp32 device vector of ``layout.P`` elements and is never modified.
+        ``dp_epsilon`` accounts for the releases and states the adjacency.  Returns (flat,
+        info): ``norms`` {id: update norm}, ``scales`` {id: s, 1.0 for a client inside the
+        radius}, ``rejected`` (sorted ids), ``sigma`` (the fp32 value used) and
+        ``clipped_fraction`` (of the clients kept)."""
+        _, active = self._in_id_order("dp_mean", rows, ids, 1)
+        P = self._flat_operand("start", start)
+        clip = finite_number("clip", clip, positive=True)
+        z = finite_number("noise_multiplier", noise_multiplier)
+        if z < 0:
+            raise ValueError(f"noise_multiplier must be >= 0, not {noise_multiplier!r}")
+        d2 = self.sqdist_to([r for _, r in active], start).cpu().tolist()
+        kept, scales, coeffs = clip_scales(d2, clip)  # ValueError when nothing is kept
+        sigma = _native.fl32(z * clip / len(kept))
+        if not math.isfinite(sigma):
+            raise ValueError(f"dp_mean: sigma = noise_multiplier * clip / {len(kept)} = {sigma} "
+                             "is not finite in fp32")
+        flat = self._vector(P, out)
+        flat.copy_(start)
+        _native.dp_clip_noise_step(self.U, _i32([active[k][1] for k in kept], self.device),
+                                   _f32(coeffs, self.device), P, flat, sigma, seed, stream_id)
+        info = {"norms": {active[k][0]: math.sqrt(d2[k]) for k in kept},
+                "scales": {active[k][0]: s for k, s in zip(kept, scales)},
+                "rejected": sorted(active[k][0] for k in range(len(active)) if k not in kept),
+                "sigma": sigma,
+                "clipped_fraction": sum(1 for s in scales if s < 1.0) / len(kept)}
         return flat, info
 
     def gram(self, rows, base=None, cols=None):

@@ -99,6 +99,8 @@ class _ShardedMixin:
                            "not every honest update the attackers craft from")
     _server_opt_unsupported = ("the optimizer state would have to be kept identical on every "
                                "rank of the sharded servers")
+    _dp_unsupported = ("a rank of the sharded servers holds only its own clients' rows, and the "
+                       "noise must be drawn once for the sum over ranks")
 
     def _init_shard(self, worker_number, group, chunks):
         # before FedServer.__init__, which publishes the initial broadcast to

@@ -56,6 +56,7 @@ class FedQuantServer(FedServer):
     _attack_unsupported = "its store holds the clients' int payloads, not fp32 rows to rewrite"
     _server_opt_unsupported = ("its round model is re-quantized before it is broadcast, so the "
                                "clients never start from the stepped model")
+    _dp_unsupported = "its store holds the clients' int payloads, not fp32 rows to clip"
 
     def __init__(self, quantization_level=256, stochastic=False, seed=0, granularity="model",
                  **kwargs):

@@ -12,7 +12,7 @@ import torch
 
 from .. import _native
 from ..aggregation import (ATTACKS, ClientParameters, ClientUpdateStore, attack_coefficients,
-                           finite_number)
+                           dp_epsilon, finite_number)
 from ..layout import ParameterLayout
 from ..model_util import ModelUtil
 from ..task_queue import RepeatedResult
@@ -45,10 +45,15 @@ OPTIONS = {
     "server_momentum": _Option(None, (float, "in [0, 1)"), "server_opt", SERVER_OPTIMIZERS),
     "server_beta2": _Option(0.99, (float, "in [0, 1)"), "server_opt", ("adam", "yogi")),
     "server_tau": _Option(1e-3, (float, "positive"), "server_opt", ("adagrad", "adam", "yogi")),
+    # differentially private FedAvg: on when dp_clip is set, which the others need
+    "dp_clip": _Option(None, (float, "positive"), "dp", ("dp_clip",)),
+    "dp_noise_multiplier": _Option(1.0, (float, "non-negative"), "dp", ("dp_clip",)),
+    "dp_seed": _Option(0, (int, 0), "dp", ("dp_clip",)),
+    "dp_delta": _Option(1e-5, (float, "in (0, 1)"), "dp", ("dp_clip",)),
 }
-DEFAULTS, ATTACK_DEFAULTS, SERVER_OPT_DEFAULTS = (
+DEFAULTS, ATTACK_DEFAULTS, SERVER_OPT_DEFAULTS, DP_DEFAULTS = (
     {name: o.default for name, o in OPTIONS.items() if o.feature == feature}
-    for feature in ("rule", "attack", "server_opt"))
+    for feature in ("rule", "attack", "server_opt", "dp"))
 # Every robust rule needs 2*trim < K (trim is 0 under all but the trimmed mean).
 _TRIM_FITS = (lambda K, p: 2 * p["trim"] < K,
               "trim={trim} leaves nothing of {clients} (2*trim < {n} is needed)")
@@ -206,6 +211,36 @@ class FedServer(Server):
     pseudo-gradient and applied update, ``reset_server_optimizer()`` starts the state
     over.
 
+    ``dp_clip`` turns the round into client-level differentially private FedAvg (McMahan,
+    Ramage, Talwar & Zhang 2018; None, the default: off).  Every client's update, taken
+    from the previous global model, is clipped to the Euclidean norm ``dp_clip`` (in the
+    units of the parameters), the clipped updates are averaged, every client counting once
+    (the sample counts are ignored, as the robust rules ignore them), and Gaussian noise of
+    standard deviation ``dp_noise_multiplier`` * ``dp_clip`` / K is added to every
+    coordinate: one distance pass and one fused launch that reads the rows once
+    (dls_dp_clip_noise_step_f32, ``ClientUpdateStore.dp_mean``).  The noise is the
+    library's Philox4x32-10 stream under the key ``dp_seed`` (an integer in 0..2^64 - 1)
+    with the round number as the stream id, so a run is reproducible bit for bit and no two
+    rounds share noise; its normals are truncated at sqrt(48 ln 2) ~ 5.768 standard
+    deviations (probability 8e-9 per coordinate), and a ``dp_seed`` that is published is no
+    secret: a deployment draws it from the operating system.  It needs
+    ``aggregation_rule="mean"`` and ``aggregation_mode="exact"`` and at most
+    ``_native.ROBUST_MAX_K`` clients, and a previous global model to clip against: a round
+    without one (round 1 of a server without a tester) raises ``ValueError``.  A client with
+    a non-finite update is rejected and K counts the others.  ``dp_noise_multiplier`` (z,
+    default 1.0; 0 clips without noise and guarantees nothing) and ``dp_delta`` (default
+    1e-5) set the guarantee: after T rounds the released models are (epsilon, dp_delta)-DP
+    with epsilon = ``aggregation.dp_epsilon(z, T, dp_delta)`` under the adjacency "one
+    client's clipped update replaced by zero, K fixed, every client in every round".  A
+    ``dp_*`` option without ``dp_clip`` raises.  A ``server_optimizer``, if set, steps on the
+    noised aggregate: post-processing, which keeps the guarantee.  ``last_dp`` holds the
+    latest round's ``norms`` (each client's update norm), ``scales`` (1.0: not clipped),
+    ``rejected``, ``sigma``, ``clipped_fraction``, ``releases`` and ``epsilon``.
+    ``get_subset_model`` of such a server returns the clipped mean of the subset WITHOUT
+    noise (the same entry point with sigma = 0): an analysis hook for Shapley-style callers,
+    reproducible for any call order, and not a release: its result is not private and is
+    not counted in ``epsilon``.
+
     The robust rules ignore the clients' sample counts n_i (every client counts
     once), take at most ``_native.ROBUST_MAX_K`` clients and are bit-identical for
     any arrival order.  Hooks, ``prev_model``, ``get_metric`` and the round protocol
@@ -215,6 +250,7 @@ class FedServer(Server):
     _robust_unsupported = None  # the robust rules
     _attack_unsupported = None  # the Byzantine client attacks
     _server_opt_unsupported = None  # a server optimizer
+    _dp_unsupported = None  # differentially private FedAvg
 
     def __init__(self, aggregation_mode="exact", aggregation_rule="mean",
                  trim=DEFAULTS["trim"], byzantine=DEFAULTS["byzantine"],
@@ -226,7 +262,9 @@ class FedServer(Server):
                  server_optimizer=None, server_lr=SERVER_OPT_DEFAULTS["server_lr"],
                  server_momentum=SERVER_OPT_DEFAULTS["server_momentum"],
                  server_beta2=SERVER_OPT_DEFAULTS["server_beta2"],
-                 server_tau=SERVER_OPT_DEFAULTS["server_tau"], **kwargs):
+                 server_tau=SERVER_OPT_DEFAULTS["server_tau"], dp_clip=DP_DEFAULTS["dp_clip"],
+                 dp_noise_multiplier=DP_DEFAULTS["dp_noise_multiplier"],
+                 dp_seed=DP_DEFAULTS["dp_seed"], dp_delta=DP_DEFAULTS["dp_delta"], **kwargs):
         # the options by name (the first statement: only the arguments are bound yet)
         given = {name: v for name, v in locals().items() if name in OPTIONS}
         if aggregation_mode not in _MODES:
@@ -238,9 +276,16 @@ class FedServer(Server):
                                        **{name: given[name] for name in ATTACK_DEFAULTS})
         server_opt = self._check_server_opt(
             server_optimizer, **{name: given[name] for name in SERVER_OPT_DEFAULTS})
+        self._check_dp(aggregation_rule, aggregation_mode, workers,
+                       **{name: given[name] for name in DP_DEFAULTS})
         super().__init__(**kwargs)
         _native.require_gpu()
         self.round = 0
+        self.dp_clip = None if dp_clip is None else float(dp_clip)
+        self.dp_noise_multiplier = float(dp_noise_multiplier)
+        self.dp_seed, self.dp_delta = dp_seed, float(dp_delta)
+        self.last_dp = {}
+        self._dp_releases = 0  # the rounds released so far: what epsilon is composed over
         self.server_optimizer = server_optimizer
         # the resolved lr, momentum, beta2, tau, and the fp32 values the kernel is handed
         self.server_lr, self.server_momentum, self.server_beta2, self.server_tau = \
@@ -278,7 +323,9 @@ class FedServer(Server):
                 continue
             if held is float:
                 finite_number(name, v, positive=which == "positive")
-                if which == "in [0, 1)" and not 0.0 <= v < 1.0:
+                if (which == "in [0, 1)" and not 0.0 <= v < 1.0) \
+                        or (which == "in (0, 1)" and not 0.0 < v < 1.0) \
+                        or (which == "non-negative" and v < 0.0):
                     raise ValueError(f"{name} must be {which}, not {v!r}")
             elif isinstance(v, bool) or not isinstance(v, int) or (which is not None and v < which):
                 what = ("an integer or None" if which is None
@@ -414,6 +461,32 @@ class FedServer(Server):
                              "when rounded to fp32")
         return lr, beta1, float(server_beta2), float(server_tau)
 
+    @classmethod
+    def _check_dp(cls, rule, mode, worker_number, dp_clip=DP_DEFAULTS["dp_clip"],
+                  dp_noise_multiplier=DP_DEFAULTS["dp_noise_multiplier"],
+                  dp_seed=DP_DEFAULTS["dp_seed"], dp_delta=DP_DEFAULTS["dp_delta"]):
+        """ValueError for differential-privacy options that no round could run."""
+        p = {"dp_clip": dp_clip, "dp_noise_multiplier": dp_noise_multiplier, "dp_seed": dp_seed,
+             "dp_delta": dp_delta}
+        cls._check_kinds(p)
+        if dp_seed >= 1 << 64:
+            raise ValueError(f"dp_seed must be an integer in 0..2^64 - 1, not {dp_seed!r}")
+        if dp_clip is None:
+            for name, v in p.items():
+                if v != DP_DEFAULTS[name]:
+                    raise ValueError(f"{name}={v} needs dp_clip set, the clipping norm of "
+                                     "differentially private FedAvg, not None")
+            return
+        cls._check_runs(f"dp_clip={dp_clip}", cls._dp_unsupported,
+                        "is the server that runs differentially private FedAvg")
+        if rule != "mean" or mode != "exact":
+            raise ValueError(f"dp_clip={dp_clip} needs aggregation_rule='mean' and "
+                             "aggregation_mode='exact' (DP-FedAvg is the clipped mean plus noise, "
+                             f"with one arithmetic), not {rule!r} and {mode!r}")
+        if worker_number is not None and worker_number > _native.ROBUST_MAX_K:
+            raise ValueError(f"dp_clip={dp_clip} takes at most ROBUST_MAX_K={_native.ROBUST_MAX_K} "
+                             f"clients, not worker_number={worker_number}")
+
     def _initial_model(self):
         """The model the first round starts from: the tester's; none without a tester."""
         return copy.deepcopy(
@@ -479,6 +552,8 @@ class FedServer(Server):
 
     def _subset_flat(self, store, ids):
         """The aggregate of the clients ``ids`` under the server's rule, as a flat vector."""
+        if self.dp_clip is not None:
+            return self._dp_flat(store, ids, release=False)
         # the rules that report, break ties and order by worker id are handed the ids (no
         # subclass that overrides _aggregate runs those rules)
         extra = {"ids": ids} if RULES[self.aggregation_rule]["ids"] else {}
@@ -552,6 +627,39 @@ class FedServer(Server):
                  len(info["distances"]), len(rows),
                  sum(1 for s in info["scales"].values() if s < 1.0), self.cc_tau,
                  list(self.last_rejected), info["moved"])
+        return flat
+
+    def _dp_flat(self, store, ids, release):
+        """DP-FedAvg over the clients ``ids`` from the previous global model
+        (``store.dp_mean``).  ``release``: the round's aggregate, with the noise of stream
+        ``self.round``, booked in ``last_dp``; otherwise the clipped mean without noise (sigma
+        = 0 through the same entry point), which books nothing."""
+        start = self._prev_flat(store)
+        if start is None:
+            raise ValueError(f"dp_clip={self.dp_clip}: no previous global model in round "
+                             f"{self.round}: an update cannot be clipped without the model it "
+                             "started from (a server with a tester starts from the tester's)")
+        if len(ids) > _native.ROBUST_MAX_K:
+            raise ValueError(f"dp_clip={self.dp_clip} takes at most ROBUST_MAX_K="
+                             f"{_native.ROBUST_MAX_K} clients, not {len(ids)}")
+        flat, info = store.dp_mean([self.parameters.row_of(i) for i in ids], ids, start,
+                                   self.dp_clip, self.dp_noise_multiplier if release else 0.0,
+                                   self.dp_seed, self.round)
+        if not release:
+            return flat
+        # the padding between the tensors drew noise like any coordinate: back to zero
+        ends = [o + n for o, n in zip(store.layout.offsets, store.layout.numels)]
+        for a, b in zip(ends, store.layout.offsets[1:] + [store.layout.P]):
+            flat[a:b] = 0.0
+        self._dp_releases += 1
+        self.last_dp = dict(info, round=self.round, releases=self._dp_releases,
+                            epsilon=dp_epsilon(self.dp_noise_multiplier, self._dp_releases,
+                                               self.dp_delta), delta=self.dp_delta)
+        log.info("dp: round %s, %s of %s clients, %s clipped to %s, rejected workers %s, sigma %s, "
+                 "(epsilon %s, delta %s) over %s releases", self.round, len(info["norms"]),
+                 len(ids), sum(1 for s in info["scales"].values() if s < 1.0), self.dp_clip,
+                 info["rejected"], info["sigma"], self.last_dp["epsilon"], self.dp_delta,
+                 self._dp_releases)
         return flat
 
     def _fold_round(self):
@@ -698,12 +806,16 @@ class FedServer(Server):
         if self.aggregation_rule == "foolsgold":
             self._fold_round()
         log.info("begin aggregating")
-        if self.server_optimizer is None:
+        if self.server_optimizer is None and self.dp_clip is None:
             avg_parameter = self.get_subset_model(self.parameters.keys())
         else:
             store = self.parameters.store
-            avg_parameter = store.layout.views(self._server_opt_round(
-                store, self._subset_flat(store, list(self.parameters.keys()))))
+            ids = list(self.parameters.keys())
+            flat = self._subset_flat(store, ids) if self.dp_clip is None \
+                else self._dp_flat(store, ids, release=True)
+            if self.server_optimizer is not None:  # on the noised aggregate: post-processing
+                flat = self._server_opt_round(store, flat)
+            avg_parameter = store.layout.views(flat)
         data = self._process_aggregated_parameter(avg_parameter)
         self.__prev_model = copy.deepcopy(data)
         acc = self.get_metric(self.prev_model)

@@ -30,12 +30,13 @@ class FedTopKServer(FedServer):
 
     ``payload_counts`` holds, per round, the number of entries each worker sent.
 
-    ``aggregation_rule`` other than "mean", ``attack`` and ``server_optimizer`` raise
+    ``aggregation_rule`` other than "mean", ``attack``, ``server_optimizer`` and ``dp_clip`` raise
     ``ValueError``: composing sparsification with them is out of scope here."""
 
     _robust_unsupported = "it holds the clients' sparse updates, not fp32 rows"
     _attack_unsupported = "it holds the clients' sparse updates, not fp32 rows"
     _server_opt_unsupported = "it holds the clients' sparse updates, not fp32 rows"
+    _dp_unsupported = "it holds the clients' sparse updates, not fp32 rows"
 
     def __init__(self, initial_model=None, **kwargs):
         if kwargs.get("tester") is None and not initial_model:

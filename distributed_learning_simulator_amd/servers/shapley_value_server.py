@@ -39,6 +39,8 @@ class ShapleyValueServer(FedServer):
     _robust_unsupported = "coalition models come from the batched subset-mean kernels"
     _server_opt_unsupported = ("its round hook picks or records the round model among the "
                                "coalitions' plain means")
+    _dp_unsupported = ("every coalition model it scores would be a release of its own, which "
+                       "the accountant does not cover")
 
     def __init__(self, subset_method="exact", subset_batch=None, eval_streams=1,
                  utility_metric="acc", **kwargs):

@@ -16,6 +16,7 @@
         [--attack alie --attackers 3,7 [--attack_z 1.0] |
          --attack ipm --attackers 3,7 [--attack_eps 0.1] |
          --attack sign_flip --attackers 3,7 [--attack_scale 1.0]]
+        [--dp_clip 1.0 [--dp_noise_multiplier 1.0] [--dp_seed 0] [--dp_delta 1e-5]]
     python -m distributed_learning_simulator_amd.simulator --distributed_algorithm fed_topk \\
         --worker_number 10 --round 5 [--topk_ratio 0.01] [--topk_error_feedback 1]
 
@@ -37,8 +38,8 @@ import torch
 from .aggregation import ATTACKS
 from .factory import get_server, get_worker
 from .models import MODELS, synthetic_classification
-from .servers.fed_server import (ATTACK_DEFAULTS, DEFAULTS, RULES, SERVER_OPT_DEFAULTS,
-                                 SERVER_OPTIMIZERS)
+from .servers.fed_server import (ATTACK_DEFAULTS, DEFAULTS, DP_DEFAULTS, RULES,
+                                 SERVER_OPT_DEFAULTS, SERVER_OPTIMIZERS)
 from .trainer import Inferencer, Trainer
 
 TOPK_DEFAULTS = {"topk_ratio": 0.01, "topk_error_feedback": 1}
@@ -119,6 +120,15 @@ def get_config(argv=None):
     ap.add_argument("--server_optimizer", type=str, default=None, choices=SERVER_OPTIMIZERS)
     for name in SERVER_OPT_DEFAULTS:
         ap.add_argument("--" + name, type=float, default=None)
+    # client-level differentially private FedAvg on the fed server: every client's update is
+    # clipped to the norm --dp_clip, the clipped updates are averaged and Gaussian noise of
+    # standard deviation --dp_noise_multiplier x --dp_clip / workers is added (default
+    # multiplier 1.0), drawn from the library's Philox stream under --dp_seed (default 0);
+    # --dp_delta (default 1e-5) is the delta of the reported (epsilon, delta)
+    ap.add_argument("--dp_clip", type=float, default=None)
+    ap.add_argument("--dp_noise_multiplier", type=float, default=None)
+    ap.add_argument("--dp_seed", type=int, default=None)
+    ap.add_argument("--dp_delta", type=float, default=None)
     # fed_topk: every worker sends the ceil(--topk_ratio x parameters) largest-magnitude
     # coordinates of its update and keeps the rest in a residual that is added back next
     # round (--topk_error_feedback 0: the residual is dropped, plain top-k)
@@ -133,6 +143,10 @@ def get_config(argv=None):
         config.topk_ratio = TOPK_DEFAULTS["topk_ratio"]
     if config.topk_error_feedback is None:
         config.topk_error_feedback = TOPK_DEFAULTS["topk_error_feedback"]
+    if config.distributed_algorithm != "fed" and any(
+            getattr(config, name) is not None for name in DP_DEFAULTS):
+        ap.error("--dp_clip and its parameters apply to --distributed_algorithm fed alone, the "
+                 "server that holds fp32 client rows and releases one model per round")
     if config.distributed_algorithm == "sign_SGD" and any(
             getattr(config, name) is not None
             for name in ("server_optimizer",) + tuple(SERVER_OPT_DEFAULTS)):
@@ -165,7 +179,7 @@ def server_kwargs(config):
     those rules alone, and
     the attack with its attackers and parameters when --attack is given (the server
     rejects a parameter that belongs to another attack), and --server_optimizer and
-    each of its parameters that was given."""
+    each of its parameters that was given, and likewise --dp_clip and each of its."""
     if config.distributed_algorithm == "sign_SGD":
         return {}
     kwargs = {"aggregation_mode": config.aggregation_mode}
@@ -180,8 +194,8 @@ def server_kwargs(config):
         kwargs["attackers"] = tuple(getattr(config, "attackers", ()))
         for name, default in ATTACK_DEFAULTS.items():
             kwargs[name] = getattr(config, name, default)
-    for name in ("server_optimizer",) + tuple(SERVER_OPT_DEFAULTS):  # only the ones given
-        if getattr(config, name, None) is not None:
+    for name in ("server_optimizer",) + tuple(SERVER_OPT_DEFAULTS) + tuple(DP_DEFAULTS):
+        if getattr(config, name, None) is not None:  # only the ones given
             kwargs[name] = getattr(config, name)
     return kwargs
 

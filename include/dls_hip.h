@@ -852,6 +852,77 @@ int dls_sparse_fedavg_f32(const float *base, const int32_t *idx, const float *va
                           const int64_t *off, const float *weight, int32_t K, float total,
                           int64_t P, float *out, dls_stream_t stream);
 
+/* The library's random stream and the DP-FedAvg step on it (csrc/dpnoise.hip).
+ *
+ * The stream is counter-based Philox4x32-10 (Salmon, Moraes, Dror & Shaw 2011):
+ * multipliers 0xD2511F53 (on counter word 0) and 0xCD9E8D57 (on word 2), Weyl key
+ * increments 0x9E3779B9 and 0xBB67AE85, ten rounds, the key bumped between rounds (the
+ * Random123 known-answer vectors).  key = (seed & 0xffffffff, seed >> 32); counter =
+ * (block & 0xffffffff, block >> 32, stream_id & 0xffffffff, stream_id >> 32) with
+ * block = coordinate / 4; word coordinate % 4 of the block's output belongs to the
+ * coordinate.  A value is a function of (seed, stream_id, coordinate) alone: never of
+ * the launch shape, the CU count, the HIP stream, K, the vector width or the call it
+ * is drawn in.  Two calls that share (seed, stream_id) draw the SAME values for the
+ * same coordinates: callers give every use a stream_id of its own (FedServer: the
+ * round number).
+ *   uniform of a word w:  u = ((w >> 9) + 0.5) * 2^-23, exact in fp32, in
+ *                         [2^-24, 1 - 2^-24]: never 0 and never 1
+ *   normals (Box-Muller): words 0, 1 of a block give coordinates 4b, 4b+1 and words
+ *                         2, 3 give 4b+2, 4b+3.  Of a word pair (a, b):
+ *                           r = sqrtf(fl(-2 * logf(u_a)))
+ *                           g_even = fl(r * cospif(fl(2 * u_b)))
+ *                           g_odd  = fl(r * sinpif(fl(2 * u_b)))
+ *                         2 * u_b and -2 * logf are exact, the square root is correctly
+ *                         rounded, every operation is rounded once and none is fused
+ *                         (-ffp-contract=off); logf, cospif and sinpif are the device
+ *                         math library's, so the normals are defined up to its error:
+ *                         |g - exact| <= (e_log / 2 + e_trig + 1.5) * 2^-23 * r with
+ *                         e_log and e_trig the functions' errors in ulp (DESIGN.md has
+ *                         the measured values).
+ * The tail is truncated: u_a >= 2^-24 gives |g| <= sqrt(48 ln 2) ~ 5.768, which the
+ * standard normal exceeds with probability 8e-9.
+ *
+ *   dls_philox_u32:          out[i] = the word of coordinate first + i, i < n; exact.
+ *   dls_philox_normal_f32:   out[i] = the normal of coordinate first + i.
+ *   dls_normal_from_bits_f32: out[2j], out[2j+1] = (g_even, g_odd) of the word pair
+ *                            (bits[2j], bits[2j+1]), j < n / 2: the transform alone, on
+ *                            words the caller chooses.  out may be bits itself.
+ * out and bits are device arrays of n 4-byte elements, 4-byte aligned (DLS_ELAYOUT
+ * otherwise); first >= 0, n >= 0, first + n <= 2^63 - 1, n even for
+ * dls_normal_from_bits_f32, no null pointer (DLS_EINVAL otherwise).  Every check runs
+ * before any device call; n == 0 launches nothing.  The bits of
+ * dls_philox_normal_f32 are those of dls_normal_from_bits_f32 on the words of
+ * dls_philox_u32 for any first and n (an odd first or n included: the pairing is by
+ * coordinate, not by position in out).
+ *
+ * dls_dp_clip_noise_step_f32: one step of client-level DP-FedAvg (McMahan, Ramage,
+ * Talwar & Zhang 2018): the clipped mean of dls_centered_clip_step_f32 and Gaussian
+ * noise, in one read of the rows.  Operands, layout rules (P and ldu multiples of 4,
+ * ldu >= P, U and z 16-byte aligned, c 4-byte aligned: DLS_ELAYOUT), the range of K
+ * and the order of the checks are those of dls_centered_clip_step_f32; there is no
+ * dist2 and no workspace.  sigma must be finite and >= 0 (DLS_EINVAL; checked after K,
+ * before the layout).  Per coordinate p, in the order of `rows`, every operation
+ * rounded once and never fused:
+ *   d_k = fl32(U[rows[k]][p] - z[p]);  t_k = fl32(c[k] * d_k);  acc = t_0;
+ *   acc = fl32(acc + t_k) for k = 1 .. K-1;  y = fl32(z[p] + acc)
+ * (the bits of the clip step), then
+ *   z'[p] = fl32(y + fl32(sigma * g_p)),  g_p the normal of coordinate p.
+ * sigma == 0 draws nothing and stores y itself: z' then equals the clip step's bit
+ * for bit, the sign of a zero included.  Given dls_philox_normal_f32's g, numpy float32
+ * reproduces z' bit for bit wherever it is not NaN.  z' does not depend on ldu, on the
+ * rows' position in U, on the HIP stream or on the CU count.  A row that holds an inf
+ * or NaN poisons its coordinate even with c[k] = 0.  A failed check leaves z untouched;
+ * P == 0 launches nothing.  Traffic: K rows and z read once, z written once:
+ * (K + 2) * P * 4 bytes. */
+int dls_philox_u32(uint32_t *out, int64_t n, uint64_t seed, uint64_t stream_id, int64_t first,
+                   dls_stream_t stream);
+int dls_philox_normal_f32(float *out, int64_t n, uint64_t seed, uint64_t stream_id,
+                          int64_t first, dls_stream_t stream);
+int dls_normal_from_bits_f32(const uint32_t *bits, int64_t n, float *out, dls_stream_t stream);
+int dls_dp_clip_noise_step_f32(const float *U, int64_t ldu, const int32_t *rows, int32_t K,
+                               const float *c, int64_t P, float *z, float sigma, uint64_t seed,
+                               uint64_t stream_id, dls_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
