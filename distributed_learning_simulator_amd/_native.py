@@ -22,6 +22,7 @@ SIGN_NAN_MARK = 1 << 24
 QTILE_GROUPS = 10  # DLS_QTILE_GROUPS
 SUBSET_UNION_MAX = 64  # DLS_SUBSET_UNION_MAX: coalitions per dls_subset_fedavg_union_f32 call
 ROBUST_MAX_K = 64  # DLS_ROBUST_MAX_K: client rows per dls_trimmed_mean_f32 call
+SECAGG_MAX_STREAMS = 1088  # DLS_SECAGG_MAX_STREAMS: masks added and removed per secagg call
 
 
 def sign_words(P):
@@ -53,6 +54,7 @@ class QTile(ctypes.Structure):
 
 _i32, _i64, _f32, _p, _u64 = (ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p,
                               ctypes.c_uint64)
+_u32, _f64 = ctypes.c_uint32, ctypes.c_double
 
 # name -> argtypes (restype int unless noted); mirrors include/dls_hip.h
 SIGNATURES = {
@@ -87,6 +89,10 @@ SIGNATURES = {
     "dls_normal_from_bits_f32": ([_p, _i64, _p, _p], _i32),
     "dls_dp_clip_noise_step_f32": ([_p, _i64, _p, _i32, _p, _i64, _p, _f32, _u64, _u64, _p],
                                    _i32),
+    "dls_secagg_mask_f32": ([_p, _p, _i64, _i32, _i32, _u32, _p, _i32, _p, _i32, _u64, _p, _p, _p],
+                            _i32),
+    "dls_secagg_unmask_f32": ([_p, _i64, _p, _i32, _p, _i32, _p, _i32, _u64, _p, _i32, _f64, _i64,
+                               _p, _p, _p], _i32),
     "dls_subset_gemm_f32": ([_p, _i32, _i32, _p, _i64, _p, _i64, _p, _i64, _p], _i32),
     "dls_sign_pack_f32": ([_p, _i64, _i32, _i64, _p, _i64, _p, _p], _i32),
     "dls_sign_vote_count": ([_p, _i64, _p, _i32, _i64, _p, _p], _i32),
@@ -191,6 +197,7 @@ CSRC_HASHED = [  # the Makefile's HASHED, in its order
     "weiszfeld.hip",
     "gram.hip",
     "serveropt.hip",
+    "secagg.hip",
     "topk.hip",
     "dpnoise.hip",
     "dls_common.h",
@@ -198,6 +205,7 @@ CSRC_HASHED = [  # the Makefile's HASHED, in its order
     "loss_common.h",
     "sign_geometry.h",
     "rows_common.h",
+    "philox_common.h",
     os.path.join("..", "..", "include", "dls_hip.h"),
 ]
 
@@ -323,18 +331,19 @@ def _row_pitch(t):
     return t.stride(0) if t.shape[0] > 1 else t.shape[1]
 
 
-def _rows_operands(fn, U, rows, P, names=("U", "rows")):
+def _rows_operands(fn, U, rows, P, names=("U", "rows"), dtype=torch.float32):
     """The checks every rows-family wrapper makes on a matrix, a row table and P
-    (``names``: what the messages call the two tensors): returns (K, P, ldu)."""
-    return (_rows_table(fn, U, rows, names),) + _rows_extent(fn, U, P)
+    (``names``: what the messages call the two tensors; ``dtype``: the matrix's): returns
+    (K, P, ldu)."""
+    return (_rows_table(fn, U, rows, names, dtype),) + _rows_extent(fn, U, P)
 
 
-def _rows_table(fn, U, rows, names=("U", "rows")):
+def _rows_table(fn, U, rows, names=("U", "rows"), dtype=torch.float32):
     """The first half of ``_rows_operands``, the two tensors: returns K."""
-    if (not torch.is_tensor(U) or U.dtype != torch.float32 or U.dim() != 2
+    if (not torch.is_tensor(U) or U.dtype != dtype or U.dim() != 2
             or (U.shape[1] > 1 and U.stride(1) != 1)):
-        raise RuntimeError(f"{fn}: {names[0]} must be an fp32 [rows, ld] matrix with unit "
-                           "element stride")
+        raise RuntimeError(f"{fn}: {names[0]} must be an {_DTYPE_NAMES[dtype]} [rows, ld] matrix "
+                           "with unit element stride")
     # 1-D with unit stride and any length (K is checked below) is "contiguous 1-D"
     _check_tensor(fn, names[1], rows, torch.int32, 0, "a contiguous int32 [K] tensor",
                   exact=False, contiguous=False)
@@ -674,6 +683,105 @@ def dp_clip_noise_step(U, rows, c, P, z, sigma, seed, stream_id, stream=None):
                                                 fl32(sigma), seed, stream_id, _stream(stream, U)),
                "dls_dp_clip_noise_step_f32")
     return z
+
+
+# ------------------------------------------------------------------ secure aggregation
+def _int_in(fn, name, v, lo, hi, hi_text=None):
+    """int(v); RuntimeError unless v is an integer in lo..hi."""
+    if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+        raise RuntimeError(f"{fn}: {name}={v!r} must be an integer in {lo}..{hi_text or hi}")
+    return v
+
+
+def _stream_table(fn, name, t):
+    """A table of stream ids: an int64 vector with unit stride that holds the uint64 ids' bit
+    patterns (torch has no arithmetic on uint64), or None for none: returns (t, count)."""
+    if t is None:
+        return None, 0
+    _check_tensor(fn, name, t, torch.int64, 0, "an int64 vector with unit stride (the uint64 "
+                  "stream ids' bit patterns), or None", exact=False, contiguous=False)
+    return (t, t.numel()) if t.numel() else (None, 0)
+
+
+def _secagg_streams(fn, add_streams, sub_streams):
+    add, n_add = _stream_table(fn, "add_streams", add_streams)
+    sub, n_sub = _stream_table(fn, "sub_streams", sub_streams)
+    if n_add + n_sub > SECAGG_MAX_STREAMS:
+        raise RuntimeError(f"{fn}: {n_add} + {n_sub} streams (at most SECAGG_MAX_STREAMS="
+                           f"{SECAGG_MAX_STREAMS})")
+    return add, n_add, sub, n_sub
+
+
+def _secagg_extent(fn, P):
+    P = int(P)
+    if P < 0 or P % 4 != 0:
+        raise RuntimeError(f"{fn}: P={P} must be a non-negative multiple of 4")
+    return P
+
+
+def secagg_mask(w, base, P, frac_bits, bits, weight, add_streams, sub_streams, seed, y, stats,
+                stream=None):
+    """The client's fused encode + mask (dls_secagg_mask_f32): y[:P] = q * weight + the mask
+    words of ``add_streams`` - those of ``sub_streams``, mod 2^32, with q = clamp(rintf(fl32(
+    fl32(w - base) * 2^frac_bits)), -L, L), L = 2^(bits-1) - 1, and q = 0 where w - base is
+    not finite; stats[0] += the saturated coordinates, stats[1] += the non-finite ones
+    (added to: zero it first).  w, base: fp32 vectors of at least P elements; y: an int32
+    vector of at least P (the uint32 bit patterns, as in ``philox_u32``); stats: int32 [2];
+    the stream tables: int64 vectors (uint64 bit patterns) or None.  Exact.  Returns y."""
+    fn = "secagg_mask"
+    P = _secagg_extent(fn, P)
+    _f32_vector(fn, "w", w, P)
+    _f32_vector(fn, "base", base, P)
+    _unit_vector(fn, "y", y, torch.int32, P, count=("P", P))
+    _unit_vector(fn, "stats", stats, torch.int32, 2, exact=True)
+    frac_bits = _int_in(fn, "frac_bits", frac_bits, 0, 126)
+    bits = _int_in(fn, "bits", bits, 2, 31)
+    weight = _int_in(fn, "weight", weight, 1, (1 << 32) - 1, "2^32 - 1")
+    add, n_add, sub, n_sub = _secagg_streams(fn, add_streams, sub_streams)
+    seed = _uint64(fn, "seed", seed)
+    _check_same_device(fn, w, _anchor="w", base=base, y=y, stats=stats, add_streams=add,
+                       sub_streams=sub)
+    _aligned16(fn, w=w, base=base, y=y)
+    _check_disjoint({"y": y[:P], "w": w[:P], "base": base[:P]}, f"{fn}: {{a}} and {{b}} overlap",
+                    allowed=lambda a, b: "y" not in (a, b))
+    _ptr(w), _ptr(base), _ptr(y), _ptr(stats), _ptr(add), _ptr(sub)  # no CPU path
+    if P != 0:
+        _check(lib().dls_secagg_mask_f32(_ptr(w), _ptr(base), P, frac_bits, bits, weight,
+                                         _ptr(add), n_add, _ptr(sub), n_sub, seed, _ptr(y),
+                                         _ptr(stats), _stream(stream, w)), "dls_secagg_mask_f32")
+    return y
+
+
+def secagg_unmask(Y, rows, add_streams, sub_streams, seed, base, frac_bits, total, P, out,
+                  sum_out=None, stream=None):
+    """The server's fused sum + mask recovery + decode (dls_secagg_unmask_f32): S = the sum
+    of the K = rows.numel() selected rows of Y + the mask words of ``add_streams`` - those of
+    ``sub_streams``, mod 2^32; out[:P] = fl32(base + (float)((double)(int32)S * 2^-frac_bits
+    / total)); sum_out[:P] = S if given.  Y: an int32 [rows, ld] matrix (uint32 bit
+    patterns); total: finite, >= 1 (used as fp64); out may be base.  Exact.  Returns out."""
+    fn = "secagg_unmask"
+    K, P, ldy = _rows_operands(fn, Y, rows, P, names=("Y", "rows"), dtype=torch.int32)
+    _f32_vector(fn, "base", base, P)
+    _f32_vector(fn, "out", out, P)
+    if sum_out is not None:
+        _unit_vector(fn, "sum_out", sum_out, torch.int32, P, count=("P", P))
+    frac_bits = _int_in(fn, "frac_bits", frac_bits, 0, 126)
+    if isinstance(total, bool) or not isinstance(total, (int, float)) \
+            or not math.isfinite(total) or total < 1:
+        raise RuntimeError(f"{fn}: total={total!r} must be finite and >= 1")
+    add, n_add, sub, n_sub = _secagg_streams(fn, add_streams, sub_streams)
+    seed = _uint64(fn, "seed", seed)
+    _rows_placement(fn, Y, ("base", "out", "sum_out"), rows=rows, base=base, out=out,
+                    sum_out=sum_out, add_streams=add, sub_streams=sub)
+    outs = {"out": out[:P]} if sum_out is None else {"out": out[:P], "sum_out": sum_out[:P]}
+    _check_disjoint({"Y": Y, **outs}, f"{fn}: {{a}} and {{b}} overlap")
+    _ptr(Y), _ptr(rows), _ptr(base), _ptr(out), _ptr(sum_out), _ptr(add), _ptr(sub)  # no CPU path
+    if P != 0:
+        _check(lib().dls_secagg_unmask_f32(_ptr(Y), ldy, _ptr(rows), K, _ptr(add), n_add,
+                                           _ptr(sub), n_sub, seed, _ptr(base), frac_bits,
+                                           float(total), P, _ptr(out), _ptr(sum_out),
+                                           _stream(stream, Y)), "dls_secagg_unmask_f32")
+    return out
 
 
 # DLS_SERVER_OPT_* (include/dls_hip.h): the kinds, and the launch shape of the step

@@ -250,6 +250,95 @@ def dp_epsilon(noise_multiplier, rounds, delta):
     return rounds / (2.0 * z * z) + math.sqrt(2.0 * rounds * math.log(1.0 / delta)) / z
 
 
+SECAGG_MAX_WORKER_ID = (1 << 16) - 1  # a stream id holds two worker ids of 16 bits
+
+
+def secagg_stream_id(round, a, b):
+    """The Philox stream id of a secure-aggregation mask: (round << 32) | (a << 16) | b for
+    worker ids a <= b <= 65535 and 0 <= round < 2^32.  a < b: the pair mask workers a and b
+    share; a == b: worker a's self mask (Bonawitz et al. 2017, double masking).  No two masks
+    of a run share an id, and none repeats across rounds."""
+    for name, v, top in (("round", round, (1 << 32) - 1), ("a", a, SECAGG_MAX_WORKER_ID),
+                         ("b", b, SECAGG_MAX_WORKER_ID)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= top:
+            raise ValueError(f"secagg_stream_id: {name}={v!r} must be an integer in 0..{top}")
+    if a > b:
+        raise ValueError(f"secagg_stream_id: a={a} must not exceed b={b} (a pair is named by its "
+                         "smaller id first)")
+    return (round << 32) | (a << 16) | b
+
+
+def _secagg_ids(name, ids):
+    """The sorted list of the distinct worker ids ``ids``."""
+    try:
+        ids = list(ids)
+    except TypeError:
+        raise ValueError(f"{name} must be a collection of worker ids, not {ids!r}")
+    if any(isinstance(w, bool) or not isinstance(w, int) or not 0 <= w <= SECAGG_MAX_WORKER_ID
+           for w in ids):
+        raise ValueError(f"{name} must be integer worker ids in 0..{SECAGG_MAX_WORKER_ID}, not "
+                         f"{ids!r}")
+    if len(set(ids)) != len(ids):
+        raise ValueError(f"{name} must be distinct worker ids, not {ids!r}")
+    return sorted(ids)
+
+
+def secagg_client_streams(worker_id, participants, round):
+    """(add, sub): the stream ids whose masks worker ``worker_id`` adds to and subtracts from
+    its encoded update in ``round``, among the round's ``participants`` (which include it).
+    add: its self mask and the pair masks with every participant of a larger id; sub: the pair
+    masks with every participant of a smaller id.  Summed over all participants, every pair
+    mask is added once and subtracted once."""
+    ids = _secagg_ids("participants", participants)
+    if worker_id not in ids:
+        raise ValueError(f"worker {worker_id!r} is not among the participants {ids}")
+    add = [secagg_stream_id(round, worker_id, worker_id)]
+    add += [secagg_stream_id(round, worker_id, j) for j in ids if j > worker_id]
+    sub = [secagg_stream_id(round, j, worker_id) for j in ids if j < worker_id]
+    return add, sub
+
+
+def secagg_server_streams(survivors, dropped, round):
+    """(add, sub): the stream ids whose masks the server adds to and subtracts from the sum of
+    the ``survivors``' payloads, when the workers in ``dropped`` took part in the key agreement
+    of ``round`` and sent nothing that is used.  sub: every survivor's self mask (its shares
+    are reconstructed because it survived) and the pair mask (i, d) of each survivor i and
+    dropped d with i < d, which i added and d never cancelled; add: the pair mask (d, i) for
+    d < i, which i subtracted.  The masks between two survivors cancel in the sum; those
+    between two dropped workers never entered it."""
+    alive, gone = _secagg_ids("survivors", survivors), _secagg_ids("dropped", dropped)
+    both = sorted(set(alive) & set(gone))
+    if both:
+        raise ValueError(f"workers {both} cannot both survive and drop")
+    sub = [secagg_stream_id(round, i, i) for i in alive]
+    sub += [secagg_stream_id(round, i, d) for i in alive for d in gone if i < d]
+    add = [secagg_stream_id(round, d, i) for i in alive for d in gone if d < i]
+    return add, sub
+
+
+def secagg_check_capacity(bits, weights):
+    """The sum of the weights, after checking that a sum of updates quantised to ``bits`` bits
+    (|q| <= L = 2^(bits-1) - 1) under these integer ``weights`` cannot wrap the ring:
+    L * sum(weights) < 2^31.  The ValueError names the largest ``secagg_bits`` that fits."""
+    if isinstance(bits, bool) or not isinstance(bits, int) or not 2 <= bits <= 31:
+        raise ValueError(f"secagg_bits must be an integer in 2..31, not {bits!r}")
+    weights = list(weights)
+    if not weights or any(isinstance(n, bool) or not isinstance(n, int) or not 1 <= n < 1 << 32
+                          for n in weights):
+        raise ValueError(f"the weights must be integers in 1..2^32 - 1, at least one, not "
+                         f"{weights!r}")
+    total = sum(weights)
+    if ((1 << (bits - 1)) - 1) * total >= 1 << 31:
+        fits = max((b for b in range(2, 32) if ((1 << (b - 1)) - 1) * total < 1 << 31),
+                   default=None)
+        raise ValueError(
+            f"secagg_bits={bits} does not fit: (2^{bits - 1} - 1) * {total} (the sum of the "
+            f"weights) reaches 2^31 and the masked sum would wrap; "
+            + (f"the largest secagg_bits that fits is {fits}" if fits is not None
+               else "no secagg_bits fits weights this large"))
+    return total
+
+
 def foolsgold_weights(G, kappa=1.0):
     """The FoolsGold weights (Fung, Yoon & Beschastnikh, RAID 2020) from the [K, K] Gram
     matrix of the clients' accumulated updates, on the host in fp64: (alpha, info).

@@ -448,6 +448,10 @@ def get_sharded_server(algorithm, **kwargs):
         raise RuntimeError("fed_topk runs on the one-process server only (factory.get_server("
                            "'fed_topk', sharded=False, ...)): a sharded server over sparse "
                            "payloads is not implemented")
+    if algorithm == "fed_secagg":
+        raise RuntimeError("fed_secagg runs on the one-process server only (factory.get_server("
+                           "'fed_secagg', sharded=False, ...)): a sharded server over masked "
+                           "payloads is not implemented")
     if algorithm not in table:
         raise RuntimeError("unknown algorithm:" + algorithm)
     return table[algorithm](**kwargs)

@@ -1,5 +1,6 @@
 """Plugin factory (reference: factory.py:14-35) — same algorithm names and errors."""
 from .servers.fed_quant_server import FedQuantServer
+from .servers.fed_secagg_server import FedSecAggServer
 from .servers.fed_server import FedServer
 from .servers.fed_topk_server import FedTopKServer
 from .servers.GTG_shapley_value_server import GTGShapleyValueServer
@@ -7,6 +8,7 @@ from .servers.multiround_shapley_value_server import MultiRoundShapleyValueServe
 from .servers.server import Server
 from .servers.sign_sgd_server import SignSGDServer
 from .workers.fed_quant_worker import FedQuantWorker
+from .workers.fed_secagg_worker import FedSecAggWorker
 from .workers.fed_topk_worker import FedTopKWorker
 from .workers.fed_worker import FedWorker
 from .workers.sign_sgd_worker import SignSGDWorker
@@ -30,6 +32,8 @@ def get_server(algorithm, sharded=None, **kwargs) -> Server:
         return FedServer(**kwargs)
     if algorithm == "fed_topk":
         return FedTopKServer(**kwargs)
+    if algorithm == "fed_secagg":
+        return FedSecAggServer(**kwargs)
     if algorithm == "multiround_shapley_value":
         return MultiRoundShapleyValueServer(**kwargs)
     if algorithm == "GTG_shapley_value":
@@ -44,6 +48,8 @@ def get_worker(algorithm, **kwargs) -> Worker:
         return FedQuantWorker(**kwargs)
     if algorithm == "fed_topk":
         return FedTopKWorker(**kwargs)
+    if algorithm == "fed_secagg":
+        return FedSecAggWorker(**kwargs)
     if algorithm in ("fed", "multiround_shapley_value", "GTG_shapley_value"):
         return FedWorker(**kwargs)
     raise RuntimeError("unknown algorithm:" + algorithm)

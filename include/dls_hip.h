@@ -923,6 +923,58 @@ int dls_dp_clip_noise_step_f32(const float *U, int64_t ldu, const int32_t *rows,
                                const float *c, int64_t P, float *z, float sigma, uint64_t seed,
                                uint64_t stream_id, dls_stream_t stream);
 
+/* Secure aggregation in the ring Z_2^32 on pairwise masks drawn from the stream above
+ * (csrc/secagg.hip; Bonawitz et al. 2017, "Practical Secure Aggregation for
+ * Privacy-Preserving Machine Learning").  The mask word m_t[p] of stream id t and
+ * coordinate p is dls_philox_u32's word under (seed, t, p); every sum below is mod 2^32.
+ * Both calls are exact: numpy reproduces them bit for bit, for any launch shape, HIP
+ * stream, CU count, ldy and position of the rows in Y.
+ *
+ * dls_secagg_mask_f32: the client's fused encode + mask.  With L = 2^(bits-1) - 1, per
+ * coordinate p, every fp32 operation rounded once:
+ *   d = fl32(w[p] - base[p]);  r = rintf(fl32(d * 2^frac_bits)), ties to even
+ *   q = clamp(r, -L, L) as int32; a d that is not finite (inf, NaN) gives q = 0
+ *   y[p] = (uint32)q * weight + sum_{t in add_streams} m_t[p] - sum_{t in sub_streams} m_t[p]
+ *   stats[0] += #{p : d finite and |r| > L} (saturated; an overflowed product counts)
+ *   stats[1] += #{p : d not finite}
+ * stats is ADDED to (int32 [2], device; integer atomics: an order-independent sum), so a
+ * caller zeroes it once and may mask several pieces into it.
+ *
+ * dls_secagg_unmask_f32: the server's fused sum + mask recovery + decode over the K rows
+ * Y[rows[k] * ldy ..] (uint32, rows device int32 [K]):
+ *   S[p] = sum_k Y[rows[k]][p] + sum_{t in add_streams} m_t[p] - sum_{t in sub_streams} m_t[p]
+ *   v = (int32)S[p], two's complement
+ *   delta = (float)(((double)v * 2^-frac_bits) / total): the product is exact, the IEEE
+ *           fp64 division rounds once and the cast to fp32 rounds once (to nearest even)
+ *   out[p] = fl32(base[p] + delta);  sum_out[p] = S[p] when sum_out is not null
+ * Nothing in the decode is fused, reassociated or approximated.  out may be base itself.
+ *
+ * Checks, each before any device call, in this order: no null pointer (sum_out may be
+ * null; the stream tables come below) and, for unmask, 1 <= K <= DLS_ROBUST_MAX_K; for mask
+ * 2 <= bits <= 31 and weight >= 1; 0 <= frac_bits <= 126; n_add, n_sub >= 0 and n_add +
+ * n_sub <= DLS_SECAGG_MAX_STREAMS (64 self masks plus the worst survivor x dropped product,
+ * 32 * 32); a stream table is null only when its count is 0; for unmask total finite and
+ * >= 1 (DLS_EINVAL); then P >= 0 (DLS_EINVAL), P and ldy multiples of 4, ldy >= P, w, base, y,
+ * Y, out and sum_out 16-byte aligned, the stream tables 8-byte and rows / stats 4-byte
+ * aligned (DLS_ELAYOUT).  A failed check leaves the outputs untouched; P == 0 launches
+ * nothing.  The stream tables are device arrays of uint64.  y must not overlap w or base,
+ * out and sum_out must not overlap Y or each other (preconditions).
+ * Launch shape: one launch each; 256-thread blocks, a lane owns four consecutive
+ * coordinates (one Philox block), tile n of 256 coordinates belongs to wave n % nW with
+ * nW <= 2048 a function of P alone; no LDS, no floating-point atomics.  Traffic: mask
+ * 3 * P * 4 bytes and (n_add + n_sub) / 4 Philox blocks per coordinate; unmask (K + 2) * P
+ * * 4 bytes (+ P * 4 with sum_out) and as many blocks. */
+#define DLS_SECAGG_MAX_STREAMS 1088
+int dls_secagg_mask_f32(const float *w, const float *base, int64_t P, int32_t frac_bits,
+                        int32_t bits, uint32_t weight, const uint64_t *add_streams, int32_t n_add,
+                        const uint64_t *sub_streams, int32_t n_sub, uint64_t seed, uint32_t *y,
+                        int32_t *stats, dls_stream_t stream);
+int dls_secagg_unmask_f32(const uint32_t *Y, int64_t ldy, const int32_t *rows, int32_t K,
+                          const uint64_t *add_streams, int32_t n_add, const uint64_t *sub_streams,
+                          int32_t n_sub, uint64_t seed, const float *base, int32_t frac_bits,
+                          double total, int64_t P, float *out, uint32_t *sum_out,
+                          dls_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
