@@ -84,6 +84,10 @@ SIGNATURES = {
     "dls_topk_workspace": ([_i64], _i64),
     "dls_topk_compress_f32": ([_p, _p, _p, _i64, _i64, _p, _p, _p, _p, _p], _i32),
     "dls_sparse_fedavg_f32": ([_p, _p, _p, _p, _p, _i32, _f32, _i64, _p, _p], _i32),
+    "dls_efsign_workspace": ([_i64, _i64], _i64),
+    "dls_efsign_compress_f32": ([_p, _p, _p, _i64, _p, _p, _i32, _p, _p, _p, _p, _p], _i32),
+    "dls_efsign_fedavg_f32": ([_p, _p, _i64, _p, _i64, _p, _p, _i32, _p, _f32, _i32, _i64, _p, _p],
+                              _i32),
     "dls_philox_u32": ([_p, _i64, _u64, _u64, _i64, _p], _i32),
     "dls_philox_normal_f32": ([_p, _i64, _u64, _u64, _i64, _p], _i32),
     "dls_normal_from_bits_f32": ([_p, _i64, _p, _p], _i32),
@@ -198,6 +202,7 @@ CSRC_HASHED = [  # the Makefile's HASHED, in its order
     "gram.hip",
     "serveropt.hip",
     "secagg.hip",
+    "efsign.hip",
     "topk.hip",
     "dpnoise.hip",
     "dls_common.h",
@@ -960,6 +965,150 @@ def sparse_fedavg(base, idx, val, off, weight, total, P, out, stream=None):
                                        _ptr(val) if has else None, _ptr(off), _ptr(weight), K,
                                        total, P, _ptr(out), _stream(stream, base)),
            "dls_sparse_fedavg_f32")
+    return out
+
+
+# ------------------------------------------- scaled-sign compression, error feedback
+# DLS_EFSIGN_* (include/dls_hip.h)
+EFSIGN_CHUNK = 4096  # real elements of one tensor per block of the L1 pass
+EFSIGN_CLIENT_TILE = 64  # clients per tile of dls_efsign_fedavg_f32
+
+
+class EfsignSegments:
+    """The tensors of a flat row as dls_efsign_* take them: ``bounds`` int64 [T + 1] and
+    ``count`` int64 [T] on the device, checked on the host (efsign_segments)."""
+
+    __slots__ = ("bounds", "count", "T", "P")
+
+    def __init__(self, bounds, count, T, P):
+        self.bounds, self.count, self.T, self.P = bounds, count, T, P
+
+
+def efsign_segments(bounds, count, device):
+    """Check the segment arrays on the host (the library cannot: they live on the device)
+    and upload them.  bounds: T + 1 ascending multiples of 64 from 0 to P, 64 <= P < 2^31;
+    count: T integers, 1 <= count[t] <= bounds[t + 1] - bounds[t].  Malformed segments are
+    the library's DLS_EINVAL, raised here."""
+    fn = "efsign_segments"
+    bounds, count = [int(b) for b in bounds], [int(c) for c in count]
+    T = len(count)
+
+    def refuse(what):
+        raise RuntimeError(f"{fn}: {what} (DLS_EINVAL)")
+    if T < 1 or len(bounds) != T + 1:
+        refuse(f"bounds must hold T + 1 = {T + 1} entries for T = {T} >= 1 counts, not "
+               f"{len(bounds)}")
+    if bounds[0] != 0 or not 64 <= bounds[-1] < 1 << 31:
+        refuse(f"bounds must run from 0 to P, 64 <= P < 2^31, not {bounds[0]}..{bounds[-1]}")
+    for t in range(T + 1):
+        if bounds[t] % 64:
+            refuse(f"bounds[{t}]={bounds[t]} is not a multiple of 64")
+    for t in range(T):
+        if not 1 <= count[t] <= bounds[t + 1] - bounds[t]:
+            refuse(f"count[{t}]={count[t]} must lie in 1..bounds[{t + 1}] - bounds[{t}] = "
+                   f"{bounds[t + 1] - bounds[t]}")
+    return EfsignSegments(torch.tensor(bounds, dtype=torch.int64).to(device),
+                          torch.tensor(count, dtype=torch.int64).to(device), T, bounds[-1])
+
+
+def efsign_layout_segments(layout, device):
+    """efsign_segments of a ParameterLayout: one segment per tensor."""
+    return efsign_segments(list(layout.offsets) + [layout.P], [max(n, 1) for n in layout.numels],
+                           device)
+
+
+def _efsign_extent(fn, seg):
+    if not isinstance(seg, EfsignSegments):
+        raise RuntimeError(f"{fn}: seg must come from efsign_segments, not "
+                           f"{type(seg).__name__}")
+    return seg.P, seg.T
+
+
+def efsign_workspace(P, T, device):
+    """The scratch buffer dls_efsign_compress_f32 needs for rows of P elements in T tensors
+    (a uint8 tensor on ``device``; its contents never matter between calls)."""
+    nbytes = int(lib().dls_efsign_workspace(int(P), int(T)))
+    if nbytes < 0:
+        _check(nbytes, "dls_efsign_workspace")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def efsign_compress(w, base, e, seg, bits, scales, stats, workspace, stream=None):
+    """Scaled-sign compression with error feedback (dls_efsign_compress_f32): with u = fl32(
+    fl32(w - base) + e) and s[t] = fl32(sum |u| / count[t]) per tensor, bit j of ``bits``
+    (int64 [P / 64] words) is u[j] < 0, ``scales`` (fp32 [T]) is s, e becomes u - s or u + s
+    by the bit (+0.0 on padding) and stats (int32 [1]) the number of non-finite u.  w, base,
+    e: fp32 vectors of at least P = seg.P elements with unit stride; workspace:
+    ``efsign_workspace(P, T)``.  e must not overlap w or base; every tensor 16-byte
+    aligned.  Nothing is synchronised.  Returns (bits, scales)."""
+    fn = "efsign_compress"
+    P, T = _efsign_extent(fn, seg)
+    for name, t in (("w", w), ("base", base), ("e", e)):
+        _f32_vector(fn, name, t, P)
+    _unit_vector(fn, "bits", bits, torch.int64, P // 64)
+    _unit_vector(fn, "scales", scales, torch.float32, T)
+    _unit_vector(fn, "stats", stats, torch.int32, 1)
+    need = int(lib().dls_efsign_workspace(P, T))
+    _check_tensor(fn, "workspace", workspace, torch.uint8, need, lambda: "a uint8 vector of at "
+                  f"least {need} bytes (efsign_workspace(P, T))", exact=False, contiguous=False)
+    _check_same_device(fn, w, _anchor="w", base=base, e=e, bits=bits, scales=scales, stats=stats,
+                       workspace=workspace, bounds=seg.bounds)
+    for name, other in (("w", w), ("base", base)):
+        if _overlaps(e[:P], other[:P]):
+            raise RuntimeError(f"{fn}: e and {name} overlap (the residual is updated in place)")
+    _check_disjoint({"e": e[:P], "bits": bits[:P // 64], "scales": scales[:T], "stats": stats[:1],
+                     "workspace": workspace}, f"{fn}: {{a}} and {{b}} overlap")
+    for name, t in (("w", w), ("base", base), ("e", e), ("bits", bits), ("scales", scales),
+                    ("stats", stats), ("workspace", workspace)):
+        _aligned16(fn, **{name: t})
+    for t in (w, base, e, bits, scales, stats, workspace, seg.bounds, seg.count):
+        _ptr(t)  # no CPU path
+    _check(lib().dls_efsign_compress_f32(_ptr(w), _ptr(base), _ptr(e), P, _ptr(seg.bounds),
+                                         _ptr(seg.count), T, _ptr(bits), _ptr(scales),
+                                         _ptr(stats), _ptr(workspace), _stream(stream, w)),
+           "dls_efsign_compress_f32")
+    return bits, scales
+
+
+def efsign_fedavg(base, bits, scales, seg, weight, total, out, stream=None):
+    """FedAvg over K clients' bit rows, added to ``base`` (dls_efsign_fedavg_f32): bits int64
+    [K, >= P / 64] and scales fp32 [K, >= T] with unit stride along a row; weight fp32 [K] =
+    the n_i, total = their fp32 sum.  On a real coordinate of tensor t, out = fl32(base +
+    acc), acc the chain of +-fl32(fl32(s[i][t] * n_i) / N) over the clients in row order
+    (the first assigns, the rest add); padding keeps base's bits.  base, out: fp32 vectors
+    of at least P elements, 16-byte aligned, not overlapping.  Returns out."""
+    fn = "efsign_fedavg"
+    P, T = _efsign_extent(fn, seg)
+    _f32_vector(fn, "base", base, P)
+    _f32_vector(fn, "out", out, P)
+    _check_tensor(fn, "weight", weight, torch.float32, 1, "a contiguous fp32 [K] tensor, K >= 1",
+                  exact=False, contiguous=False)
+    K = weight.numel()
+    for name, t, dtype, n in (("bits", bits, torch.int64, P // 64),
+                              ("scales", scales, torch.float32, T)):
+        if not (torch.is_tensor(t) and t.dtype == dtype and t.dim() == 2 and t.shape[0] == K
+                and t.shape[1] >= n and t.stride(1) == 1 and (K == 1 or t.stride(0) >= n)):
+            raise RuntimeError(f"{fn}: {name} must be an {_DTYPE_NAMES[dtype]} [K={K}, >= {n}] "
+                               "matrix with unit stride along its rows")
+    total = fl32(total)
+    if not math.isfinite(total) or total <= 0.0:
+        raise RuntimeError(f"{fn}: total={total} must be a positive finite number")
+    _check_same_device(fn, base, _anchor="base", bits=bits, scales=scales, weight=weight, out=out,
+                       bounds=seg.bounds)
+    if _overlaps(out[:P], base[:P]):
+        raise RuntimeError(f"{fn}: out and base overlap (padding slots are copied)")
+    for name, t in (("bits", bits), ("scales", scales), ("weight", weight)):
+        if _overlaps(out[:P], t):
+            raise RuntimeError(f"{fn}: out and {name} overlap")
+    _aligned16(fn, base=base, out=out)
+    _aligned16(fn, bits=bits, scales=scales, weight=weight)
+    for t in (base, bits, scales, weight, out):
+        _ptr(t)  # no CPU path
+    _check(lib().dls_efsign_fedavg_f32(_ptr(base), _ptr(bits), _row_pitch(bits), _ptr(scales),
+                                       _row_pitch(scales), _ptr(seg.bounds), _ptr(seg.count), T,
+                                       _ptr(weight), total, K, P, _ptr(out),
+                                       _stream(stream, base)),
+           "dls_efsign_fedavg_f32")
     return out
 
 

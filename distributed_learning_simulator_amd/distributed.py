@@ -452,6 +452,10 @@ def get_sharded_server(algorithm, **kwargs):
         raise RuntimeError("fed_secagg runs on the one-process server only (factory.get_server("
                            "'fed_secagg', sharded=False, ...)): a sharded server over masked "
                            "payloads is not implemented")
+    if algorithm == "fed_efsign":
+        raise RuntimeError("fed_efsign runs on the one-process server only (factory.get_server("
+                           "'fed_efsign', sharded=False, ...)): a sharded server over sign "
+                           "payloads is not implemented")
     if algorithm not in table:
         raise RuntimeError("unknown algorithm:" + algorithm)
     return table[algorithm](**kwargs)

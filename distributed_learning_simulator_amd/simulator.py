@@ -22,6 +22,8 @@
     python -m distributed_learning_simulator_amd.simulator --distributed_algorithm fed_secagg \\
         --worker_number 10 --round 5 [--secagg_bits 20] [--secagg_frac_bits 16] [--secagg_seed 0]
         [--secagg_weighted 1] [--secagg_dropouts 3,7] [--secagg_threshold 6]
+    python -m distributed_learning_simulator_amd.simulator --distributed_algorithm fed_efsign \\
+        --worker_number 10 --round 5 [--efsign_error_feedback 1]
 
 Same flags and flow as the reference: IID split of the training set over the
 workers (:48-50), a tester on the test split (:51), ``factory.get_server``
@@ -141,6 +143,11 @@ def get_config(argv=None):
     # round (--topk_error_feedback 0: the residual is dropped, plain top-k)
     ap.add_argument("--topk_ratio", type=float, default=None)
     ap.add_argument("--topk_error_feedback", type=int, default=None, choices=(0, 1))
+    # fed_efsign: every worker sends one bit per coordinate of its update and one scale per
+    # tensor (its mean magnitude) and keeps what the bits did not carry in a residual that is
+    # added back next round (--efsign_error_feedback 0: the residual is dropped, plain
+    # scaled sign)
+    ap.add_argument("--efsign_error_feedback", type=int, default=None, choices=(0, 1))
     # fed_secagg: every worker sends its update quantised to --secagg_bits bits with
     # --secagg_frac_bits fractional ones (defaults 20 and 16: +-8 at 1.5e-5) and masked in
     # Z_2^32 with the pair and self masks of the Philox stream under --secagg_seed;
@@ -166,6 +173,10 @@ def get_config(argv=None):
             config.topk_ratio is not None or config.topk_error_feedback is not None):
         ap.error("--topk_ratio and --topk_error_feedback apply to --distributed_algorithm "
                  "fed_topk alone")
+    if config.distributed_algorithm != "fed_efsign" and config.efsign_error_feedback is not None:
+        ap.error("--efsign_error_feedback applies to --distributed_algorithm fed_efsign alone")
+    if config.efsign_error_feedback is None:
+        config.efsign_error_feedback = 1
     if config.topk_ratio is None:
         config.topk_ratio = TOPK_DEFAULTS["topk_ratio"]
     if config.topk_error_feedback is None:
@@ -234,7 +245,8 @@ def server_kwargs(config):
 def worker_kwargs(config):
     """The keyword arguments run() passes to factory.get_worker beside trainer / queue /
     round / worker_id: the sparsifier's for fed_topk, the mask format, seed, weighting and
-    the round's participants (every worker) for fed_secagg, none for the other algorithms."""
+    the round's participants (every worker) for fed_secagg, the error-feedback switch for
+    fed_efsign, none for the other algorithms."""
     if config.distributed_algorithm == "fed_secagg":
         return {"secagg_bits": getattr(config, "secagg_bits", SECAGG_FLAGS["secagg_bits"]),
                 "secagg_frac_bits": getattr(config, "secagg_frac_bits",
@@ -243,6 +255,8 @@ def worker_kwargs(config):
                 "secagg_weighted": bool(getattr(config, "secagg_weighted",
                                                 SECAGG_FLAGS["secagg_weighted"])),
                 "participants": tuple(range(config.worker_number))}
+    if config.distributed_algorithm == "fed_efsign":
+        return {"error_feedback": bool(getattr(config, "efsign_error_feedback", 1))}
     if config.distributed_algorithm != "fed_topk":
         return {}
     return {"topk_ratio": getattr(config, "topk_ratio", TOPK_DEFAULTS["topk_ratio"]),

@@ -975,6 +975,78 @@ int dls_secagg_unmask_f32(const uint32_t *Y, int64_t ldy, const int32_t *rows, i
                           double total, int64_t P, float *out, uint32_t *sum_out,
                           dls_stream_t stream);
 
+/* Scaled-sign compression with error feedback (Karimireddy, Rebjock, Stich & Jaggi 2019,
+ * "Error feedback fixes SignSGD"; the compressor of 1-bit SGD / 1-bit Adam;
+ * csrc/efsign.hip): one bit per coordinate and one fp32 scale per tensor.  The reference
+ * simulator has no such compressor: the definitions below are this library's and
+ * tests/efsign_ref.py restates them in numpy.
+ *
+ * Segments.  The row of P coordinates (the flat parameter layout) holds T tensors; tensor
+ * t occupies [bounds[t], bounds[t+1]), bounds int64 [T+1] on the device, bounds[0] = 0,
+ * bounds[T] = P, ascending, every entry a multiple of 64; count int64 [T] on the device, 1
+ * <= count[t] <= bounds[t+1] - bounds[t], is its number of real elements: the slots at or
+ * beyond bounds[t] + count[t] are padding.  A 64-coordinate word never straddles two
+ * tensors.  Malformed segments are DLS_EINVAL, but who checks is split: the two arrays live
+ * on the device, so the library checks what it can see (P, T, the pointers) and the
+ * binding (_native.efsign_segments) checks the arrays' contents on the host before it
+ * uploads them.  With arrays that break the rules the kernels still read and write inside
+ * the row and the workspace; what they compute is then unspecified.
+ *
+ * The client's compressor.  In fp32, one rounding per operation:
+ *   u[j]   = fl(fl(w[j] - base[j]) + e[j]) for a real j, as in dls_topk_compress_f32
+ *   s[t]   = fl32(L1_t / count[t]): L1_t the fp64 sum of |u[j]| over the real j of tensor
+ *            t, the division in fp64, the quotient rounded once to fp32; scales[t] = s[t]
+ *   bit j % 64 of bits[j / 64] = 1 iff u[j] < 0 (a comparison: -0.0, +0.0 and NaN give 0);
+ *            padding slots give 0
+ *   e[j]   = fl(u[j] - s[t]) where the bit is 0, fl(u[j] + s[t]) where it is 1, in place;
+ *            padding slots of e are written +0.0
+ *   stats[0] = #{real j : u[j] not finite} (int32 [1]; the call completes, the caller
+ *            decides; s[t], and with it e, of such a tensor are not finite)
+ * The order of the sum L1_t is a function of count[t] alone: not of where the tensor sits
+ * in the row, of T, the grid, the CU count or the stream.  Chunk c of a tensor is its real
+ * elements c * DLS_EFSIGN_CHUNK .. ; of a chunk, thread i of 256 adds the elements 4 (256 v
+ * + i) + k, v and then k ascending over 0..3, a wave's 64 sums are combined by the xor
+ * butterfly (distances 32, 16, .., 1) and the four wave sums are added in wave order; a
+ * tensor's chunk sums are added per lane l over the chunks l, l + 64, .. ascending and
+ * combined by the same butterfly.  There are no floating-point atomics (the non-finite
+ * counts meet in one integer atomic add).
+ * No null pointer, 64 <= P < 2^31 (DLS_EINVAL); P a multiple of 64 (DLS_ELAYOUT); 1 <= T <=
+ * P / 64 (DLS_EINVAL); every pointer 16-byte aligned (DLS_ELAYOUT); e must not overlap w or
+ * base (DLS_EINVAL); all checked before any device call, in this order.  workspace: the bytes
+ * dls_efsign_workspace(P, T) returns (negative: the status of a bad P or T); it may hold
+ * anything on entry.  Four launches on the stream (the chunk plan, u and the chunk sums,
+ * the scales, the bits and the residual); there is no grid cap: one block per chunk.
+ * Nothing is allocated and nothing is synchronised inside the call.
+ *
+ * The server's side: FedAvg over K clients' bit rows, added to the model they started
+ * from.  bits uint64 [K, ldb], ldb >= P / 64; scales fp32 [K, lds], lds >= T; weight[i] =
+ * fl32(n_i) and total = fl32(sum of the n_i), as dls_fedavg_f32 takes them.  For a real
+ * coordinate j of tensor t:
+ *   c[i][t] = fl(fl(scales[i][t] * weight[i]) / total), the correctly rounded division
+ *             of DLS_FEDAVG_EXACT
+ *   acc     = the reference FedAvg chain (servers/fed_server.py:44-66) over the clients
+ *             i = 0..K-1 in the given order: the first assigns +c or -c by its bit (-c
+ *             is c with the sign bit flipped, so a zero scale gives -0.0), the later
+ *             ones add theirs with fp32 +
+ *   out[j]  = fl(base[j] + acc)
+ * and out[j] = base[j], the same bits, on a padding slot.  K >= 1 without an upper limit
+ * (clients are walked in tiles of DLS_EFSIGN_CLIENT_TILE), P and T as above (DLS_EINVAL);
+ * ldb, lds and the 16-byte alignment of every pointer (DLS_ELAYOUT); out must not
+ * overlap base (DLS_EINVAL); all checked before the launch.  One launch, no prologue, no
+ * atomics: one lane walks a coordinate's chain, so the bits are the same for any launch
+ * geometry.  Traffic: K / 8 + 8 bytes per coordinate. */
+#define DLS_EFSIGN_CHUNK 4096
+#define DLS_EFSIGN_CLIENT_TILE 64
+int64_t dls_efsign_workspace(int64_t P, int64_t T);
+int dls_efsign_compress_f32(const float *w, const float *base, float *e, int64_t P,
+                            const int64_t *bounds, const int64_t *count, int32_t T,
+                            uint64_t *bits, float *scales, int32_t *stats, void *workspace,
+                            dls_stream_t stream);
+int dls_efsign_fedavg_f32(const float *base, const uint64_t *bits, int64_t ldb,
+                          const float *scales, int64_t lds, const int64_t *bounds,
+                          const int64_t *count, int32_t T, const float *weight, float total,
+                          int32_t K, int64_t P, float *out, dls_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
