@@ -88,6 +88,10 @@ SIGNATURES = {
     "dls_efsign_compress_f32": ([_p, _p, _p, _i64, _p, _p, _i32, _p, _p, _p, _p, _p], _i32),
     "dls_efsign_fedavg_f32": ([_p, _p, _i64, _p, _i64, _p, _p, _i32, _p, _f32, _i32, _i64, _p, _p],
                               _i32),
+    "dls_hadamard_rotate_f32": ([_p, _i64, _u64, _u64, _i32, _p, _p], _i32),
+    "dls_drive_compress_f32": ([_p, _p, _i64, _u64, _u64, _i32, _p, _p, _p, _p], _i32),
+    "dls_drive_fedavg_f32": ([_p, _p, _i64, _p, _i64, _p, _f32, _i32, _i64, _u64, _u64, _p, _p],
+                             _i32),
     "dls_philox_u32": ([_p, _i64, _u64, _u64, _i64, _p], _i32),
     "dls_philox_normal_f32": ([_p, _i64, _u64, _u64, _i64, _p], _i32),
     "dls_normal_from_bits_f32": ([_p, _i64, _p, _p], _i32),
@@ -203,6 +207,7 @@ CSRC_HASHED = [  # the Makefile's HASHED, in its order
     "serveropt.hip",
     "secagg.hip",
     "efsign.hip",
+    "drive.hip",
     "topk.hip",
     "dpnoise.hip",
     "dls_common.h",
@@ -1109,6 +1114,132 @@ def efsign_fedavg(base, bits, scales, seg, weight, total, out, stream=None):
                                        _ptr(weight), total, K, P, _ptr(out),
                                        _stream(stream, base)),
            "dls_efsign_fedavg_f32")
+    return out
+
+
+# ----------------------------------------------- rotated one-bit compression (DRIVE)
+# DLS_DRIVE_* (include/dls_hip.h)
+DRIVE_BLOCK = 4096  # coordinates per block of the rotation
+DRIVE_CLIENT_TILE = 64  # clients per tile of dls_drive_fedavg_f32
+DRIVE_SCALES = {"unbiased": 0, "mse": 1}  # DLS_DRIVE_UNBIASED, DLS_DRIVE_MSE
+
+
+def drive_blocks(P):
+    """NB, the rotation's blocks of a row of P coordinates; it has Pd = DRIVE_BLOCK * NB
+    rotated coordinates."""
+    return (int(P) + DRIVE_BLOCK - 1) // DRIVE_BLOCK
+
+
+def _drive_extent(fn, P):
+    P = int(P)
+    if not 64 <= P < 1 << 31 or P % 64 != 0:
+        raise RuntimeError(f"{fn}: P={P} must be a multiple of 64 in 64..2^31 - 64")
+    return P, drive_blocks(P)
+
+
+def _drive_rotation(fn, seed, stream_id):
+    return _uint64(fn, "seed", seed), _uint64(fn, "stream_id", stream_id)
+
+
+def hadamard_rotate(x, P, seed, stream_id, inverse=False, out=None, stream=None):
+    """The block rotation of the rotated compressor on its own (dls_hadamard_rotate_f32): per
+    block of DRIVE_BLOCK coordinates y = 2^-6 H(sigma * x), sigma the signs of the Philox
+    stream under (seed, stream_id) and H the Walsh-Hadamard butterflies in ascending stage
+    order; ``inverse``: x = sigma * 2^-6 H(y).  Forward reads x[:P] and writes out[:Pd],
+    inverse reads x[:Pd] and writes out[:P]; out (default: a new vector) must not overlap
+    x; both 16-byte aligned.  Exact: numpy float32 reproduces every bit.  Returns out."""
+    fn = "hadamard_rotate"
+    P, NB = _drive_extent(fn, P)
+    Pd = NB * DRIVE_BLOCK
+    n_in, n_out = (Pd, P) if inverse else (P, Pd)
+    _unit_vector(fn, "x", x, torch.float32, n_in)
+    if out is None:
+        out = torch.empty(n_out, dtype=torch.float32, device=x.device)
+    _unit_vector(fn, "out", out, torch.float32, n_out)
+    seed, stream_id = _drive_rotation(fn, seed, stream_id)
+    _check_same_device(fn, x, _anchor="x", out=out)
+    if _overlaps(out[:n_out], x[:n_in]):
+        raise RuntimeError(f"{fn}: out and x overlap")
+    _aligned16(fn, x=x, out=out)
+    _ptr(x), _ptr(out)  # no CPU path
+    _check(lib().dls_hadamard_rotate_f32(_ptr(x), P, seed, stream_id, int(bool(inverse)),
+                                         _ptr(out), _stream(stream, x)),
+           "dls_hadamard_rotate_f32")
+    return out
+
+
+def drive_compress(w, base, P, seed, stream_id, scale, bits, scales, stats, stream=None):
+    """Rotated one-bit compression (dls_drive_compress_f32): with y the forward rotation
+    (``hadamard_rotate``) of u = fl32(w - base) under (seed, stream_id), bit j of ``bits``
+    (int64 [Pd / 64] words) is y[j] < 0 and ``scales`` (fp32 [NB]) holds per block sum y^2 /
+    sum |y| (``scale`` "unbiased") or sum |y| / 4096 ("mse"), the sums in fp64; stats (int32
+    [1]) becomes the number of non-finite u.  w, base: fp32 vectors of at least P elements
+    with unit stride; nothing is kept between calls.  Every tensor 16-byte aligned; the
+    outputs overlap neither each other nor w or base.  Nothing is synchronised.  Returns
+    (bits, scales)."""
+    fn = "drive_compress"
+    P, NB = _drive_extent(fn, P)
+    if scale not in DRIVE_SCALES:
+        raise RuntimeError(f"{fn}: scale={scale!r} must be one of {sorted(DRIVE_SCALES)}")
+    _f32_vector(fn, "w", w, P)
+    _f32_vector(fn, "base", base, P)
+    _unit_vector(fn, "bits", bits, torch.int64, NB * DRIVE_BLOCK // 64)
+    _unit_vector(fn, "scales", scales, torch.float32, NB)
+    _unit_vector(fn, "stats", stats, torch.int32, 1)
+    seed, stream_id = _drive_rotation(fn, seed, stream_id)
+    _check_same_device(fn, w, _anchor="w", base=base, bits=bits, scales=scales, stats=stats)
+    _check_disjoint({"w": w[:P], "base": base[:P], "bits": bits[:NB * DRIVE_BLOCK // 64],
+                     "scales": scales[:NB], "stats": stats[:1]}, f"{fn}: {{a}} and {{b}} overlap",
+                    allowed=lambda a, b: (a, b) == ("w", "base"))
+    _aligned16(fn, w=w, base=base, bits=bits, scales=scales, stats=stats)
+    for t in (w, base, bits, scales, stats):
+        _ptr(t)  # no CPU path
+    _check(lib().dls_drive_compress_f32(_ptr(w), _ptr(base), P, seed, stream_id,
+                                        DRIVE_SCALES[scale], _ptr(bits), _ptr(scales),
+                                        _ptr(stats), _stream(stream, w)),
+           "dls_drive_compress_f32")
+    return bits, scales
+
+
+def drive_fedavg(base, bits, scales, weight, total, P, seed, stream_id, out, stream=None):
+    """FedAvg over K clients' rotated bit rows, rotated back and added to ``base``
+    (dls_drive_fedavg_f32): bits int64 [K, >= Pd / 64] and scales fp32 [K, >= NB] with unit
+    stride along a row; weight fp32 [K] = the n_i, total = their fp32 sum.  Per rotated
+    coordinate of block B the chain of +-fl32(fl32(s[i][B] * n_i) / N) over the clients in row
+    order (the first assigns, the rest add), then one inverse rotation under (seed,
+    stream_id) and out = fl32(base + v) on the P coordinates.  base, out: fp32 vectors of at
+    least P elements, 16-byte aligned, not overlapping.  Returns out."""
+    fn = "drive_fedavg"
+    P, NB = _drive_extent(fn, P)
+    _f32_vector(fn, "base", base, P)
+    _f32_vector(fn, "out", out, P)
+    _check_tensor(fn, "weight", weight, torch.float32, 1, "a contiguous fp32 [K] tensor, K >= 1",
+                  exact=False, contiguous=False)
+    K = weight.numel()
+    for name, t, dtype, n in (("bits", bits, torch.int64, NB * DRIVE_BLOCK // 64),
+                              ("scales", scales, torch.float32, NB)):
+        if not (torch.is_tensor(t) and t.dtype == dtype and t.dim() == 2 and t.shape[0] == K
+                and t.shape[1] >= n and t.stride(1) == 1 and (K == 1 or t.stride(0) >= n)):
+            raise RuntimeError(f"{fn}: {name} must be an {_DTYPE_NAMES[dtype]} [K={K}, >= {n}] "
+                               "matrix with unit stride along its rows")
+    total = fl32(total)
+    if not math.isfinite(total) or total <= 0.0:
+        raise RuntimeError(f"{fn}: total={total} must be a positive finite number")
+    seed, stream_id = _drive_rotation(fn, seed, stream_id)
+    _check_same_device(fn, base, _anchor="base", bits=bits, scales=scales, weight=weight, out=out)
+    if _overlaps(out[:P], base[:P]):
+        raise RuntimeError(f"{fn}: out and base overlap")
+    for name, t in (("bits", bits), ("scales", scales), ("weight", weight)):
+        if _overlaps(out[:P], t):
+            raise RuntimeError(f"{fn}: out and {name} overlap")
+    _aligned16(fn, base=base, out=out)
+    _aligned16(fn, bits=bits, scales=scales, weight=weight)
+    for t in (base, bits, scales, weight, out):
+        _ptr(t)  # no CPU path
+    _check(lib().dls_drive_fedavg_f32(_ptr(base), _ptr(bits), _row_pitch(bits), _ptr(scales),
+                                      _row_pitch(scales), _ptr(weight), total, K, P, seed,
+                                      stream_id, _ptr(out), _stream(stream, base)),
+           "dls_drive_fedavg_f32")
     return out
 
 

@@ -1,4 +1,5 @@
 """Plugin factory (reference: factory.py:14-35) — same algorithm names and errors."""
+from .servers.fed_drive_server import FedDriveServer
 from .servers.fed_efsign_server import FedEFSignServer
 from .servers.fed_quant_server import FedQuantServer
 from .servers.fed_secagg_server import FedSecAggServer
@@ -8,6 +9,7 @@ from .servers.GTG_shapley_value_server import GTGShapleyValueServer
 from .servers.multiround_shapley_value_server import MultiRoundShapleyValueServer
 from .servers.server import Server
 from .servers.sign_sgd_server import SignSGDServer
+from .workers.fed_drive_worker import FedDriveWorker
 from .workers.fed_efsign_worker import FedEFSignWorker
 from .workers.fed_quant_worker import FedQuantWorker
 from .workers.fed_secagg_worker import FedSecAggWorker
@@ -38,6 +40,8 @@ def get_server(algorithm, sharded=None, **kwargs) -> Server:
         return FedSecAggServer(**kwargs)
     if algorithm == "fed_efsign":
         return FedEFSignServer(**kwargs)
+    if algorithm == "fed_drive":
+        return FedDriveServer(**kwargs)
     if algorithm == "multiround_shapley_value":
         return MultiRoundShapleyValueServer(**kwargs)
     if algorithm == "GTG_shapley_value":
@@ -56,6 +60,8 @@ def get_worker(algorithm, **kwargs) -> Worker:
         return FedSecAggWorker(**kwargs)
     if algorithm == "fed_efsign":
         return FedEFSignWorker(**kwargs)
+    if algorithm == "fed_drive":
+        return FedDriveWorker(**kwargs)
     if algorithm in ("fed", "multiround_shapley_value", "GTG_shapley_value"):
         return FedWorker(**kwargs)
     raise RuntimeError("unknown algorithm:" + algorithm)

@@ -24,6 +24,8 @@
         [--secagg_weighted 1] [--secagg_dropouts 3,7] [--secagg_threshold 6]
     python -m distributed_learning_simulator_amd.simulator --distributed_algorithm fed_efsign \\
         --worker_number 10 --round 5 [--efsign_error_feedback 1]
+    python -m distributed_learning_simulator_amd.simulator --distributed_algorithm fed_drive \\
+        --worker_number 10 --round 5 [--drive_seed 0] [--drive_scale unbiased|mse]
 
 Same flags and flow as the reference: IID split of the training set over the
 workers (:48-50), a tester on the test split (:51), ``factory.get_server``
@@ -49,6 +51,7 @@ from .trainer import Inferencer, Trainer
 from .workers.fed_secagg_worker import SECAGG_DEFAULTS
 
 TOPK_DEFAULTS = {"topk_ratio": 0.01, "topk_error_feedback": 1}
+DRIVE_DEFAULTS = {"drive_seed": 0, "drive_scale": "unbiased"}
 # the fed_secagg flags and what they hold when not given (threshold None: a majority)
 SECAGG_FLAGS = {**{name: int(v) for name, v in SECAGG_DEFAULTS.items()},
                 "secagg_dropouts": (), "secagg_threshold": None}
@@ -148,6 +151,13 @@ def get_config(argv=None):
     # added back next round (--efsign_error_feedback 0: the residual is dropped, plain
     # scaled sign)
     ap.add_argument("--efsign_error_feedback", type=int, default=None, choices=(0, 1))
+    # fed_drive: every worker sends one bit per coordinate of its update after a random
+    # Hadamard rotation that all workers of a round share (drawn from the library's Philox
+    # stream under --drive_seed, a fresh one every round) and one scale per 4096 coordinates:
+    # --drive_scale unbiased (DRIVE's, right in expectation) or mse (the least squared error
+    # of one decode).  The workers keep nothing between rounds
+    ap.add_argument("--drive_seed", type=int, default=None)
+    ap.add_argument("--drive_scale", type=str, default=None, choices=("unbiased", "mse"))
     # fed_secagg: every worker sends its update quantised to --secagg_bits bits with
     # --secagg_frac_bits fractional ones (defaults 20 and 16: +-8 at 1.5e-5) and masked in
     # Z_2^32 with the pair and self masks of the Philox stream under --secagg_seed;
@@ -177,6 +187,14 @@ def get_config(argv=None):
         ap.error("--efsign_error_feedback applies to --distributed_algorithm fed_efsign alone")
     if config.efsign_error_feedback is None:
         config.efsign_error_feedback = 1
+    if config.distributed_algorithm != "fed_drive" and any(
+            getattr(config, name) is not None for name in DRIVE_DEFAULTS):
+        ap.error("--drive_seed and --drive_scale apply to --distributed_algorithm fed_drive alone")
+    for name, default in DRIVE_DEFAULTS.items():
+        if getattr(config, name) is None:
+            setattr(config, name, default)
+    if not 0 <= config.drive_seed < 1 << 64:
+        ap.error("--drive_seed must lie in 0..2^64 - 1")
     if config.topk_ratio is None:
         config.topk_ratio = TOPK_DEFAULTS["topk_ratio"]
     if config.topk_error_feedback is None:
@@ -239,6 +257,8 @@ def server_kwargs(config):
         for name in ("secagg_bits", "secagg_frac_bits", "secagg_seed", "secagg_threshold"):
             kwargs[name] = getattr(config, name, SECAGG_FLAGS[name])
         kwargs["secagg_dropouts"] = tuple(getattr(config, "secagg_dropouts", ()))
+    if config.distributed_algorithm == "fed_drive":  # the rotation the workers use
+        kwargs["seed"] = getattr(config, "drive_seed", DRIVE_DEFAULTS["drive_seed"])
     return kwargs
 
 
@@ -246,7 +266,11 @@ def worker_kwargs(config):
     """The keyword arguments run() passes to factory.get_worker beside trainer / queue /
     round / worker_id: the sparsifier's for fed_topk, the mask format, seed, weighting and
     the round's participants (every worker) for fed_secagg, the error-feedback switch for
-    fed_efsign, none for the other algorithms."""
+    fed_efsign, the rotation's seed and the scale for fed_drive, none for the other
+    algorithms."""
+    if config.distributed_algorithm == "fed_drive":
+        return {"seed": getattr(config, "drive_seed", DRIVE_DEFAULTS["drive_seed"]),
+                "scale": getattr(config, "drive_scale", DRIVE_DEFAULTS["drive_scale"])}
     if config.distributed_algorithm == "fed_secagg":
         return {"secagg_bits": getattr(config, "secagg_bits", SECAGG_FLAGS["secagg_bits"]),
                 "secagg_frac_bits": getattr(config, "secagg_frac_bits",

@@ -1047,6 +1047,74 @@ int dls_efsign_fedavg_f32(const float *base, const uint64_t *bits, int64_t ldb,
                           const int64_t *count, int32_t T, const float *weight, float total,
                           int32_t K, int64_t P, float *out, dls_stream_t stream);
 
+/* Rotated one-bit compression (csrc/drive.hip): a public random rotation shared by all
+ * clients of a round (Suresh, Yu, Kumar & McMahan 2017, "Distributed mean estimation with
+ * limited communication") and the scale that makes the one-bit estimate unbiased (Vargaftik
+ * et al. 2021, "DRIVE: one-bit distributed mean estimation").  No client state: nothing is
+ * kept from round to round.  The reference simulator has no such compressor: the definitions
+ * below are this library's and tests/drive_ref.py restates them in numpy.
+ *
+ * The rotation.  A row of P coordinates, 64 <= P < 2^31, P a multiple of 64, is cut into NB =
+ * ceil(P / DLS_DRIVE_BLOCK) blocks of D = DLS_DRIVE_BLOCK = 4096 coordinates, Pd = D * NB
+ * rotated coordinates in all; a coordinate j >= P reads as +0.0 and is never written.
+ *   sigma[j] = -1 where bit j % 32 of dls_philox_u32's word of coordinate j / 32 under (seed,
+ *              stream_id) is set, else +1; applying it flips the sign bit (exact, also for
+ *              zeros, inf and NaN)
+ *   H        per block, the stages h = 1, 2, 4, .., 2048 in ascending order: every pair (i,
+ *              i + h) of the block with i & h == 0 becomes (fl32(a + b), fl32(a - b)); then
+ *              one fl32(2^-6 * x).  Every operation is rounded once and none is fused, so a
+ *              result is a function of the block's 4096 inputs alone
+ *   forward  y = 2^-6 H(sigma * x) per block;  inverse  x = sigma * 2^-6 H(y)
+ * dls_hadamard_rotate_f32: inverse == 0 reads x[0, P) and writes out[0, Pd); inverse == 1
+ * reads x[0, Pd) and writes out[0, P).  out must not overlap x.
+ *
+ * dls_drive_compress_f32, the client's side: u[j] = fl32(w[j] - base[j]), y the forward
+ * rotation of u.
+ *   bits    uint64 [Pd / 64]: bit j % 64 of word j / 64 is y[j] < 0 (a comparison: -0.0 and
+ *           NaN give 0); all Pd bits carry information, those of the last block past P too
+ *   scales  fp32 [NB]: with the fp64 sums sq = sum (double)y[j]^2 and l1 = sum |(double)y[j]|
+ *           over the block's 4096 rotated coordinates, DLS_DRIVE_UNBIASED: (float)(sq / l1),
+ *           DLS_DRIVE_MSE: (float)(l1 / 4096.0); l1 == 0 gives +0.0 in both.  The order of the
+ *           sums depends on j alone: the thread that holds the coordinates 1024 v + 64 r + l of
+ *           the block (v the wave, l the lane) adds them over r = 0..15 ascending, a wave's 64
+ *           sums are combined by the xor butterfly (distances 32, 16, .., 1) and the four
+ *           wave sums are added in wave order
+ *   stats   int32 [1]: stats[0] is set, not added to, to #{j < P : u[j] not finite} (the call
+ *           completes, the caller decides; the scales of such a block are not finite)
+ * One launch, no workspace, no floating-point atomics.  Traffic: 8 P + P / 8 bytes.
+ *
+ * dls_drive_fedavg_f32, the server's side: FedAvg over K clients' bit rows in the rotated
+ * domain, rotated back once and added to the model the clients started from.  bits uint64 [K,
+ * ldb], ldb >= Pd / 64; scales fp32 [K, lds], lds >= NB; weight[i] = fl32(n_i), total =
+ * fl32(sum of the n_i).  Per block B:
+ *   c[i]   = fl(fl(scales[i][B] * weight[i]) / total), the correctly rounded division of
+ *            DLS_FEDAVG_EXACT
+ *   z[j]   = the chain over the clients i = 0..K-1 in the given order of -c[i] where client
+ *            i's bit j is set, else +c[i]: the first assigns, the later ones add with fp32 +
+ *   v      = the inverse rotation of z;  out[j] = fl(base[j] + v[j]) for j < P
+ * K >= 1 without an upper limit (clients are walked in tiles of DLS_DRIVE_CLIENT_TILE).  One
+ * launch, no atomics: the same bits for any launch geometry, HIP stream or pitch.  out must
+ * not overlap base.  Traffic: (K / 8 + 8) P bytes and 4 K NB of scales.
+ *
+ * Checks, each before any device call, in this order: no null pointer; inverse 0 or 1,
+ * scale_mode one of the two, K >= 1; 64 <= P < 2^31 (DLS_EINVAL); P a multiple of 64, ldb and
+ * lds, every pointer 16-byte aligned (DLS_ELAYOUT); the overlaps named above, and for the
+ * compressor bits, scales and stats against w and base (DLS_EINVAL).  A failed check writes
+ * nothing.  Nothing is synchronised inside a call; the compressor keeps one 64-bit word of device
+ * memory per HIP stream, allocated when a stream first compresses. */
+#define DLS_DRIVE_BLOCK 4096
+#define DLS_DRIVE_CLIENT_TILE 64
+#define DLS_DRIVE_UNBIASED 0
+#define DLS_DRIVE_MSE 1
+int dls_hadamard_rotate_f32(const float *x, int64_t P, uint64_t seed, uint64_t stream_id,
+                            int32_t inverse, float *out, dls_stream_t stream);
+int dls_drive_compress_f32(const float *w, const float *base, int64_t P, uint64_t seed,
+                           uint64_t stream_id, int32_t scale_mode, uint64_t *bits, float *scales,
+                           int32_t *stats, dls_stream_t stream);
+int dls_drive_fedavg_f32(const float *base, const uint64_t *bits, int64_t ldb, const float *scales,
+                         int64_t lds, const float *weight, float total, int32_t K, int64_t P,
+                         uint64_t seed, uint64_t stream_id, float *out, dls_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
