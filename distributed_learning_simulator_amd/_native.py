@@ -92,6 +92,9 @@ SIGNATURES = {
     "dls_drive_compress_f32": ([_p, _p, _i64, _u64, _u64, _i32, _p, _p, _p, _p], _i32),
     "dls_drive_fedavg_f32": ([_p, _p, _i64, _p, _i64, _p, _f32, _i32, _i64, _u64, _u64, _p, _p],
                              _i32),
+    "dls_sketch_workspace": ([_i64, _i32, _i64], _i64),
+    "dls_sketch_f32": ([_p, _p, _i64, _i32, _i64, _u64, _u64, _p, _p, _p, _p], _i32),
+    "dls_unsketch_f32": ([_p, _i64, _i32, _i64, _u64, _u64, _p, _p], _i32),
     "dls_philox_u32": ([_p, _i64, _u64, _u64, _i64, _p], _i32),
     "dls_philox_normal_f32": ([_p, _i64, _u64, _u64, _i64, _p], _i32),
     "dls_normal_from_bits_f32": ([_p, _i64, _p, _p], _i32),
@@ -208,6 +211,7 @@ CSRC_HASHED = [  # the Makefile's HASHED, in its order
     "secagg.hip",
     "efsign.hip",
     "drive.hip",
+    "sketch.hip",
     "topk.hip",
     "dpnoise.hip",
     "dls_common.h",
@@ -1241,6 +1245,94 @@ def drive_fedavg(base, bits, scales, weight, total, P, seed, stream_id, out, str
                                       stream_id, _ptr(out), _stream(stream, base)),
            "dls_drive_fedavg_f32")
     return out
+
+
+# --------------------------------------------------- FetchSGD's Count Sketch
+# DLS_SKETCH_* (include/dls_hip.h)
+SKETCH_ROWS = (1, 3, 5, 7)  # R
+SKETCH_MIN_COLS, SKETCH_MAX_COLS = 1024, 1 << 24  # C, a power of two
+SKETCH_QSEG = 32  # blocks per segment of a bucket's sum
+
+
+def sketch_default_cols(P):
+    """The largest power of two <= P / 32, clamped to the legal range of C."""
+    c = max(int(P) // 32, 1)
+    return min(max(1 << (c.bit_length() - 1), SKETCH_MIN_COLS), SKETCH_MAX_COLS)
+
+
+def _sketch_shape(fn, P, R, C):
+    P, R, C = int(P), int(R), int(C)
+    if R not in SKETCH_ROWS:
+        raise RuntimeError(f"{fn}: R={R} must be one of {SKETCH_ROWS}")
+    if not SKETCH_MIN_COLS <= C <= SKETCH_MAX_COLS or C & (C - 1):
+        raise RuntimeError(f"{fn}: C={C} must be a power of two in 1024..2^24")
+    if not 4 <= P < 1 << 31 or P % 4 != 0:
+        raise RuntimeError(f"{fn}: P={P} must be a multiple of 4 in 4..2^31 - 4")
+    return P, R, C
+
+
+def sketch_workspace(P, R, C, device):
+    """The scratch buffer dls_sketch_f32 needs for this shape (a uint8 tensor on ``device``;
+    its contents never matter between calls)."""
+    P, R, C = _sketch_shape("sketch_workspace", P, R, C)
+    nbytes = int(lib().dls_sketch_workspace(P, R, C))
+    if nbytes < 0:
+        _check(nbytes, "dls_sketch_workspace")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def sketch(w, base, P, R, C, seed, stream_id, table, stats, workspace, stream=None):
+    """The Count Sketch of u = fl32(w - base) (``base`` None: of w) under (seed, stream_id)
+    (dls_sketch_f32): table (fp32 [R, C], contiguous) gets in bucket b of row r the signed sum
+    of the coordinates q C + (b ^ m_r(q)), one per block q of C coordinates, added in the
+    contract's order, so every bit is defined; stats (int32 [1]) becomes the number of
+    non-finite u.  w, base: fp32 vectors of at least P elements with unit stride; workspace:
+    ``sketch_workspace(P, R, C)``.  Every tensor 16-byte aligned; the outputs overlap neither
+    each other nor w or base.  Nothing is synchronised.  Returns table."""
+    fn = "sketch"
+    P, R, C = _sketch_shape(fn, P, R, C)
+    _f32_vector(fn, "w", w, P)
+    if base is not None:
+        _f32_vector(fn, "base", base, P)
+    _k_tensor(fn, "table", table, torch.float32, (R, C))
+    _unit_vector(fn, "stats", stats, torch.int32, 1)
+    seed, stream_id = _uint64(fn, "seed", seed), _uint64(fn, "stream_id", stream_id)
+    need = int(lib().dls_sketch_workspace(P, R, C))
+    _check_tensor(fn, "workspace", workspace, torch.uint8, need, lambda: "a uint8 vector of at "
+                  f"least {need} bytes (sketch_workspace(P, R, C))", exact=False, contiguous=False)
+    _check_same_device(fn, w, _anchor="w", base=base, table=table, stats=stats,
+                       workspace=workspace)
+    ins = {"w": w[:P]} if base is None else {"w": w[:P], "base": base[:P]}
+    _check_disjoint({**ins, "table": table, "stats": stats[:1], "workspace": workspace},
+                    f"{fn}: {{a}} and {{b}} overlap", allowed=lambda a, b: (a, b) == ("w", "base"))
+    _aligned16(fn, w=w, base=base, table=table, stats=stats, workspace=workspace)
+    for t in (w, base, table, stats, workspace):
+        _ptr(t)  # no CPU path
+    _check(lib().dls_sketch_f32(_ptr(w), _ptr(base), P, R, C, seed, stream_id, _ptr(table),
+                                _ptr(stats), _ptr(workspace), _stream(stream, w)),
+           "dls_sketch_f32")
+    return table
+
+
+def unsketch(table, P, R, C, seed, stream_id, est, stream=None):
+    """The estimate of every coordinate from a sketch (dls_unsketch_f32): est[j] (fp32, at
+    least P elements, unit stride) = the median over the rows r of s_r(j) * table[r][(j % C)
+    ^ m_r(j / C)] under the total order on bit patterns, the bits of the element of middle
+    rank: a function of the table alone.  table: fp32 [R, C], contiguous; both 16-byte
+    aligned, not overlapping.  Returns est."""
+    fn = "unsketch"
+    P, R, C = _sketch_shape(fn, P, R, C)
+    _k_tensor(fn, "table", table, torch.float32, (R, C))
+    _f32_vector(fn, "est", est, P)
+    seed, stream_id = _uint64(fn, "seed", seed), _uint64(fn, "stream_id", stream_id)
+    _check_same_device(fn, table, _anchor="table", est=est)
+    if _overlaps(est[:P], table):
+        raise RuntimeError(f"{fn}: est and table overlap")
+    _aligned16(fn, table=table, est=est)
+    _ptr(table), _ptr(est)  # no CPU path
+    _check(lib().dls_unsketch_f32(_ptr(table), P, R, C, seed, stream_id, _ptr(est),
+                                  _stream(stream, table)), "dls_unsketch_f32")
+    return est
 
 
 def subset_fedavg(U, sub_off, sub_rows, sub_weight, sub_total, P, out, stream=None):

@@ -44,6 +44,11 @@ hipStream_t side_stream(hipStream_t parent, int idx);
 // joins), created on first use and kept per (parent stream, idx), so a call
 // allocates nothing; nullptr on error.
 hipEvent_t call_event(hipStream_t parent, int idx);
+// The word (tickets taken << 32 | count so far) the blocks of one launch meet in to sum an
+// integer (dls_drive_compress_f32 and dls_sketch_f32: the non-finite coordinates): device
+// memory, zero between calls, created on first use and kept per stream (calls on one stream
+// are ordered), so a call allocates nothing; nullptr on error.
+unsigned long long *stream_cell(hipStream_t st);
 // FMA mode of dls_dequant_fedavg_mode: the tiles of table groups 0-9 in launch
 // pieces of one wave per SIMD (quant_fma.hip; groups 8-9 exact).
 int launch_dequant_fma_stream(const dls_qtile *tiles, const int32_t *nfast, const void *Q,

@@ -125,6 +125,26 @@ hipEvent_t call_event(hipStream_t parent, int idx) {
     return e;
 }
 
+unsigned long long *stream_cell(hipStream_t st) {
+    static std::mutex mu;
+    static std::unordered_map<std::string, unsigned long long *> cells;
+    int dev = 0, cur = 0;
+    if (hipStreamGetDevice(st, &dev) != hipSuccess || hipGetDevice(&cur) != hipSuccess)
+        return nullptr;
+    char key[64];
+    snprintf(key, sizeof(key), "%p/%d", (void *)st, dev);
+    std::lock_guard<std::mutex> g(mu);
+    auto it = cells.find(key);
+    if (it != cells.end()) return it->second;
+    if (cur != dev && hipSetDevice(dev) != hipSuccess) return nullptr;
+    void *p = nullptr;
+    hipError_t rc = hipMalloc(&p, 16);
+    if (rc == hipSuccess) rc = hipMemset(p, 0, 16);
+    if (cur != dev) (void)hipSetDevice(cur);
+    if (rc != hipSuccess) return nullptr;
+    return cells[key] = static_cast<unsigned long long *>(p);
+}
+
 // One block of mantissas; `target` lets the compiler vectorise the fma / div
 // (the box's and this container's hosts are AVX-512 EPYC / Xeon parts).
 __attribute__((target("avx2,fma"))) static bool two_constant_block(uint32_t m0, uint32_t n, float b,

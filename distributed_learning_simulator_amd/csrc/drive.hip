@@ -36,9 +36,6 @@
 // the cell zero for the next call.  Nothing else passes between blocks, so there is no fence
 // (on a multi-die part a device-scope release writes the die's L2 back: with a fence per
 // block the compressor took 128 us on the ResNet-18 row instead of 48).
-#include <mutex>
-#include <unordered_map>
-
 #include "philox_common.h"
 
 #ifndef DLS_DRIVE_XLANE
@@ -356,29 +353,6 @@ inline int check_extent(const char *fn, int64_t P) {
 
 inline int64_t blocks_of(int64_t P) { return (P + kD - 1) / kD; }
 
-// The word (tickets taken << 32 | non-finite coordinates so far) the blocks of one
-// dls_drive_compress_f32 meet in: device memory, zero between calls, created on first use
-// and kept per stream, so a call allocates nothing.
-unsigned long long *compress_cell(hipStream_t st) {
-    static std::mutex mu;
-    static std::unordered_map<std::string, unsigned long long *> cells;
-    int dev = 0, cur = 0;
-    if (hipStreamGetDevice(st, &dev) != hipSuccess || hipGetDevice(&cur) != hipSuccess)
-        return nullptr;
-    char key[64];
-    snprintf(key, sizeof(key), "%p/%d", (void *)st, dev);
-    std::lock_guard<std::mutex> g(mu);
-    auto it = cells.find(key);
-    if (it != cells.end()) return it->second;
-    if (cur != dev && hipSetDevice(dev) != hipSuccess) return nullptr;
-    void *p = nullptr;
-    hipError_t rc = hipMalloc(&p, 16);
-    if (rc == hipSuccess) rc = hipMemset(p, 0, 16);
-    if (cur != dev) (void)hipSetDevice(cur);
-    if (rc != hipSuccess) return nullptr;
-    return cells[key] = static_cast<unsigned long long *>(p);
-}
-
 }  // namespace
 }  // namespace dls
 
@@ -425,7 +399,7 @@ extern "C" int dls_drive_compress_f32(const float *w, const float *base, int64_t
                     !overlap(scales, 4 * NB, w, 4 * P) && !overlap(scales, 4 * NB, base, 4 * P) &&
                     !overlap(stats, 4, w, 4 * P) && !overlap(stats, 4, base, 4 * P),
                 DLS_EINVAL, "%s: bits, scales and stats must not alias w or base", fn);
-    unsigned long long *cell = compress_cell(as_stream(stream));
+    unsigned long long *cell = stream_cell(as_stream(stream));
     DLS_REQUIRE(cell, DLS_EINVAL, "%s: no device memory for the stream's counter cell", fn);
     hipLaunchKernelGGL(k_drive_compress, dim3((unsigned)NB), dim3(kBlock), 0, as_stream(stream), w,
                        base, P, make_key(seed, stream_id), (int)scale_mode, bits, scales, stats,

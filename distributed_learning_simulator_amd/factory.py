@@ -3,6 +3,7 @@ from .servers.fed_drive_server import FedDriveServer
 from .servers.fed_efsign_server import FedEFSignServer
 from .servers.fed_quant_server import FedQuantServer
 from .servers.fed_secagg_server import FedSecAggServer
+from .servers.fed_sketch_server import FedSketchServer
 from .servers.fed_server import FedServer
 from .servers.fed_topk_server import FedTopKServer
 from .servers.GTG_shapley_value_server import GTGShapleyValueServer
@@ -13,6 +14,7 @@ from .workers.fed_drive_worker import FedDriveWorker
 from .workers.fed_efsign_worker import FedEFSignWorker
 from .workers.fed_quant_worker import FedQuantWorker
 from .workers.fed_secagg_worker import FedSecAggWorker
+from .workers.fed_sketch_worker import FedSketchWorker
 from .workers.fed_topk_worker import FedTopKWorker
 from .workers.fed_worker import FedWorker
 from .workers.sign_sgd_worker import SignSGDWorker
@@ -42,6 +44,8 @@ def get_server(algorithm, sharded=None, **kwargs) -> Server:
         return FedEFSignServer(**kwargs)
     if algorithm == "fed_drive":
         return FedDriveServer(**kwargs)
+    if algorithm == "fed_sketch":
+        return FedSketchServer(**kwargs)
     if algorithm == "multiround_shapley_value":
         return MultiRoundShapleyValueServer(**kwargs)
     if algorithm == "GTG_shapley_value":
@@ -62,6 +66,8 @@ def get_worker(algorithm, **kwargs) -> Worker:
         return FedEFSignWorker(**kwargs)
     if algorithm == "fed_drive":
         return FedDriveWorker(**kwargs)
+    if algorithm == "fed_sketch":
+        return FedSketchWorker(**kwargs)
     if algorithm in ("fed", "multiround_shapley_value", "GTG_shapley_value"):
         return FedWorker(**kwargs)
     raise RuntimeError("unknown algorithm:" + algorithm)

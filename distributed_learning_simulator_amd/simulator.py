@@ -26,6 +26,9 @@
         --worker_number 10 --round 5 [--efsign_error_feedback 1]
     python -m distributed_learning_simulator_amd.simulator --distributed_algorithm fed_drive \\
         --worker_number 10 --round 5 [--drive_seed 0] [--drive_scale unbiased|mse]
+    python -m distributed_learning_simulator_amd.simulator --distributed_algorithm fed_sketch \\
+        --worker_number 10 --round 5 [--sketch_rows 5] [--sketch_cols 262144] \\
+        [--sketch_ratio 0.01] [--sketch_momentum 0.9] [--sketch_seed 0]
 
 Same flags and flow as the reference: IID split of the training set over the
 workers (:48-50), a tester on the test split (:51), ``factory.get_server``
@@ -52,6 +55,9 @@ from .workers.fed_secagg_worker import SECAGG_DEFAULTS
 
 TOPK_DEFAULTS = {"topk_ratio": 0.01, "topk_error_feedback": 1}
 DRIVE_DEFAULTS = {"drive_seed": 0, "drive_scale": "unbiased"}
+# sketch_cols None: the largest power of two <= P / 32, clamped to 1024..2^24
+SKETCH_DEFAULTS = {"sketch_rows": 5, "sketch_cols": None, "sketch_ratio": 0.01,
+                   "sketch_momentum": 0.9, "sketch_seed": 0}
 # the fed_secagg flags and what they hold when not given (threshold None: a majority)
 SECAGG_FLAGS = {**{name: int(v) for name, v in SECAGG_DEFAULTS.items()},
                 "secagg_dropouts": (), "secagg_threshold": None}
@@ -158,6 +164,16 @@ def get_config(argv=None):
     # of one decode).  The workers keep nothing between rounds
     ap.add_argument("--drive_seed", type=int, default=None)
     ap.add_argument("--drive_scale", type=str, default=None, choices=("unbiased", "mse"))
+    # fed_sketch (FetchSGD): every worker sends a Count Sketch of its update, --sketch_rows x
+    # --sketch_cols fp32 buckets (cols a power of two; default the largest <= P / 32), under the
+    # hash of --sketch_seed, and keeps nothing between rounds; the server keeps momentum
+    # (--sketch_momentum) and the error accumulation in sketch space and moves the model on the
+    # --sketch_ratio * P coordinates of the largest estimates
+    ap.add_argument("--sketch_rows", type=int, default=None, choices=(1, 3, 5, 7))
+    ap.add_argument("--sketch_cols", type=int, default=None)
+    ap.add_argument("--sketch_ratio", type=float, default=None)
+    ap.add_argument("--sketch_momentum", type=float, default=None)
+    ap.add_argument("--sketch_seed", type=int, default=None)
     # fed_secagg: every worker sends its update quantised to --secagg_bits bits with
     # --secagg_frac_bits fractional ones (defaults 20 and 16: +-8 at 1.5e-5) and masked in
     # Z_2^32 with the pair and self masks of the Philox stream under --secagg_seed;
@@ -195,6 +211,22 @@ def get_config(argv=None):
             setattr(config, name, default)
     if not 0 <= config.drive_seed < 1 << 64:
         ap.error("--drive_seed must lie in 0..2^64 - 1")
+    if config.distributed_algorithm != "fed_sketch" and any(
+            getattr(config, name) is not None for name in SKETCH_DEFAULTS):
+        ap.error("--sketch_rows, --sketch_cols, --sketch_ratio, --sketch_momentum and "
+                 "--sketch_seed apply to --distributed_algorithm fed_sketch alone")
+    for name, default in SKETCH_DEFAULTS.items():
+        if getattr(config, name) is None:
+            setattr(config, name, default)
+    cols = config.sketch_cols
+    if cols is not None and (not 1024 <= cols <= 1 << 24 or cols & (cols - 1)):
+        ap.error("--sketch_cols must be a power of two in 1024..2^24")
+    if not 0.0 < config.sketch_ratio <= 1.0:
+        ap.error("--sketch_ratio must lie in (0, 1]")
+    if not 0.0 <= config.sketch_momentum < 1.0:
+        ap.error("--sketch_momentum must lie in [0, 1)")
+    if not 0 <= config.sketch_seed < 1 << 64:
+        ap.error("--sketch_seed must lie in 0..2^64 - 1")
     if config.topk_ratio is None:
         config.topk_ratio = TOPK_DEFAULTS["topk_ratio"]
     if config.topk_error_feedback is None:
@@ -259,15 +291,27 @@ def server_kwargs(config):
         kwargs["secagg_dropouts"] = tuple(getattr(config, "secagg_dropouts", ()))
     if config.distributed_algorithm == "fed_drive":  # the rotation the workers use
         kwargs["seed"] = getattr(config, "drive_seed", DRIVE_DEFAULTS["drive_seed"])
+    if config.distributed_algorithm == "fed_sketch":  # the workers' table and hash, and the round's
+        kwargs.update(_sketch_table(config))
+        kwargs["ratio"] = getattr(config, "sketch_ratio", SKETCH_DEFAULTS["sketch_ratio"])
+        kwargs["momentum"] = getattr(config, "sketch_momentum", SKETCH_DEFAULTS["sketch_momentum"])
     return kwargs
+
+
+def _sketch_table(config):
+    """The table's shape and the hash's seed: what a fed_sketch server and its workers share."""
+    return {name: getattr(config, "sketch_" + name, SKETCH_DEFAULTS["sketch_" + name])
+            for name in ("rows", "cols", "seed")}
 
 
 def worker_kwargs(config):
     """The keyword arguments run() passes to factory.get_worker beside trainer / queue /
     round / worker_id: the sparsifier's for fed_topk, the mask format, seed, weighting and
     the round's participants (every worker) for fed_secagg, the error-feedback switch for
-    fed_efsign, the rotation's seed and the scale for fed_drive, none for the other
-    algorithms."""
+    fed_efsign, the rotation's seed and the scale for fed_drive, the table's shape and the
+    hash's seed for fed_sketch, none for the other algorithms."""
+    if config.distributed_algorithm == "fed_sketch":
+        return _sketch_table(config)
     if config.distributed_algorithm == "fed_drive":
         return {"seed": getattr(config, "drive_seed", DRIVE_DEFAULTS["drive_seed"]),
                 "scale": getattr(config, "drive_scale", DRIVE_DEFAULTS["drive_scale"])}

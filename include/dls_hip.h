@@ -1115,6 +1115,64 @@ int dls_drive_fedavg_f32(const float *base, const uint64_t *bits, int64_t ldb, c
                          int64_t lds, const float *weight, float total, int32_t K, int64_t P,
                          uint64_t seed, uint64_t stream_id, float *out, dls_stream_t stream);
 
+/* FetchSGD's Count Sketch (csrc/sketch.hip; Rothchild et al. 2020, "FetchSGD: Communication-
+ * Efficient Federated Learning with Sketching"): sparsification without client state.  A client
+ * sends an R x C table, a linear function of its update, so the server averages tables, keeps
+ * momentum and the error accumulation in sketch space, and reads a top-k out of the inverse.
+ * The reference simulator has no such compressor: the definitions below are this library's and
+ * tests/sketch_ref.py restates them in numpy.
+ *
+ * Shape.  R rows, R in {1, 3, 5, 7} (DLS_SKETCH_MAX_ROWS); C columns, a power of two, 1024 <= C
+ * <= 2^24; a row of P coordinates, 4 <= P < 2^31, P a multiple of 4, in NQ = ceil(P / C) blocks
+ * of C: coordinate j = q C + t lies in block q at offset t.  A coordinate j >= P contributes
+ * +0.0 and no sign is applied to it.
+ *   m_r(q)  = (dls_philox_u32's word of coordinate 8 q + r under (seed, stream_id)) & (C - 1)
+ *   bucket  of coordinate j in row r: t ^ m_r(q).  Within a block the map is a bijection onto
+ *           the C buckets; coordinates of different blocks collide with probability 1 / C,
+ *           independently per row.  Bucket b of row r so receives exactly one coordinate per
+ *           block, q C + (b ^ m_r(q)): the sketch is a gather
+ *   s_r(j)  = -1 where bit j % 32 of the word of coordinate 2^32 + r 2^26 + j / 32 under (seed,
+ *           stream_id) is set, else +1; applying it flips the sign bit (exact, also for zeros,
+ *           inf and NaN)
+ * (seed, stream_id) is a run's: the server's accumulators live in sketch space across rounds.
+ *
+ * dls_sketch_f32, the client's side: u[j] = fl32(w[j] - base[j]); base may be null, then u = w.
+ *   table   fp32 [R, C]: T[r][b] = the fp32 sum over q of s_r(i) u[i], i = q C + (b ^ m_r(q)).
+ *           The blocks are taken in segments of DLS_SKETCH_QSEG = 32: within a segment q
+ *           ascends, the first term assigns and each later one is added with one fp32 +; the
+ *           segment partials are then added in ascending segment order, the first assigning.
+ *           Nothing is fused
+ *   stats   int32 [1]: stats[0] is set, not added to, to #{j < P : u[j] not finite}, counted
+ *           once and not per row (the call completes, the caller decides)
+ *   workspace  the bytes dls_sketch_workspace(P, R, C) returns (negative: the status of a bad
+ *           shape); it may hold anything on entry.  With fewer than 1024 tiles of 1024 buckets
+ *           in the table, the segments are spread over workgroups and their partials go
+ *           through it (a second launch adds them); otherwise one launch
+ * No floating-point atomics: the bits depend on neither the grid, the HIP stream nor the CU
+ * count.  The non-finite counts meet in dls_drive_compress_f32's per-stream word.  Traffic: the
+ * row (and base) is read R times, R * 4 P (8 P) bytes, all but the first from cache where the
+ * row fits one; R C 4 bytes written.
+ *
+ * dls_unsketch_f32, the server's side: for j < P, e_r = s_r(j) T[r][(j % C) ^ m_r(j / C)] and
+ * est[j] = the median of e_0 .. e_{R-1} under the total order on bit patterns key(x) = b if b
+ * >= 0 else b ^ 0x7fffffff (b the bits as int32; keys compared as signed integers): est[j] has
+ * the bits of the element of middle rank.  So -0.0 < +0.0, NaNs sort to the ends by their
+ * sign and up to (R - 1) / 2 of them are outvoted; the result is a function of the table
+ * alone.  One launch; traffic 4 P bytes written and the table.
+ *
+ * Checks, each before any device call, in this order: no null pointer (base may be null); R, C
+ * and P in range (DLS_EINVAL); P a multiple of 4 and every pointer 16-byte aligned
+ * (DLS_ELAYOUT); table, stats and workspace overlap neither w or base nor each other, est does
+ * not overlap table (DLS_EINVAL).  A failed check writes nothing.  Nothing is synchronised. */
+#define DLS_SKETCH_MAX_ROWS 7
+#define DLS_SKETCH_QSEG 32
+int64_t dls_sketch_workspace(int64_t P, int32_t R, int64_t C);
+int dls_sketch_f32(const float *w, const float *base, int64_t P, int32_t R, int64_t C,
+                   uint64_t seed, uint64_t stream_id, float *table, int32_t *stats,
+                   void *workspace, dls_stream_t stream);
+int dls_unsketch_f32(const float *table, int64_t P, int32_t R, int64_t C, uint64_t seed,
+                     uint64_t stream_id, float *est, dls_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
