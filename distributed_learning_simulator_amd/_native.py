@@ -95,6 +95,12 @@ SIGNATURES = {
     "dls_sketch_workspace": ([_i64, _i32, _i64], _i64),
     "dls_sketch_f32": ([_p, _p, _i64, _i32, _i64, _u64, _u64, _p, _p, _p, _p], _i32),
     "dls_unsketch_f32": ([_p, _i64, _i32, _i64, _u64, _u64, _p, _p], _i32),
+    "dls_powersgd_payload_len": ([_p, _i64, _i32], _i64),
+    "dls_powersgd_workspace": ([_p, _i64, _i32, _i64], _i64),
+    "dls_powersgd_compress_f32": ([_p, _p, _p, _i64, _p, _i32, _i32, _p, _p, _i64, _p, _p, _i64,
+                                   _p], _i32),
+    "dls_powersgd_fedavg_f32": ([_p, _p, _i64, _i64, _p, _i32, _i32, _p, _f32, _i32, _i64, _p, _p],
+                                _i32),
     "dls_philox_u32": ([_p, _i64, _u64, _u64, _i64, _p], _i32),
     "dls_philox_normal_f32": ([_p, _i64, _u64, _u64, _i64, _p], _i32),
     "dls_normal_from_bits_f32": ([_p, _i64, _p, _p], _i32),
@@ -212,6 +218,7 @@ CSRC_HASHED = [  # the Makefile's HASHED, in its order
     "efsign.hip",
     "drive.hip",
     "sketch.hip",
+    "powersgd.hip",
     "topk.hip",
     "dpnoise.hip",
     "dls_common.h",
@@ -1333,6 +1340,206 @@ def unsketch(table, P, R, C, seed, stream_id, est, stream=None):
     _check(lib().dls_unsketch_f32(_ptr(table), P, R, C, seed, stream_id, _ptr(est),
                                   _stream(stream, table)), "dls_unsketch_f32")
     return est
+
+
+# ------------------------------------------- low-rank compression (PowerSGD), error feedback
+# DLS_POWERSGD_* (include/dls_hip.h)
+POWERSGD_MAX_RANK = 16
+POWERSGD_CHUNK = 256  # columns of one work item of the compressor's first pass
+POWERSGD_CLIENT_TILE = 64  # clients per tile of dls_powersgd_fedavg_f32
+POWERSGD_PLAN_WORDS = 10
+
+
+def _ru64(x):
+    return (x + 63) // 64 * 64
+
+
+def powersgd_matrix_view(shape):
+    """(n, m) of a tensor: n = d0, m = numel / d0 (a vector: m = 1; a scalar: 1 x 1)."""
+    shape = tuple(int(d) for d in shape)
+    numel = max(math.prod(shape), 1) if shape else 1
+    n = max(shape[0], 1) if shape else 1
+    return n, numel // n
+
+
+def powersgd_compressed(n, m, r):
+    """The compressed / dense rule at rank r."""
+    return r <= min(n, m) and (n + m) * r < n * m
+
+
+class PowerSGDPlan:
+    """The tensors of a flat row as dls_powersgd_* take them: ``table`` int64 [T + 1,
+    POWERSGD_PLAN_WORDS] on the device and its host copy ``rows``; ``L`` floats per payload,
+    ``workspace_bytes`` for the compressor; built and checked on the host (powersgd_plan)."""
+
+    __slots__ = ("table", "rows", "T", "P", "r", "L", "workspace_bytes")
+
+    def __init__(self, table, rows, T, P, r, L, workspace_bytes):
+        self.table, self.rows, self.T, self.P, self.r = table, rows, T, P, r
+        self.L, self.workspace_bytes = L, workspace_bytes
+
+    def kind(self, t):
+        return self.rows[t][3]
+
+    def blocks(self, t):
+        """(offset of P^ or of the values, offset of Q) of tensor t in a payload."""
+        return self.rows[t][4], self.rows[t][5]
+
+
+def powersgd_plan(bounds, dims, r, device):
+    """Build the plan on the host (the library cannot check it: it lives on the device) and
+    upload it.  bounds: T + 1 ascending multiples of 64 from 0 to P, 64 <= P < 2^31; dims: T
+    pairs (n, m), n, m >= 1, n m <= bounds[t + 1] - bounds[t]; r in 1..16.  Malformed
+    arguments are the library's DLS_EINVAL, raised here."""
+    fn = "powersgd_plan"
+
+    def refuse(what):
+        raise RuntimeError(f"{fn}: {what} (DLS_EINVAL)")
+    if isinstance(r, bool) or not isinstance(r, int) or not 1 <= r <= POWERSGD_MAX_RANK:
+        refuse(f"r={r!r} must be an integer in 1..{POWERSGD_MAX_RANK}")
+    bounds, dims = [int(b) for b in bounds], [(int(n), int(m)) for n, m in dims]
+    T = len(dims)
+    if T < 1 or len(bounds) != T + 1:
+        refuse(f"bounds must hold T + 1 = {T + 1} entries for T = {T} >= 1 tensors, not "
+               f"{len(bounds)}")
+    if bounds[0] != 0 or not 64 <= bounds[-1] < 1 << 31:
+        refuse(f"bounds must run from 0 to P, 64 <= P < 2^31, not {bounds[0]}..{bounds[-1]}")
+    P = bounds[-1]
+    if any(b % 64 for b in bounds):
+        refuse("every bound must be a multiple of 64")
+    rows, poff = [], 0
+    ws = (4 * (P // 16 + T) + 15) // 16 * 16
+    first = [0, 0, 0]
+    for t, (n, m) in enumerate(dims):
+        ext = bounds[t + 1] - bounds[t]
+        if n < 1 or m < 1 or not n * m <= ext:
+            refuse(f"tensor {t} is {n} x {m}: n, m >= 1 and n m <= bounds[{t + 1}] - bounds[{t}] "
+                   f"= {ext}")
+        if powersgd_compressed(n, m, r):
+            chunks = -(-m // POWERSGD_CHUNK)
+            rows.append([bounds[t], n, m, 1, poff, poff + _ru64(n * r), ws] + first)
+            poff += _ru64(n * r) + _ru64(m * r)
+            ws += 128 * n + 64 * n * chunks
+            items = (-(-n // 16) * chunks, -(-m // 16), -(-n // 32) * -(-m // 64))
+        else:
+            rows.append([bounds[t], n, m, 0, poff, 0, 0] + first)
+            poff += _ru64(n * m)
+            items = (-(-ext // 1024), 0, -(-ext // 1024))
+        first = [a + b for a, b in zip(first, items)]
+    rows.append([P, 0, 0, 0, poff, 0, ws] + first)
+    if not poff < 1 << 31:
+        refuse(f"the payload would hold {poff} floats (< 2^31)")
+    flat = (ctypes.c_int64 * (2 * T))(*[d for nm in dims for d in nm])
+    sizes = (int(lib().dls_powersgd_payload_len(flat, T, r)),
+             int(lib().dls_powersgd_workspace(flat, T, r, P)))
+    if sizes != (poff, ws):
+        raise RuntimeError(f"{fn}: the library sizes the payload and the workspace {sizes}, the "
+                           f"binding {(poff, ws)}: {lib().dls_last_error().decode(errors='replace')}")
+    return PowerSGDPlan(torch.tensor(rows, dtype=torch.int64).to(device), rows, T, P, r, poff, ws)
+
+
+def powersgd_layout_plan(layout, r, device):
+    """powersgd_plan of a ParameterLayout: one entry per tensor."""
+    return powersgd_plan(list(layout.offsets) + [layout.P],
+                         [powersgd_matrix_view(s) for s in layout.shapes], r, device)
+
+
+def _powersgd_extent(fn, plan):
+    if not isinstance(plan, PowerSGDPlan):
+        raise RuntimeError(f"{fn}: plan must come from powersgd_plan, not {type(plan).__name__}")
+    return plan.P, plan.T, plan.r, plan.L
+
+
+def powersgd_workspace(plan, device):
+    """The scratch buffer dls_powersgd_compress_f32 needs under this plan (a uint8 tensor on
+    ``device``; its contents never matter between calls)."""
+    _powersgd_extent("powersgd_workspace", plan)
+    return torch.empty(plan.workspace_bytes, dtype=torch.uint8, device=device)
+
+
+def powersgd_compress(w, base, e, plan, q0, payload, stats, workspace, stream=None):
+    """One power-iteration step per weight matrix with error feedback
+    (dls_powersgd_compress_f32): with u = fl32(fl32(w - base) + e), per compressed tensor P^ =
+    orth(U Q0) and Q = U^T P^ go to ``payload`` (fp32 [L], the plan's blocks), e becomes u - P^
+    Q^T; a dense tensor sends w and zeroes its e.  q0: fp32 [L], read at the Q blocks.  e may
+    be None (no error feedback, nothing written back).  stats (int32 [1]): the number of
+    non-finite u.  Every tensor 16-byte aligned; nothing is synchronised.  Returns payload."""
+    fn = "powersgd_compress"
+    P, T, r, L = _powersgd_extent(fn, plan)
+    for name, t in (("w", w), ("base", base)) + ((("e", e),) if e is not None else ()):
+        _f32_vector(fn, name, t, P)
+    for name, t in (("q0", q0), ("payload", payload)):
+        _unit_vector(fn, name, t, torch.float32, L, count=("L", L))
+    _unit_vector(fn, "stats", stats, torch.int32, 1)
+    need = plan.workspace_bytes
+    _check_tensor(fn, "workspace", workspace, torch.uint8, need, lambda: "a uint8 vector of at "
+                  f"least {need} bytes (powersgd_workspace(plan))", exact=False, contiguous=False)
+    _check_same_device(fn, w, _anchor="w", base=base, e=e, q0=q0, payload=payload, stats=stats,
+                       workspace=workspace, plan=plan.table)
+    if e is not None:
+        for name, other in (("w", w), ("base", base)):
+            if _overlaps(e[:P], other[:P]):
+                raise RuntimeError(f"{fn}: e and {name} overlap (the residual is updated in place)")
+    outs = {"payload": payload[:L], "stats": stats[:1], "workspace": workspace}
+    if e is not None:
+        outs["e"] = e[:P]
+    _check_disjoint(outs, f"{fn}: {{a}} and {{b}} overlap")
+    for name, t in (("w", w[:P]), ("base", base[:P]), ("q0", q0[:L])):
+        for oname, o in outs.items():
+            if oname != "e" and _overlaps(o, t):
+                raise RuntimeError(f"{fn}: {oname} and {name} overlap")
+    for name, t in (("w", w), ("base", base), ("e", e), ("q0", q0), ("payload", payload),
+                    ("stats", stats), ("workspace", workspace)):
+        _aligned16(fn, **{name: t})
+    for t in (w, base, q0, payload, stats, workspace, plan.table):
+        _ptr(t)  # no CPU path
+    _check(lib().dls_powersgd_compress_f32(_ptr(w), _ptr(base), _ptr(e), P, _ptr(plan.table), T, r,
+                                           _ptr(q0), _ptr(payload), L, _ptr(stats),
+                                           _ptr(workspace), workspace.numel(), _stream(stream, w)),
+           "dls_powersgd_compress_f32")
+    return payload
+
+
+def powersgd_fedavg(base, payloads, plan, weight, total, out, stream=None):
+    """``base`` + the FedAvg of K clients' low-rank payloads (dls_powersgd_fedavg_f32):
+    payloads fp32 [K, >= L] with unit stride along a row; weight fp32 [K] = the n_i, total =
+    their fp32 sum.  A compressed tensor gets fl32(base + sum_i sum_q fl32(c_i P^_i) Q_i), c_i
+    = fl32(n_i / N), one fma chain in client order; a dense one the exact FedAvg chain of the
+    sent values; padding keeps base's bits.  base, out: fp32 vectors of at least P elements,
+    16-byte aligned, not overlapping.  Returns out."""
+    fn = "powersgd_fedavg"
+    P, T, r, L = _powersgd_extent(fn, plan)
+    _f32_vector(fn, "base", base, P)
+    _f32_vector(fn, "out", out, P)
+    _check_tensor(fn, "weight", weight, torch.float32, 1, "a contiguous fp32 [K] tensor, K >= 1",
+                  exact=False, contiguous=False)
+    K = weight.numel()
+    t = payloads
+    if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.dim() == 2 and t.shape[0] == K
+            and t.shape[1] >= L and t.stride(1) == 1 and (K == 1 or t.stride(0) >= L)):
+        raise RuntimeError(f"{fn}: payloads must be an fp32 [K={K}, >= {L}] matrix with unit "
+                           "stride along its rows")
+    total = fl32(total)
+    if not math.isfinite(total) or total <= 0.0:
+        raise RuntimeError(f"{fn}: total={total} must be a positive finite number")
+    _check_same_device(fn, base, _anchor="base", payloads=payloads, weight=weight, out=out,
+                       plan=plan.table)
+    if _overlaps(out[:P], base[:P]):
+        raise RuntimeError(f"{fn}: out and base overlap (padding slots are copied)")
+    for name, t in (("payloads", payloads), ("weight", weight)):
+        if _overlaps(out[:P], t):
+            raise RuntimeError(f"{fn}: out and {name} overlap")
+    _aligned16(fn, base=base, out=out)
+    _aligned16(fn, payloads=payloads, weight=weight)
+    if _row_pitch(payloads) % 4:
+        raise RuntimeError(f"{fn}: the pitch of payloads must be a multiple of 4 floats")
+    for t in (base, payloads, weight, out, plan.table):
+        _ptr(t)  # no CPU path
+    _check(lib().dls_powersgd_fedavg_f32(_ptr(base), _ptr(payloads), _row_pitch(payloads), L,
+                                         _ptr(plan.table), T, r, _ptr(weight), total, K, P,
+                                         _ptr(out), _stream(stream, base)),
+           "dls_powersgd_fedavg_f32")
+    return out
 
 
 def subset_fedavg(U, sub_off, sub_rows, sub_weight, sub_total, P, out, stream=None):

@@ -464,6 +464,10 @@ def get_sharded_server(algorithm, **kwargs):
         raise RuntimeError("fed_sketch runs on the one-process server only (factory.get_server("
                            "'fed_sketch', sharded=False, ...)): a sharded server over Count Sketch "
                            "payloads is not implemented")
+    if algorithm == "fed_powersgd":
+        raise RuntimeError("fed_powersgd runs on the one-process server only (factory.get_server("
+                           "'fed_powersgd', sharded=False, ...)): a sharded server over low-rank "
+                           "payloads is not implemented")
     if algorithm not in table:
         raise RuntimeError("unknown algorithm:" + algorithm)
     return table[algorithm](**kwargs)

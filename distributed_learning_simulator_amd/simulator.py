@@ -29,6 +29,9 @@
     python -m distributed_learning_simulator_amd.simulator --distributed_algorithm fed_sketch \\
         --worker_number 10 --round 5 [--sketch_rows 5] [--sketch_cols 262144] \\
         [--sketch_ratio 0.01] [--sketch_momentum 0.9] [--sketch_seed 0]
+    python -m distributed_learning_simulator_amd.simulator --distributed_algorithm fed_powersgd \\
+        --worker_number 10 --round 5 [--powersgd_rank 4] [--powersgd_seed 0] \\
+        [--powersgd_warm_start 1] [--powersgd_error_feedback 1]
 
 Same flags and flow as the reference: IID split of the training set over the
 workers (:48-50), a tester on the test split (:51), ``factory.get_server``
@@ -58,6 +61,8 @@ DRIVE_DEFAULTS = {"drive_seed": 0, "drive_scale": "unbiased"}
 # sketch_cols None: the largest power of two <= P / 32, clamped to 1024..2^24
 SKETCH_DEFAULTS = {"sketch_rows": 5, "sketch_cols": None, "sketch_ratio": 0.01,
                    "sketch_momentum": 0.9, "sketch_seed": 0}
+POWERSGD_DEFAULTS = {"powersgd_rank": 4, "powersgd_seed": 0, "powersgd_warm_start": 1,
+                     "powersgd_error_feedback": 1}
 # the fed_secagg flags and what they hold when not given (threshold None: a majority)
 SECAGG_FLAGS = {**{name: int(v) for name, v in SECAGG_DEFAULTS.items()},
                 "secagg_dropouts": (), "secagg_threshold": None}
@@ -174,6 +179,16 @@ def get_config(argv=None):
     ap.add_argument("--sketch_ratio", type=float, default=None)
     ap.add_argument("--sketch_momentum", type=float, default=None)
     ap.add_argument("--sketch_seed", type=int, default=None)
+    # fed_powersgd: every worker sends, per weight matrix of its update, the rank ---powersgd_rank
+    # factors of one power-iteration step (vectors and matrices too small to gain go as they
+    # are) and keeps what the factors did not carry in a residual that is added back next round
+    # (--powersgd_error_feedback 0: the residual is dropped); the step starts from the worker's
+    # last Q (--powersgd_warm_start 0: from a fresh Gaussian every round), round 1 from the
+    # library's Philox stream under --powersgd_seed
+    ap.add_argument("--powersgd_rank", type=int, default=None)
+    ap.add_argument("--powersgd_seed", type=int, default=None)
+    ap.add_argument("--powersgd_warm_start", type=int, default=None, choices=(0, 1))
+    ap.add_argument("--powersgd_error_feedback", type=int, default=None, choices=(0, 1))
     # fed_secagg: every worker sends its update quantised to --secagg_bits bits with
     # --secagg_frac_bits fractional ones (defaults 20 and 16: +-8 at 1.5e-5) and masked in
     # Z_2^32 with the pair and self masks of the Philox stream under --secagg_seed;
@@ -227,6 +242,17 @@ def get_config(argv=None):
         ap.error("--sketch_momentum must lie in [0, 1)")
     if not 0 <= config.sketch_seed < 1 << 64:
         ap.error("--sketch_seed must lie in 0..2^64 - 1")
+    if config.distributed_algorithm != "fed_powersgd" and any(
+            getattr(config, name) is not None for name in POWERSGD_DEFAULTS):
+        ap.error("--powersgd_rank, --powersgd_seed, --powersgd_warm_start and "
+                 "--powersgd_error_feedback apply to --distributed_algorithm fed_powersgd alone")
+    for name, default in POWERSGD_DEFAULTS.items():
+        if getattr(config, name) is None:
+            setattr(config, name, default)
+    if not 1 <= config.powersgd_rank <= 16:
+        ap.error("--powersgd_rank must lie in 1..16")
+    if not 0 <= config.powersgd_seed < 1 << 64:
+        ap.error("--powersgd_seed must lie in 0..2^64 - 1")
     if config.topk_ratio is None:
         config.topk_ratio = TOPK_DEFAULTS["topk_ratio"]
     if config.topk_error_feedback is None:
@@ -295,6 +321,8 @@ def server_kwargs(config):
         kwargs.update(_sketch_table(config))
         kwargs["ratio"] = getattr(config, "sketch_ratio", SKETCH_DEFAULTS["sketch_ratio"])
         kwargs["momentum"] = getattr(config, "sketch_momentum", SKETCH_DEFAULTS["sketch_momentum"])
+    if config.distributed_algorithm == "fed_powersgd":  # the rank the workers' payloads have
+        kwargs["rank"] = getattr(config, "powersgd_rank", POWERSGD_DEFAULTS["powersgd_rank"])
     return kwargs
 
 
@@ -309,7 +337,12 @@ def worker_kwargs(config):
     round / worker_id: the sparsifier's for fed_topk, the mask format, seed, weighting and
     the round's participants (every worker) for fed_secagg, the error-feedback switch for
     fed_efsign, the rotation's seed and the scale for fed_drive, the table's shape and the
-    hash's seed for fed_sketch, none for the other algorithms."""
+    hash's seed for fed_sketch, the rank, the seed and the two switches for fed_powersgd, none
+    for the other algorithms."""
+    if config.distributed_algorithm == "fed_powersgd":
+        get = lambda name: getattr(config, "powersgd_" + name, POWERSGD_DEFAULTS["powersgd_" + name])
+        return {"rank": get("rank"), "seed": get("seed"), "warm_start": bool(get("warm_start")),
+                "error_feedback": bool(get("error_feedback"))}
     if config.distributed_algorithm == "fed_sketch":
         return _sketch_table(config)
     if config.distributed_algorithm == "fed_drive":

@@ -1173,6 +1173,106 @@ int dls_sketch_f32(const float *w, const float *base, int64_t P, int32_t R, int6
 int dls_unsketch_f32(const float *table, int64_t P, int32_t R, int64_t C, uint64_t seed,
                      uint64_t stream_id, float *est, dls_stream_t stream);
 
+/* Low-rank update compression with error feedback (Vogels, Karimireddy & Jaggi 2019,
+ * "PowerSGD: practical low-rank gradient compression"; csrc/powersgd.hip): one power-iteration
+ * step per weight matrix on the client, each client on its own (no all-reduce of P), and the
+ * FedAvg of the clients' factors on the server.  The reference simulator has no such
+ * compressor: the definitions below are this library's and tests/powersgd_ref.py restates them
+ * in numpy.
+ *
+ * Tensors.  A tensor of shape (d0, d1, ..) is seen as the row-major matrix n = d0, m = numel /
+ * d0 (a vector: m = 1).  At rank r, 1 <= r <= DLS_POWERSGD_MAX_RANK, it is COMPRESSED iff r <=
+ * min(n, m) and (n + m) r < n m, else DENSE (every vector is dense: m = 1 fails the second
+ * test).  A payload (fp32 [L]) holds per tensor, in tensor order, every block starting at a
+ * multiple of 64 floats and padded to one with +0.0: compressed, the block P^ [n][r] and then
+ * the block Q [m][r], both row-major; dense, one block of the n m values.
+ *
+ * The plan.  int64 [T + 1][DLS_POWERSGD_PLAN_WORDS] on the device; row t: 0 the tensor's
+ * offset in the row of P coordinates (a multiple of 64; row T holds P, so tensor t occupies
+ * [off[t], off[t + 1]) and the slots from n m on are padding), 1 n, 2 m, 3 kind (1
+ * compressed, 0 dense), 4 the offset of its P^ (or value) block in the payload, 5 of its Q
+ * block, 6 the byte offset of its region of the workspace (compressed: 128 n + 64 n ceil(m /
+ * DLS_POWERSGD_CHUNK) bytes, from dls_powersgd_workspace's first 16-byte multiple >= 4 (P / 16
+ * + T) on), 7 / 8 / 9 the number of work items of the tensors before it in the compressor's
+ * first pass (compressed: ceil(n / 16) ceil(m / DLS_POWERSGD_CHUNK); dense: ceil(extent /
+ * 1024)), its last pass (ceil(m / 16); 0) and the server (ceil(n / 32) ceil(m / 64); ceil(
+ * extent / 1024)); row T holds the totals.  The plan lives on the device, so who checks is
+ * split as for dls_efsign_*: the binding (_native.powersgd_plan) builds and checks it on the
+ * host; the library checks what it can see, and the kernels test every row against P, L and
+ * the workspace size and skip a tensor that does not fit, so they never read or write outside
+ * the arrays of the call; what they compute from a malformed plan is unspecified.
+ *
+ * The client, per compressed tensor (U the n x m view of u):
+ *   u   = fl(fl(w - base) + e), as dls_topk_compress_f32 defines it (e == NULL: u = fl(w - base))
+ *   P   = U Q0        Q0 fp32 [m][r], read from q0 at the tensor's Q block offset (q0 has the
+ *                     payload's layout)
+ *   P^  = the columns of P orthonormalised by modified Gram-Schmidt in column order 0..r-1:
+ *         column q is divided by the square root of its squared norm and at once projected
+ *         out of the columns after it.  A column whose squared norm is then 0 or not finite
+ *         becomes an all-zero column of P^ and is projected out of nothing.
+ *   Q   = U^T P^      [m][r]
+ *   e   = fl(u - R), R = P^ Q^T, in place; padding slots of e are written +0.0
+ * The payload gets P^ and Q.  For a dense tensor the payload gets w's values and e of the
+ * tensor, padding included, is written +0.0.  stats[0] (int32) = #{real j : u[j] not finite},
+ * dense tensors included; the call completes and the caller decides.  With e == NULL nothing
+ * is written back.
+ * Arithmetic.  Every matrix product runs on v_mfma_f32_16x16x4_f32: each entry is an fp32 fma
+ * chain from +0.0, zero-padded to whole instructions (adding an exact zero rounds nothing):
+ *   P: the m columns are cut into chunks of DLS_POWERSGD_CHUNK; a chunk's partial is one chain
+ *      over its columns; the partials are added in chunk order in fp64.  L = min(m,
+ *      DLS_POWERSGD_CHUNK), c = 1 (the fp64 sum's slack)
+ *   Q: one chain over the n rows, ascending: L = n, c = 0
+ *   R: one chain over q ascending: L = r; then e = fl(u - R), one more rounding
+ * with, elementwise, |computed - exact| <= g sum |a| |b| over the contraction, g = (L + c) u /
+ * (1 - (L + c) u), u = 2^-24 (each term passes through at most L roundings; products are not
+ * rounded), while the values stay in the normal range.  Gram-Schmidt runs in fp64 on the
+ * fp64 P: thread i of 256 adds its rows i, i + 256, .. ascending, a wave's 64 sums meet in the
+ * xor butterfly (distances 32, .., 1), the four wave sums are added in wave order: the order
+ * depends on n alone.  The normalised column is rounded to fp32 once, so P^T P^ = I within
+ * 3 u elementwise while kappa_2(P) n 2^-53 stays far below u.  A rank-deficient P whose
+ * deficiency is not exact in fp64 yields a normalised column of rounding noise, not zeros.
+ * Where every product and partial sum is exactly representable every output is exact, bit
+ * for bit.  No floating-point atomics and no dependence on the grid, the CU count, T or the
+ * tensor's place in the row: work items are cut relative to the tensor's own start.
+ *
+ * The server: out = base + the FedAvg of K clients' payloads (fp32 [K, ldp]); weight[i] =
+ * fl32(n_i) and total = fl32(sum of the n_i), as dls_fedavg_f32 takes them.
+ *   compressed, real coordinate (a, b):  c_i = fl(weight[i] / total) (correctly rounded);
+ *     A_i[a][q] = fl(c_i P^_i[a][q]); acc = one fma chain from +0.0 over A_i[a][q] Q_i[b][q],
+ *     client i ascending, then q ascending; out = fl(base + acc).  Elementwise |out - (base +
+ *     sum A Q)| <= g (|base| + sum |A| |Q|) with L = K r, c = 1.  Clients are walked in tiles
+ *     of DLS_POWERSGD_CLIENT_TILE, a later tile continuing the chain from the fp32 value
+ *     the tile before it left; K has no upper limit.
+ *   dense, real coordinate: the reference FedAvg chain (servers/fed_server.py:44-66) of the K
+ *     sent values: the bits dls_fedavg_f32 (DLS_FEDAVG_EXACT) gives on that slice; base plays
+ *     no part.
+ *   padding slots: base's bits.
+ * One launch.  A non-finite factor entry makes the out coordinates of its row (P^) or column
+ * (Q) of that tensor non-finite, and no others.
+ *
+ * Checks, each before any device call, in this order.  DLS_EINVAL: a null pointer (e may be
+ * null); K >= 1; 64 <= P < 2^31; 1 <= T <= P / 64; 1 <= r <= DLS_POWERSGD_MAX_RANK; 64 <= L <
+ * 2^31; the compressor's workspace_bytes at least 4 (P / 16 + T) rounded up to 16, the
+ * server's total positive and finite; e overlapping w or base, payload overlapping q0, out
+ * overlapping base.  DLS_ELAYOUT: P and L multiples of 64; ldp a multiple of 4 and >= L; every
+ * pointer 16-byte aligned.  A failed check writes nothing.  Nothing is allocated or
+ * synchronised inside a call.  The two size queries take the host array dims int64 [T][2] =
+ * (n, m) per tensor and return the payload's floats and the workspace's bytes (negative: the
+ * status of bad arguments; n, m >= 1 and n m < 2^31). */
+#define DLS_POWERSGD_MAX_RANK 16
+#define DLS_POWERSGD_CHUNK 256
+#define DLS_POWERSGD_CLIENT_TILE 64
+#define DLS_POWERSGD_PLAN_WORDS 10
+int64_t dls_powersgd_payload_len(const int64_t *dims, int64_t T, int32_t r);
+int64_t dls_powersgd_workspace(const int64_t *dims, int64_t T, int32_t r, int64_t P);
+int dls_powersgd_compress_f32(const float *w, const float *base, float *e, int64_t P,
+                              const int64_t *plan, int32_t T, int32_t r, const float *q0,
+                              float *payload, int64_t L, int32_t *stats, void *workspace,
+                              int64_t workspace_bytes, dls_stream_t stream);
+int dls_powersgd_fedavg_f32(const float *base, const float *payloads, int64_t ldp, int64_t L,
+                            const int64_t *plan, int32_t T, int32_t r, const float *weight,
+                            float total, int32_t K, int64_t P, float *out, dls_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
