@@ -92,6 +92,8 @@ SIGNATURES = {
     "dls_drive_compress_f32": ([_p, _p, _i64, _u64, _u64, _i32, _p, _p, _p, _p], _i32),
     "dls_drive_fedavg_f32": ([_p, _p, _i64, _p, _i64, _p, _f32, _i32, _i64, _u64, _u64, _p, _p],
                              _i32),
+    "dls_qsgd_compress_f32": ([_p, _p, _i64, _i32, _i32, _u64, _u64, _p, _p, _p, _p], _i32),
+    "dls_qsgd_fedavg_f32": ([_p, _p, _i64, _p, _i64, _p, _f32, _i32, _i64, _i32, _p, _p], _i32),
     "dls_sketch_workspace": ([_i64, _i32, _i64], _i64),
     "dls_sketch_f32": ([_p, _p, _i64, _i32, _i64, _u64, _u64, _p, _p, _p, _p], _i32),
     "dls_unsketch_f32": ([_p, _i64, _i32, _i64, _u64, _u64, _p, _p], _i32),
@@ -219,6 +221,7 @@ CSRC_HASHED = [  # the Makefile's HASHED, in its order
     "drive.hip",
     "sketch.hip",
     "powersgd.hip",
+    "qsgd.hip",
     "topk.hip",
     "dpnoise.hip",
     "dls_common.h",
@@ -1251,6 +1254,113 @@ def drive_fedavg(base, bits, scales, weight, total, P, seed, stream_id, out, str
                                       _row_pitch(scales), _ptr(weight), total, K, P, seed,
                                       stream_id, _ptr(out), _stream(stream, base)),
            "dls_drive_fedavg_f32")
+    return out
+
+
+# ------------------------------------------ stochastic quantization (QSGD / TernGrad)
+# DLS_QSGD_* (include/dls_hip.h)
+QSGD_BUCKET = 512  # coordinates per norm
+QSGD_CLIENT_TILE = 64  # clients per tile of dls_qsgd_fedavg_f32
+QSGD_NORMS = {"max": 0, "l2": 1}  # DLS_QSGD_MAX, DLS_QSGD_L2
+QSGD_BITS = (2, 4, 8)
+
+
+def qsgd_buckets(P):
+    """NB, the buckets (one norm each) of a row of P coordinates."""
+    return (int(P) + QSGD_BUCKET - 1) // QSGD_BUCKET
+
+
+def qsgd_code_words(P, bits):
+    """The uint32 words of a client's code row: NB * 16 * bits, the last bucket whole."""
+    if bits not in QSGD_BITS:
+        raise RuntimeError(f"qsgd_code_words: bits={bits!r} must be one of {QSGD_BITS}")
+    return qsgd_buckets(P) * 16 * bits
+
+
+def _qsgd_extent(fn, P, bits):
+    P = int(P)
+    if isinstance(bits, bool) or bits not in QSGD_BITS:
+        raise RuntimeError(f"{fn}: bits={bits!r} must be one of {QSGD_BITS}")
+    if not 64 <= P < 1 << 31 or P % 64 != 0:
+        raise RuntimeError(f"{fn}: P={P} must be a multiple of 64 in 64..2^31 - 64")
+    return P, qsgd_buckets(P), qsgd_code_words(P, bits)
+
+
+def qsgd_compress(w, base, P, bits, norm, seed, stream_id, codes, scales, stats, stream=None):
+    """Stochastic quantization (dls_qsgd_compress_f32) of u = fl32(w - base) to ``bits`` in
+    (2, 4, 8) per coordinate: per bucket of QSGD_BUCKET coordinates ``scales`` (fp32 [NB]) gets
+    d = n / s, n the bucket's ``norm`` ("max" or "l2") and s = 2^(bits - 1) - 1, and ``codes``
+    (int32 [NB * 16 * bits] holding uint32 words) the signed levels q in -s .. s, |u| / d
+    rounded up or down by the Philox word of the coordinate under (seed, stream_id), so that
+    q * d is u in expectation; stats (int32 [1]) becomes the number of non-finite u.  w, base:
+    fp32 vectors of at least P elements with unit stride; nothing is kept between calls.
+    Every tensor 16-byte aligned; the outputs overlap neither each other nor w or base.
+    Nothing is synchronised.  Returns (codes, scales)."""
+    fn = "qsgd_compress"
+    P, NB, words = _qsgd_extent(fn, P, bits)
+    if norm not in QSGD_NORMS:
+        raise RuntimeError(f"{fn}: norm={norm!r} must be one of {sorted(QSGD_NORMS)}")
+    _f32_vector(fn, "w", w, P)
+    _f32_vector(fn, "base", base, P)
+    _unit_vector(fn, "codes", codes, torch.int32, words)
+    _unit_vector(fn, "scales", scales, torch.float32, NB)
+    _unit_vector(fn, "stats", stats, torch.int32, 1)
+    seed, stream_id = _uint64(fn, "seed", seed), _uint64(fn, "stream_id", stream_id)
+    _check_same_device(fn, w, _anchor="w", base=base, codes=codes, scales=scales, stats=stats)
+    _check_disjoint({"w": w[:P], "base": base[:P], "codes": codes[:words], "scales": scales[:NB],
+                     "stats": stats[:1]}, f"{fn}: {{a}} and {{b}} overlap",
+                    allowed=lambda a, b: (a, b) == ("w", "base"))
+    _aligned16(fn, w=w, base=base, codes=codes, scales=scales, stats=stats)
+    for t in (w, base, codes, scales, stats):
+        _ptr(t)  # no CPU path
+    _check(lib().dls_qsgd_compress_f32(_ptr(w), _ptr(base), P, bits, QSGD_NORMS[norm], seed,
+                                       stream_id, _ptr(codes), _ptr(scales), _ptr(stats),
+                                       _stream(stream, w)),
+           "dls_qsgd_compress_f32")
+    return codes, scales
+
+
+def qsgd_fedavg(base, codes, scales, weight, total, P, bits, out, stream=None):
+    """FedAvg over K clients' quantized rows, added to ``base`` (dls_qsgd_fedavg_f32): codes
+    int32 [K, >= NB * 16 * bits] (uint32 words; the row pitch a multiple of 4) and scales fp32
+    [K, >= NB] with unit stride along a row; weight fp32 [K] = the n_i, total = their fp32 sum.
+    Per coordinate of bucket B the chain of fl32(q_i * fl32(fl32(d[i][B] * n_i) / N)) over the
+    clients in row order (the first assigns, the rest add) and out = fl32(base + acc) on the P
+    coordinates.  base, out: fp32 vectors of at least P elements, 16-byte aligned, not
+    overlapping.  Returns out."""
+    fn = "qsgd_fedavg"
+    P, NB, words = _qsgd_extent(fn, P, bits)
+    _f32_vector(fn, "base", base, P)
+    _f32_vector(fn, "out", out, P)
+    _check_tensor(fn, "weight", weight, torch.float32, 1, "a contiguous fp32 [K] tensor, K >= 1",
+                  exact=False, contiguous=False)
+    K = weight.numel()
+    for name, t, dtype, n in (("codes", codes, torch.int32, words),
+                              ("scales", scales, torch.float32, NB)):
+        if not (torch.is_tensor(t) and t.dtype == dtype and t.dim() == 2 and t.shape[0] == K
+                and t.shape[1] >= n and t.stride(1) == 1 and (K == 1 or t.stride(0) >= n)):
+            raise RuntimeError(f"{fn}: {name} must be an {_DTYPE_NAMES[dtype]} [K={K}, >= {n}] "
+                               "matrix with unit stride along its rows")
+    if _row_pitch(codes) % 4 != 0:
+        raise RuntimeError(f"{fn}: the row pitch of codes, {_row_pitch(codes)} words, must be a "
+                           "multiple of 4 (every row 16-byte aligned)")
+    total = fl32(total)
+    if not math.isfinite(total) or total <= 0.0:
+        raise RuntimeError(f"{fn}: total={total} must be a positive finite number")
+    _check_same_device(fn, base, _anchor="base", codes=codes, scales=scales, weight=weight, out=out)
+    if _overlaps(out[:P], base[:P]):
+        raise RuntimeError(f"{fn}: out and base overlap")
+    for name, t in (("codes", codes), ("scales", scales), ("weight", weight)):
+        if _overlaps(out[:P], t):
+            raise RuntimeError(f"{fn}: out and {name} overlap")
+    _aligned16(fn, base=base, out=out)
+    _aligned16(fn, codes=codes, scales=scales, weight=weight)
+    for t in (base, codes, scales, weight, out):
+        _ptr(t)  # no CPU path
+    _check(lib().dls_qsgd_fedavg_f32(_ptr(base), _ptr(codes), _row_pitch(codes), _ptr(scales),
+                                     _row_pitch(scales), _ptr(weight), total, K, P, bits,
+                                     _ptr(out), _stream(stream, base)),
+           "dls_qsgd_fedavg_f32")
     return out
 
 

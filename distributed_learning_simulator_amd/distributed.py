@@ -468,6 +468,10 @@ def get_sharded_server(algorithm, **kwargs):
         raise RuntimeError("fed_powersgd runs on the one-process server only (factory.get_server("
                            "'fed_powersgd', sharded=False, ...)): a sharded server over low-rank "
                            "payloads is not implemented")
+    if algorithm == "fed_qsgd":
+        raise RuntimeError("fed_qsgd runs on the one-process server only (factory.get_server("
+                           "'fed_qsgd', sharded=False, ...)): a sharded server over quantized "
+                           "payloads is not implemented")
     if algorithm not in table:
         raise RuntimeError("unknown algorithm:" + algorithm)
     return table[algorithm](**kwargs)

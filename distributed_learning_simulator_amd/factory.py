@@ -2,6 +2,7 @@
 from .servers.fed_drive_server import FedDriveServer
 from .servers.fed_efsign_server import FedEFSignServer
 from .servers.fed_powersgd_server import FedPowerSGDServer
+from .servers.fed_qsgd_server import FedQSGDServer
 from .servers.fed_quant_server import FedQuantServer
 from .servers.fed_secagg_server import FedSecAggServer
 from .servers.fed_sketch_server import FedSketchServer
@@ -14,6 +15,7 @@ from .servers.sign_sgd_server import SignSGDServer
 from .workers.fed_drive_worker import FedDriveWorker
 from .workers.fed_efsign_worker import FedEFSignWorker
 from .workers.fed_powersgd_worker import FedPowerSGDWorker
+from .workers.fed_qsgd_worker import FedQSGDWorker
 from .workers.fed_quant_worker import FedQuantWorker
 from .workers.fed_secagg_worker import FedSecAggWorker
 from .workers.fed_sketch_worker import FedSketchWorker
@@ -50,6 +52,8 @@ def get_server(algorithm, sharded=None, **kwargs) -> Server:
         return FedSketchServer(**kwargs)
     if algorithm == "fed_powersgd":
         return FedPowerSGDServer(**kwargs)
+    if algorithm == "fed_qsgd":
+        return FedQSGDServer(**kwargs)
     if algorithm == "multiround_shapley_value":
         return MultiRoundShapleyValueServer(**kwargs)
     if algorithm == "GTG_shapley_value":
@@ -74,6 +78,8 @@ def get_worker(algorithm, **kwargs) -> Worker:
         return FedSketchWorker(**kwargs)
     if algorithm == "fed_powersgd":
         return FedPowerSGDWorker(**kwargs)
+    if algorithm == "fed_qsgd":
+        return FedQSGDWorker(**kwargs)
     if algorithm in ("fed", "multiround_shapley_value", "GTG_shapley_value"):
         return FedWorker(**kwargs)
     raise RuntimeError("unknown algorithm:" + algorithm)

@@ -32,6 +32,8 @@
     python -m distributed_learning_simulator_amd.simulator --distributed_algorithm fed_powersgd \\
         --worker_number 10 --round 5 [--powersgd_rank 4] [--powersgd_seed 0] \\
         [--powersgd_warm_start 1] [--powersgd_error_feedback 1]
+    python -m distributed_learning_simulator_amd.simulator --distributed_algorithm fed_qsgd \\
+        --worker_number 10 --round 5 [--qsgd_bits 4] [--qsgd_norm l2|max] [--qsgd_seed 0]
 
 Same flags and flow as the reference: IID split of the training set over the
 workers (:48-50), a tester on the test split (:51), ``factory.get_server``
@@ -63,6 +65,7 @@ SKETCH_DEFAULTS = {"sketch_rows": 5, "sketch_cols": None, "sketch_ratio": 0.01,
                    "sketch_momentum": 0.9, "sketch_seed": 0}
 POWERSGD_DEFAULTS = {"powersgd_rank": 4, "powersgd_seed": 0, "powersgd_warm_start": 1,
                      "powersgd_error_feedback": 1}
+QSGD_DEFAULTS = {"qsgd_bits": 4, "qsgd_norm": "l2", "qsgd_seed": 0}
 # the fed_secagg flags and what they hold when not given (threshold None: a majority)
 SECAGG_FLAGS = {**{name: int(v) for name, v in SECAGG_DEFAULTS.items()},
                 "secagg_dropouts": (), "secagg_threshold": None}
@@ -189,6 +192,14 @@ def get_config(argv=None):
     ap.add_argument("--powersgd_seed", type=int, default=None)
     ap.add_argument("--powersgd_warm_start", type=int, default=None, choices=(0, 1))
     ap.add_argument("--powersgd_error_feedback", type=int, default=None, choices=(0, 1))
+    # fed_qsgd (QSGD / TernGrad): every worker sends a signed level of --qsgd_bits bits per
+    # coordinate of its update, rounded up or down at random so that the decode is unbiased (the
+    # library's Philox stream under --qsgd_seed, fresh per round and worker), and one scale per
+    # 512 coordinates from their --qsgd_norm (l2: QSGD's, max: TernGrad's at --qsgd_bits 2).  The
+    # workers keep nothing between rounds
+    ap.add_argument("--qsgd_bits", type=int, default=None, choices=(2, 4, 8))
+    ap.add_argument("--qsgd_norm", type=str, default=None, choices=("l2", "max"))
+    ap.add_argument("--qsgd_seed", type=int, default=None)
     # fed_secagg: every worker sends its update quantised to --secagg_bits bits with
     # --secagg_frac_bits fractional ones (defaults 20 and 16: +-8 at 1.5e-5) and masked in
     # Z_2^32 with the pair and self masks of the Philox stream under --secagg_seed;
@@ -253,6 +264,15 @@ def get_config(argv=None):
         ap.error("--powersgd_rank must lie in 1..16")
     if not 0 <= config.powersgd_seed < 1 << 64:
         ap.error("--powersgd_seed must lie in 0..2^64 - 1")
+    if config.distributed_algorithm != "fed_qsgd" and any(
+            getattr(config, name) is not None for name in QSGD_DEFAULTS):
+        ap.error("--qsgd_bits, --qsgd_norm and --qsgd_seed apply to --distributed_algorithm "
+                 "fed_qsgd alone")
+    for name, default in QSGD_DEFAULTS.items():
+        if getattr(config, name) is None:
+            setattr(config, name, default)
+    if not 0 <= config.qsgd_seed < 1 << 64:
+        ap.error("--qsgd_seed must lie in 0..2^64 - 1")
     if config.topk_ratio is None:
         config.topk_ratio = TOPK_DEFAULTS["topk_ratio"]
     if config.topk_error_feedback is None:
@@ -323,6 +343,8 @@ def server_kwargs(config):
         kwargs["momentum"] = getattr(config, "sketch_momentum", SKETCH_DEFAULTS["sketch_momentum"])
     if config.distributed_algorithm == "fed_powersgd":  # the rank the workers' payloads have
         kwargs["rank"] = getattr(config, "powersgd_rank", POWERSGD_DEFAULTS["powersgd_rank"])
+    if config.distributed_algorithm == "fed_qsgd":  # the width of the workers' codes
+        kwargs["bits"] = getattr(config, "qsgd_bits", QSGD_DEFAULTS["qsgd_bits"])
     return kwargs
 
 
@@ -337,7 +359,7 @@ def worker_kwargs(config):
     round / worker_id: the sparsifier's for fed_topk, the mask format, seed, weighting and
     the round's participants (every worker) for fed_secagg, the error-feedback switch for
     fed_efsign, the rotation's seed and the scale for fed_drive, the table's shape and the
-    hash's seed for fed_sketch, the rank, the seed and the two switches for fed_powersgd, none
+    hash's seed for fed_sketch, the code width, the norm and the seed for fed_qsgd, the rank, the seed and the two switches for fed_powersgd, none
     for the other algorithms."""
     if config.distributed_algorithm == "fed_powersgd":
         get = lambda name: getattr(config, "powersgd_" + name, POWERSGD_DEFAULTS["powersgd_" + name])
@@ -345,6 +367,9 @@ def worker_kwargs(config):
                 "error_feedback": bool(get("error_feedback"))}
     if config.distributed_algorithm == "fed_sketch":
         return _sketch_table(config)
+    if config.distributed_algorithm == "fed_qsgd":
+        return {name: getattr(config, "qsgd_" + name, QSGD_DEFAULTS["qsgd_" + name])
+                for name in ("bits", "norm", "seed")}
     if config.distributed_algorithm == "fed_drive":
         return {"seed": getattr(config, "drive_seed", DRIVE_DEFAULTS["drive_seed"]),
                 "scale": getattr(config, "drive_scale", DRIVE_DEFAULTS["drive_scale"])}

@@ -1115,6 +1115,75 @@ int dls_drive_fedavg_f32(const float *base, const uint64_t *bits, int64_t ldb, c
                          int64_t lds, const float *weight, float total, int32_t K, int64_t P,
                          uint64_t seed, uint64_t stream_id, float *out, dls_stream_t stream);
 
+/* Stochastic quantization (csrc/qsgd.hip; Alistarh et al. 2017, "QSGD: communication-efficient
+ * SGD via gradient quantization and encoding"; Wen et al. 2017, "TernGrad", its one-level
+ * max-norm case): an unbiased quantizer without client state and without anything the clients
+ * share.  Per bucket of coordinates the norm goes in fp32 and every coordinate as a signed level
+ * in -s .. s, rounded up or down at random so that the decode q * d is right in expectation.
+ * The reference simulator has no such compressor: the definitions below are this library's and
+ * tests/qsgd_ref.py restates them in numpy.
+ *
+ * Shape.  bits b in {2, 4, 8}; s = 2^(b-1) - 1 levels (1: ternary, 7, 127).  A row of P
+ * coordinates, 64 <= P < 2^31, P a multiple of 64, is cut into NB = ceil(P / DLS_QSGD_BUCKET)
+ * buckets of 512; a coordinate j >= P reads as +0.0, is coded 0 and is never written by the
+ * server.  Every fp32 operation below is rounded once and none is fused.
+ *
+ * dls_qsgd_compress_f32, the client's side: u[j] = fl(w[j] - base[j]).  Per bucket B the norm n:
+ *   DLS_QSGD_MAX  n = max |u[j]|, taken on the bit patterns of |u| as unsigned integers (exact
+ *                 in any order; a NaN in the bucket makes n a NaN, else an inf makes it inf)
+ *   DLS_QSGD_L2   n = (float)sqrt(S), S the fp64 sum of (double)u[j]^2 in an order that depends
+ *                 on j alone: lane l of 64 adds the squares of the bucket's coordinates 8 l ..
+ *                 8 l + 7 ascending, the 64 sums meet in the xor butterfly (distances 32, 16,
+ *                 .., 1), and the square root is taken in fp64, correctly rounded
+ *   r = fl((float)s / n), d = fl(n / (float)s), both correctly rounded;  scales[B] = d
+ *   n == 0 or n not finite: all codes of the bucket are 0 and scales[B] = d as computed (+0.0
+ *   or not finite).  Otherwise per coordinate
+ *     a = |u[j]|, t = fl(a * r), l0 = floor(t), f = t - l0 (exact)
+ *     xi = (word_j >> 8) * 2^-24, word_j dls_philox_u32's word of coordinate j under (seed,
+ *          stream_id)
+ *     l  = l0 + (xi < f), then s where l < s does not hold (so also where r overflowed to inf,
+ *          n < s / FLT_MAX: every coordinate of such a bucket is coded +-s, decoded +-n)
+ *     q  = -l where u[j] < 0 (a comparison: -0.0 and NaN give +l), else l
+ *   xi takes the 2^24 values k 2^-24 and ceil(f 2^24) of them lie below f: a level is rounded
+ *   up with probability f rounded up to the 2^-24 grid, not f itself (f == 0 never rounds up),
+ *   and the decode's expectation exceeds |u| by less than 2^-24 d.
+ *   codes   uint32 [NB * 16 * b]: the field of coordinate j is q & (2^b - 1) (two's complement;
+ *           -2^(b-1) never occurs) at bit (j % (32 / b)) * b of word j / (32 / b); all words of
+ *           the last bucket are written
+ *   stats   int32 [1]: stats[0] is set, not added to, to #{j < P : u[j] not finite} (the call
+ *           completes, the caller decides), through dls_drive_compress_f32's per-stream word
+ * One launch, no workspace, no floating-point atomics.  Traffic: 8 P + b P / 8 bytes.
+ *
+ * dls_qsgd_fedavg_f32, the server's side: FedAvg over K clients' code rows, added to the model
+ * the clients started from.  codes uint32 [K, ldc], ldc >= NB * 16 * b and a multiple of 4 (every
+ * row 16-byte aligned); scales fp32 [K, lds], lds >= NB; weight[i] = fl32(n_i), total =
+ * fl32(sum of the n_i).  Per bucket B:
+ *   c[i]   = fl(fl(scales[i][B] * weight[i]) / total), the correctly rounded division of
+ *            DLS_FEDAVG_EXACT
+ *   acc[j] = the chain over the clients i = 0..K-1 in the given order of p_i = fl((float)q_i *
+ *            c[i]): the first assigns, the later ones add with fp32 +
+ *   out[j] = fl(base[j] + acc[j]) for j < P
+ * K >= 1 without an upper limit (clients are walked in tiles of DLS_QSGD_CLIENT_TILE).  One
+ * launch, no atomics; one lane walks a coordinate's chain: the same bits for any launch
+ * geometry, HIP stream or pitch.  out must not overlap base.  Traffic: (K b / 8 + 8) P bytes and
+ * 4 K NB of scales.
+ *
+ * Checks, each before any device call, in this order: no null pointer; bits in {2, 4, 8}, norm
+ * one of the two, K >= 1, 64 <= P < 2^31 (DLS_EINVAL); P a multiple of 64, ldc and lds, every
+ * pointer 16-byte aligned (DLS_ELAYOUT); out against base, and for the compressor codes, scales
+ * and stats against w and base (DLS_EINVAL).  A failed check writes nothing.  Nothing is
+ * synchronised inside a call. */
+#define DLS_QSGD_BUCKET 512
+#define DLS_QSGD_CLIENT_TILE 64
+#define DLS_QSGD_MAX 0
+#define DLS_QSGD_L2 1
+int dls_qsgd_compress_f32(const float *w, const float *base, int64_t P, int32_t bits, int32_t norm,
+                          uint64_t seed, uint64_t stream_id, uint32_t *codes, float *scales,
+                          int32_t *stats, dls_stream_t stream);
+int dls_qsgd_fedavg_f32(const float *base, const uint32_t *codes, int64_t ldc, const float *scales,
+                        int64_t lds, const float *weight, float total, int32_t K, int64_t P,
+                        int32_t bits, float *out, dls_stream_t stream);
+
 /* FetchSGD's Count Sketch (csrc/sketch.hip; Rothchild et al. 2020, "FetchSGD: Communication-
  * Efficient Federated Learning with Sketching"): sparsification without client state.  A client
  * sends an R x C table, a linear function of its update, so the server averages tables, keeps
