@@ -94,6 +94,8 @@ SIGNATURES = {
                              _i32),
     "dls_qsgd_compress_f32": ([_p, _p, _i64, _i32, _i32, _u64, _u64, _p, _p, _p, _p], _i32),
     "dls_qsgd_fedavg_f32": ([_p, _p, _i64, _p, _i64, _p, _f32, _i32, _i64, _i32, _p, _p], _i32),
+    "dls_mx_compress_f32": ([_p, _p, _p, _i64, _i32, _i32, _u64, _u64, _p, _p, _p, _p], _i32),
+    "dls_mx_fedavg_f32": ([_p, _p, _i64, _p, _i64, _p, _f32, _i32, _i64, _i32, _p, _p], _i32),
     "dls_sketch_workspace": ([_i64, _i32, _i64], _i64),
     "dls_sketch_f32": ([_p, _p, _i64, _i32, _i64, _u64, _u64, _p, _p, _p, _p], _i32),
     "dls_unsketch_f32": ([_p, _i64, _i32, _i64, _u64, _u64, _p, _p], _i32),
@@ -222,6 +224,7 @@ CSRC_HASHED = [  # the Makefile's HASHED, in its order
     "sketch.hip",
     "powersgd.hip",
     "qsgd.hip",
+    "mx.hip",
     "topk.hip",
     "dpnoise.hip",
     "dls_common.h",
@@ -272,7 +275,7 @@ def fedavg(U, rows, weight, total, P, out, mode=FEDAVG_EXACT, stream=None):
 # The rows family (trimmed mean .. centered clip) and the vector calls after it state
 # their operand contract with these; the library checks it again (csrc/rows_common.h).
 _DTYPE_NAMES = {torch.float32: "fp32", torch.float64: "fp64", torch.int32: "int32",
-                torch.int64: "int64"}
+                torch.int64: "int64", torch.uint8: "uint8"}
 
 
 def _check_tensor(fn, name, t, dtype, n, what, exact=True, contiguous=True, device=None):
@@ -1361,6 +1364,127 @@ def qsgd_fedavg(base, codes, scales, weight, total, P, bits, out, stream=None):
                                      _row_pitch(scales), _ptr(weight), total, K, P, bits,
                                      _ptr(out), _stream(stream, base)),
            "dls_qsgd_fedavg_f32")
+    return out
+
+
+# ------------------------------------------ OCP microscaling FP8 / FP4 (MX)
+# DLS_MX_* (include/dls_hip.h)
+MX_BLOCK = 32  # coordinates per scale byte
+MX_GROUP = 512  # coordinates per wave: the rows' padding unit
+MX_CLIENT_TILE = 64  # clients per tile of dls_mx_fedavg_f32
+MX_FORMATS = {"e4m3": 0, "e5m2": 1, "e2m1": 2}  # DLS_MX_E4M3, DLS_MX_E5M2, DLS_MX_E2M1
+MX_ROUNDINGS = {"nearest": 0, "stochastic": 1}  # DLS_MX_NEAREST, DLS_MX_STOCHASTIC
+
+
+def mx_code_bits(format):
+    """Bits per coordinate of a format's codes."""
+    if format not in MX_FORMATS:
+        raise RuntimeError(f"mx_code_bits: format={format!r} must be one of {sorted(MX_FORMATS)}")
+    return 4 if format == "e2m1" else 8
+
+
+def mx_code_words(P, format):
+    """The uint32 words of a client's code row: whole groups of 512 coordinates."""
+    return -(-int(P) // MX_GROUP) * 16 * mx_code_bits(format)
+
+
+def mx_scale_bytes(P):
+    """The bytes of a client's scale row: one per block, 16 per group of 512 coordinates."""
+    return -(-int(P) // MX_GROUP) * 16
+
+
+def _mx_extent(fn, P, format):
+    P = int(P)
+    if format not in MX_FORMATS:
+        raise RuntimeError(f"{fn}: format={format!r} must be one of {sorted(MX_FORMATS)}")
+    if not 64 <= P < 1 << 31 or P % 64 != 0:
+        raise RuntimeError(f"{fn}: P={P} must be a multiple of 64 in 64..2^31 - 64")
+    return P, mx_code_words(P, format), mx_scale_bytes(P)
+
+
+def mx_compress(w, base, residual, P, format, rounding, seed, stream_id, codes, scales, stats,
+                stream=None):
+    """MX compression (dls_mx_compress_f32) of u = fl32(w - base), with ``residual`` (fp32 [P] or
+    None) of u = fl32(fl32(w - base) + residual): per block of MX_BLOCK coordinates ``scales``
+    (uint8 [16 NG]) gets the E8M0 byte e + 127 of the least power of two with max |u| <= fmax
+    2^e, and ``codes`` (int32 holding uint32 words, mx_code_words of them) the ``format``
+    ("e4m3", "e5m2", "e2m1") code of u 2^-e under ``rounding``: "nearest" (ties to the even code;
+    seed and stream_id are not read) or "stochastic" (up where the Philox word of the coordinate
+    under (seed, stream_id) lies below the fraction, unbiased).  The residual becomes u - decode,
+    the decode being exact.  stats (int32 [1]) becomes the number of non-finite u; their blocks
+    carry scale byte 255 and zero codes.  Every tensor 16-byte aligned; the outputs overlap
+    neither each other nor the inputs.  Nothing is synchronised.  Returns (codes, scales)."""
+    fn = "mx_compress"
+    P, words, sbytes = _mx_extent(fn, P, format)
+    if rounding not in MX_ROUNDINGS:
+        raise RuntimeError(f"{fn}: rounding={rounding!r} must be one of {sorted(MX_ROUNDINGS)}")
+    _f32_vector(fn, "w", w, P)
+    _f32_vector(fn, "base", base, P)
+    if residual is not None:
+        _f32_vector(fn, "residual", residual, P)
+    _unit_vector(fn, "codes", codes, torch.int32, words)
+    _unit_vector(fn, "scales", scales, torch.uint8, sbytes)
+    _unit_vector(fn, "stats", stats, torch.int32, 1)
+    seed, stream_id = _uint64(fn, "seed", seed), _uint64(fn, "stream_id", stream_id)
+    named = {"w": w[:P], "base": base[:P], "codes": codes[:words], "scales": scales[:sbytes],
+             "stats": stats[:1]}
+    if residual is not None:
+        named["residual"] = residual[:P]
+    _check_same_device(fn, w, _anchor="w", **{k: v for k, v in named.items() if k != "w"})
+    _check_disjoint(named, f"{fn}: {{a}} and {{b}} overlap",
+                    allowed=lambda a, b: (a, b) == ("w", "base"))
+    _aligned16(fn, w=w, base=base, residual=residual, codes=codes, scales=scales, stats=stats)
+    for t in named.values():
+        _ptr(t)  # no CPU path
+    _check(lib().dls_mx_compress_f32(_ptr(w), _ptr(base),
+                                     None if residual is None else _ptr(residual), P,
+                                     MX_FORMATS[format], MX_ROUNDINGS[rounding], seed, stream_id,
+                                     _ptr(codes), _ptr(scales), _ptr(stats), _stream(stream, w)),
+           "dls_mx_compress_f32")
+    return codes, scales
+
+
+def mx_fedavg(base, codes, scales, weight, total, P, format, out, stream=None):
+    """FedAvg over K clients' MX rows, added to ``base`` (dls_mx_fedavg_f32): codes int32 [K, >=
+    mx_code_words] (uint32 words; the row pitch a multiple of 4) and scales uint8 [K, >=
+    mx_scale_bytes] (the row pitch a multiple of 16) with unit stride along a row; weight fp32
+    [K] = the n_i, total = their fp32 sum.  Per coordinate the chain of fl32(x_i * fl32(n_i /
+    N)), x_i the exact decode, over the clients in row order (the first assigns, the rest add)
+    and out = fl32(base + acc) on the P coordinates.  base, out: fp32 vectors of at least P
+    elements, 16-byte aligned, not overlapping.  Returns out."""
+    fn = "mx_fedavg"
+    P, words, sbytes = _mx_extent(fn, P, format)
+    _f32_vector(fn, "base", base, P)
+    _f32_vector(fn, "out", out, P)
+    _check_tensor(fn, "weight", weight, torch.float32, 1, "a contiguous fp32 [K] tensor, K >= 1",
+                  exact=False, contiguous=False)
+    K = weight.numel()
+    for name, t, dtype, n, unit in (("codes", codes, torch.int32, words, 4),
+                                    ("scales", scales, torch.uint8, sbytes, 16)):
+        if not (torch.is_tensor(t) and t.dtype == dtype and t.dim() == 2 and t.shape[0] == K
+                and t.shape[1] >= n and t.stride(1) == 1 and (K == 1 or t.stride(0) >= n)):
+            raise RuntimeError(f"{fn}: {name} must be an {_DTYPE_NAMES[dtype]} [K={K}, >= {n}] "
+                               "matrix with unit stride along its rows")
+        if _row_pitch(t) % unit != 0:
+            raise RuntimeError(f"{fn}: the row pitch of {name}, {_row_pitch(t)} elements, must be "
+                               f"a multiple of {unit} (every row 16-byte aligned)")
+    total = fl32(total)
+    if not math.isfinite(total) or total <= 0.0:
+        raise RuntimeError(f"{fn}: total={total} must be a positive finite number")
+    _check_same_device(fn, base, _anchor="base", codes=codes, scales=scales, weight=weight, out=out)
+    if _overlaps(out[:P], base[:P]):
+        raise RuntimeError(f"{fn}: out and base overlap")
+    for name, t in (("codes", codes), ("scales", scales), ("weight", weight)):
+        if _overlaps(out[:P], t):
+            raise RuntimeError(f"{fn}: out and {name} overlap")
+    _aligned16(fn, base=base, out=out)
+    _aligned16(fn, codes=codes, scales=scales, weight=weight)
+    for t in (base, codes, scales, weight, out):
+        _ptr(t)  # no CPU path
+    _check(lib().dls_mx_fedavg_f32(_ptr(base), _ptr(codes), _row_pitch(codes), _ptr(scales),
+                                   _row_pitch(scales), _ptr(weight), total, K, P,
+                                   MX_FORMATS[format], _ptr(out), _stream(stream, base)),
+           "dls_mx_fedavg_f32")
     return out
 
 

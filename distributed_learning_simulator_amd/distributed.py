@@ -472,6 +472,10 @@ def get_sharded_server(algorithm, **kwargs):
         raise RuntimeError("fed_qsgd runs on the one-process server only (factory.get_server("
                            "'fed_qsgd', sharded=False, ...)): a sharded server over quantized "
                            "payloads is not implemented")
+    if algorithm == "fed_mx":
+        raise RuntimeError("fed_mx runs on the one-process server only (factory.get_server("
+                           "'fed_mx', sharded=False, ...)): a sharded server over microscaling "
+                           "payloads is not implemented")
     if algorithm not in table:
         raise RuntimeError("unknown algorithm:" + algorithm)
     return table[algorithm](**kwargs)

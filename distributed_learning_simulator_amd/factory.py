@@ -1,6 +1,7 @@
 """Plugin factory (reference: factory.py:14-35) — same algorithm names and errors."""
 from .servers.fed_drive_server import FedDriveServer
 from .servers.fed_efsign_server import FedEFSignServer
+from .servers.fed_mx_server import FedMXServer
 from .servers.fed_powersgd_server import FedPowerSGDServer
 from .servers.fed_qsgd_server import FedQSGDServer
 from .servers.fed_quant_server import FedQuantServer
@@ -14,6 +15,7 @@ from .servers.server import Server
 from .servers.sign_sgd_server import SignSGDServer
 from .workers.fed_drive_worker import FedDriveWorker
 from .workers.fed_efsign_worker import FedEFSignWorker
+from .workers.fed_mx_worker import FedMXWorker
 from .workers.fed_powersgd_worker import FedPowerSGDWorker
 from .workers.fed_qsgd_worker import FedQSGDWorker
 from .workers.fed_quant_worker import FedQuantWorker
@@ -54,6 +56,8 @@ def get_server(algorithm, sharded=None, **kwargs) -> Server:
         return FedPowerSGDServer(**kwargs)
     if algorithm == "fed_qsgd":
         return FedQSGDServer(**kwargs)
+    if algorithm == "fed_mx":
+        return FedMXServer(**kwargs)
     if algorithm == "multiround_shapley_value":
         return MultiRoundShapleyValueServer(**kwargs)
     if algorithm == "GTG_shapley_value":
@@ -80,6 +84,8 @@ def get_worker(algorithm, **kwargs) -> Worker:
         return FedPowerSGDWorker(**kwargs)
     if algorithm == "fed_qsgd":
         return FedQSGDWorker(**kwargs)
+    if algorithm == "fed_mx":
+        return FedMXWorker(**kwargs)
     if algorithm in ("fed", "multiround_shapley_value", "GTG_shapley_value"):
         return FedWorker(**kwargs)
     raise RuntimeError("unknown algorithm:" + algorithm)

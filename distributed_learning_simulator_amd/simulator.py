@@ -34,6 +34,9 @@
         [--powersgd_warm_start 1] [--powersgd_error_feedback 1]
     python -m distributed_learning_simulator_amd.simulator --distributed_algorithm fed_qsgd \\
         --worker_number 10 --round 5 [--qsgd_bits 4] [--qsgd_norm l2|max] [--qsgd_seed 0]
+    python -m distributed_learning_simulator_amd.simulator --distributed_algorithm fed_mx \\
+        --worker_number 10 --round 5 [--mx_format e4m3|e5m2|e2m1] \\
+        [--mx_rounding nearest|stochastic] [--mx_error_feedback 0|1] [--mx_seed 0]
 
 Same flags and flow as the reference: IID split of the training set over the
 workers (:48-50), a tester on the test split (:51), ``factory.get_server``
@@ -66,6 +69,9 @@ SKETCH_DEFAULTS = {"sketch_rows": 5, "sketch_cols": None, "sketch_ratio": 0.01,
 POWERSGD_DEFAULTS = {"powersgd_rank": 4, "powersgd_seed": 0, "powersgd_warm_start": 1,
                      "powersgd_error_feedback": 1}
 QSGD_DEFAULTS = {"qsgd_bits": 4, "qsgd_norm": "l2", "qsgd_seed": 0}
+# mx_error_feedback None: on for nearest rounding, off for stochastic
+MX_DEFAULTS = {"mx_format": "e4m3", "mx_rounding": "nearest", "mx_error_feedback": None,
+               "mx_seed": 0}
 # the fed_secagg flags and what they hold when not given (threshold None: a majority)
 SECAGG_FLAGS = {**{name: int(v) for name, v in SECAGG_DEFAULTS.items()},
                 "secagg_dropouts": (), "secagg_threshold": None}
@@ -200,6 +206,15 @@ def get_config(argv=None):
     ap.add_argument("--qsgd_bits", type=int, default=None, choices=(2, 4, 8))
     ap.add_argument("--qsgd_norm", type=str, default=None, choices=("l2", "max"))
     ap.add_argument("--qsgd_seed", type=int, default=None)
+    # fed_mx (OCP microscaling): every worker sends an --mx_format code per coordinate of its
+    # update and one power-of-two scale byte per 32 coordinates; --mx_rounding nearest is
+    # deterministic and keeps a residual (--mx_error_feedback, default 1), stochastic is unbiased
+    # (the library's Philox stream under --mx_seed, fresh per round and worker) and keeps none
+    # (default 0)
+    ap.add_argument("--mx_format", type=str, default=None, choices=("e4m3", "e5m2", "e2m1"))
+    ap.add_argument("--mx_rounding", type=str, default=None, choices=("nearest", "stochastic"))
+    ap.add_argument("--mx_error_feedback", type=int, default=None, choices=(0, 1))
+    ap.add_argument("--mx_seed", type=int, default=None)
     # fed_secagg: every worker sends its update quantised to --secagg_bits bits with
     # --secagg_frac_bits fractional ones (defaults 20 and 16: +-8 at 1.5e-5) and masked in
     # Z_2^32 with the pair and self masks of the Philox stream under --secagg_seed;
@@ -273,6 +288,15 @@ def get_config(argv=None):
             setattr(config, name, default)
     if not 0 <= config.qsgd_seed < 1 << 64:
         ap.error("--qsgd_seed must lie in 0..2^64 - 1")
+    if config.distributed_algorithm != "fed_mx" and any(
+            getattr(config, name) is not None for name in MX_DEFAULTS):
+        ap.error("--mx_format, --mx_rounding, --mx_error_feedback and --mx_seed apply to "
+                 "--distributed_algorithm fed_mx alone")
+    for name, default in MX_DEFAULTS.items():
+        if getattr(config, name) is None:
+            setattr(config, name, default)
+    if not 0 <= config.mx_seed < 1 << 64:
+        ap.error("--mx_seed must lie in 0..2^64 - 1")
     if config.topk_ratio is None:
         config.topk_ratio = TOPK_DEFAULTS["topk_ratio"]
     if config.topk_error_feedback is None:
@@ -345,6 +369,8 @@ def server_kwargs(config):
         kwargs["rank"] = getattr(config, "powersgd_rank", POWERSGD_DEFAULTS["powersgd_rank"])
     if config.distributed_algorithm == "fed_qsgd":  # the width of the workers' codes
         kwargs["bits"] = getattr(config, "qsgd_bits", QSGD_DEFAULTS["qsgd_bits"])
+    if config.distributed_algorithm == "fed_mx":  # the element format of the workers' codes
+        kwargs["format"] = getattr(config, "mx_format", MX_DEFAULTS["mx_format"])
     return kwargs
 
 
@@ -359,7 +385,8 @@ def worker_kwargs(config):
     round / worker_id: the sparsifier's for fed_topk, the mask format, seed, weighting and
     the round's participants (every worker) for fed_secagg, the error-feedback switch for
     fed_efsign, the rotation's seed and the scale for fed_drive, the table's shape and the
-    hash's seed for fed_sketch, the code width, the norm and the seed for fed_qsgd, the rank, the seed and the two switches for fed_powersgd, none
+    hash's seed for fed_sketch, the code width, the norm and the seed for fed_qsgd,
+    the element format, the rounding, the error-feedback switch and the seed for fed_mx, the rank, the seed and the two switches for fed_powersgd, none
     for the other algorithms."""
     if config.distributed_algorithm == "fed_powersgd":
         get = lambda name: getattr(config, "powersgd_" + name, POWERSGD_DEFAULTS["powersgd_" + name])
@@ -370,6 +397,11 @@ def worker_kwargs(config):
     if config.distributed_algorithm == "fed_qsgd":
         return {name: getattr(config, "qsgd_" + name, QSGD_DEFAULTS["qsgd_" + name])
                 for name in ("bits", "norm", "seed")}
+    if config.distributed_algorithm == "fed_mx":
+        get = lambda name: getattr(config, "mx_" + name, MX_DEFAULTS["mx_" + name])
+        feedback = get("error_feedback")
+        return {"format": get("format"), "rounding": get("rounding"), "seed": get("seed"),
+                "error_feedback": None if feedback is None else bool(feedback)}
     if config.distributed_algorithm == "fed_drive":
         return {"seed": getattr(config, "drive_seed", DRIVE_DEFAULTS["drive_seed"]),
                 "scale": getattr(config, "drive_scale", DRIVE_DEFAULTS["drive_scale"])}

@@ -1184,6 +1184,90 @@ int dls_qsgd_fedavg_f32(const float *base, const uint32_t *codes, int64_t ldc, c
                         int64_t lds, const float *weight, float total, int32_t K, int64_t P,
                         int32_t bits, float *out, dls_stream_t stream);
 
+/* OCP Microscaling (MX) update compression (csrc/mx.hip; Rouhani et al. 2023, "Microscaling Data
+ * Formats for Deep Learning"; the OCP MX v1.0 specification; Wang et al. 2024, "Towards Federated
+ * Learning with On-device Training and Communication in 8-bit Floating Point"): a narrow
+ * floating-point payload, one power-of-two scale per block of 32 coordinates.  The reference
+ * simulator has no such compressor: the definitions below are this library's and
+ * tests/mx_ref.py restates them in numpy.
+ *
+ * Element formats (OCP encodings: sign, exponent field, M mantissa bits, no infinities used):
+ *   DLS_MX_E4M3  M = 3, bias 7,  emax 8,  fmax 448,   least normal 2^-6,  below it multiples of 2^-9
+ *   DLS_MX_E5M2  M = 2, bias 15, emax 15, fmax 57344, least normal 2^-14, below it multiples of 2^-16
+ *   DLS_MX_E2M1  M = 1, bias 1,  emax 2,  fmax 6,     the grid 0, 0.5, 1, 1.5, 2, 3, 4, 6
+ * E4M3 and E5M2 take a byte per coordinate, E2M1 four bits.  The grid step q at a real t >= 0 is
+ * 2^(max(floor(log2 t), emin) - M), emin the least normal's exponent.
+ *
+ * Shape.  A row of P coordinates, 64 <= P < 2^31, P a multiple of 64, is cut into blocks of
+ * DLS_MX_BLOCK = 32 and groups of DLS_MX_GROUP = 512, NG = ceil(P / 512); a coordinate j >= P
+ * reads as +0.0, is coded 0 and is never written by the server.  Every fp32 operation below is
+ * rounded once and none is fused.
+ *
+ * dls_mx_compress_f32, the client's side.  u[j] = fl(w[j] - base[j]); with a residual r
+ * (nullable: null means it is neither read nor written) u[j] = fl(fl(w[j] - base[j]) + r[j]).
+ * Per block, with m the largest |u[j]| (taken on the bit patterns as unsigned integers):
+ *   e     the least integer in [-127, 127] with m <= fmax 2^e: exponent field of m - 127 - emax,
+ *         plus one where m's mantissa field exceeds fmax's, then -127 where that is less (every
+ *         denormal m and m == 0).  Nothing saturates; the OCP floor rule, which would clamp
+ *         (fmax, 2^(emax+1)) 2^e, is not used
+ *   scale byte = e + 127 (E8M0), in 0 .. 254
+ *   a block holding a NaN or an infinity: scale byte 255, all codes 0, dec = 0 below
+ * Per coordinate t = |u[j]| 2^-e as a real number, l0 the grid point at or below t, q the step
+ * there, f = (t - l0) / q in [0, 1):
+ *   DLS_MX_NEAREST     up where f > 1/2, or f == 1/2 and l0's code is odd (ties to the even code)
+ *   DLS_MX_STOCHASTIC  up exactly where xi < f as real numbers, xi = (word_j >> 8) 2^-24, word_j
+ *                      dls_philox_u32's word of coordinate j under (seed, stream_id): the
+ *                      convention of dls_qsgd_compress_f32.  f is exact, also where fp32 could
+ *                      not hold it: any f in (0, 2^-24) rounds up exactly when xi == 0
+ *   code  = sign bit of u[j] (also for zeros: -0.0 and a negative u rounded to zero give the
+ *           negative zero code) above the magnitude's OCP encoding; seed and stream_id are not
+ *           read under DLS_MX_NEAREST
+ *   dec   = code 2^e, exact in fp32 (where |u| is within half a step of 2^128 it is +-inf)
+ *   r'[j] = fl(u[j] - dec[j]) for j < P, written over r[j]; u[j] itself in a non-finite block
+ * codes   uint32 [NG * 128] (8-bit formats: code j is byte j) or [NG * 64] (E2M1: code j is
+ *         nibble j & 1 of byte j >> 1, the low nibble the even coordinate), little endian; all
+ *         words of the last group are written
+ * scales  uint8 [NG * 16], one byte per block, all bytes of the last group written (0 past P)
+ * stats   int32 [1]: stats[0] is set, not added to, to #{j < P : u[j] not finite} (the call
+ *         completes, the caller decides), through dls_drive_compress_f32's per-stream word
+ * One launch, no workspace, no floating-point atomics.  Traffic: 8 P + b P / 8 + P / 32 bytes,
+ * 8 P more with a residual.
+ *
+ * dls_mx_fedavg_f32, the server's side: FedAvg over K clients' code rows, added to the model the
+ * clients started from.  codes uint32 [K, ldc], ldc in words, at least the row's and a multiple
+ * of 4; scales uint8 [K, lds], lds in bytes, at least 16 NG and a multiple of 16; weight[i] =
+ * fl32(n_i), total = fl32(sum of the n_i).
+ *   c[i]   = fl(weight[i] / total), the correctly rounded division of DLS_FEDAVG_EXACT
+ *   x_i[j] = code 2^e, exact
+ *   acc[j] = the chain over the clients i = 0..K-1 in the given order of fl(x_i[j] * c[i]): the
+ *            first assigns, the later ones add with fp32 +
+ *   out[j] = fl(base[j] + acc[j]) for j < P
+ * Outside the contract: scale byte 255 and the code patterns the compressor never emits (E4M3's
+ * S.1111.111, E5M2's exponent field 31).  K >= 1 without an upper limit (clients are walked in
+ * tiles of DLS_MX_CLIENT_TILE).  One launch, no atomics; one lane walks a coordinate's chain: the
+ * same bits for any launch geometry, HIP stream or pitch.  out must not overlap base.  Traffic:
+ * (K (b / 8 + 1 / 32) + 8) P bytes.
+ *
+ * Checks, each before any device call, in this order: no null pointer (but residual); format one
+ * of the three, rounding one of the two, K >= 1, 64 <= P < 2^31 (DLS_EINVAL); P a multiple of 64,
+ * ldc and lds, every pointer 16-byte aligned (DLS_ELAYOUT); out against base, and for the
+ * compressor codes, scales and stats against w, base and residual, residual against w and base
+ * (DLS_EINVAL).  A failed check writes nothing.  Nothing is synchronised inside a call. */
+#define DLS_MX_BLOCK 32
+#define DLS_MX_GROUP 512
+#define DLS_MX_CLIENT_TILE 64
+#define DLS_MX_E4M3 0
+#define DLS_MX_E5M2 1
+#define DLS_MX_E2M1 2
+#define DLS_MX_NEAREST 0
+#define DLS_MX_STOCHASTIC 1
+int dls_mx_compress_f32(const float *w, const float *base, float *residual, int64_t P,
+                        int32_t format, int32_t rounding, uint64_t seed, uint64_t stream_id,
+                        uint32_t *codes, uint8_t *scales, int32_t *stats, dls_stream_t stream);
+int dls_mx_fedavg_f32(const float *base, const uint32_t *codes, int64_t ldc, const uint8_t *scales,
+                      int64_t lds, const float *weight, float total, int32_t K, int64_t P,
+                      int32_t format, float *out, dls_stream_t stream);
+
 /* FetchSGD's Count Sketch (csrc/sketch.hip; Rothchild et al. 2020, "FetchSGD: Communication-
  * Efficient Federated Learning with Sketching"): sparsification without client state.  A client
  * sends an R x C table, a linear function of its update, so the server averages tables, keeps
