@@ -92,6 +92,9 @@ SIGNATURES = {
     "dls_drive_compress_f32": ([_p, _p, _i64, _u64, _u64, _i32, _p, _p, _p, _p], _i32),
     "dls_drive_fedavg_f32": ([_p, _p, _i64, _p, _i64, _p, _f32, _i32, _i64, _u64, _u64, _p, _p],
                              _i32),
+    "dls_eden_compress_f32": ([_p, _p, _i64, _i32, _u64, _u64, _i32, _p, _p, _p, _p], _i32),
+    "dls_eden_fedavg_f32": ([_p, _p, _i64, _p, _i64, _p, _f32, _i32, _i64, _i32, _u64, _u64, _p,
+                             _p], _i32),
     "dls_qsgd_compress_f32": ([_p, _p, _i64, _i32, _i32, _u64, _u64, _p, _p, _p, _p], _i32),
     "dls_qsgd_fedavg_f32": ([_p, _p, _i64, _p, _i64, _p, _f32, _i32, _i64, _i32, _p, _p], _i32),
     "dls_mx_compress_f32": ([_p, _p, _p, _i64, _i32, _i32, _u64, _u64, _p, _p, _p, _p], _i32),
@@ -225,6 +228,7 @@ CSRC_HASHED = [  # the Makefile's HASHED, in its order
     "powersgd.hip",
     "qsgd.hip",
     "mx.hip",
+    "eden.hip",
     "topk.hip",
     "dpnoise.hip",
     "dls_common.h",
@@ -233,6 +237,7 @@ CSRC_HASHED = [  # the Makefile's HASHED, in its order
     "sign_geometry.h",
     "rows_common.h",
     "philox_common.h",
+    "hadamard_common.h",
     os.path.join("..", "..", "include", "dls_hip.h"),
 ]
 
@@ -1257,6 +1262,111 @@ def drive_fedavg(base, bits, scales, weight, total, P, seed, stream_id, out, str
                                       _row_pitch(scales), _ptr(weight), total, K, P, seed,
                                       stream_id, _ptr(out), _stream(stream, base)),
            "dls_drive_fedavg_f32")
+    return out
+
+
+# ----------------------------------------------- multi-bit rotated compression (EDEN)
+# DLS_EDEN_* (include/dls_hip.h); the tables are tools/eden_tables.py's output
+EDEN_CLIENT_TILE = 64  # clients per tile of dls_eden_fedavg_f32
+EDEN_BITS = (2, 4)
+EDEN_SCALES = {"unbiased": 0, "mse": 1}  # DLS_EDEN_UNBIASED, DLS_EDEN_MSE
+EDEN_CENTROIDS = {2: (0.4527800381183624, 1.5104175806045532),
+                  4: (0.12839503586292267, 0.38804829120635986, 0.6567591428756714,
+                      0.9423404335975647, 1.2562311887741089, 1.6180464029312134,
+                      2.069017171859741, 2.7325894832611084)}
+EDEN_BOUNDS = {2: (0.9815987944602966,),
+               4: (0.25822165608406067, 0.5224037170410156, 0.7995497584342957,
+                   1.0992858409881592, 1.4371387958526611, 1.843531847000122, 2.400803327560425)}
+
+
+def eden_code_words(P, bits):
+    """The uint32 words of a client's code row: NB * 128 * bits, the last block whole."""
+    if isinstance(bits, bool) or bits not in EDEN_BITS:
+        raise RuntimeError(f"eden_code_words: bits={bits!r} must be one of {EDEN_BITS}")
+    return drive_blocks(P) * (DRIVE_BLOCK // 32) * bits
+
+
+def _eden_extent(fn, P, bits):
+    if isinstance(bits, bool) or bits not in EDEN_BITS:
+        raise RuntimeError(f"{fn}: bits={bits!r} must be one of {EDEN_BITS}")
+    P, NB = _drive_extent(fn, P)
+    return P, NB, eden_code_words(P, bits)
+
+
+def eden_compress(w, base, P, bits, seed, stream_id, scale, codes, scales, stats, stream=None):
+    """Multi-bit rotated compression (dls_eden_compress_f32) at ``bits`` in (2, 4): with y the
+    forward rotation (``hadamard_rotate``) of u = fl32(w - base) under (seed, stream_id), per
+    block of DRIVE_BLOCK coordinates every y[j] goes as its sign and the index of the nearest
+    Lloyd-Max magnitude EDEN_CENTROIDS[bits][m] times the block's root mean square (``codes``,
+    int32 [NB * 128 * bits] holding uint32 words in the layout the header gives), and ``scales``
+    (fp32 [NB]) holds sum y^2 / sum |y| cent (``scale`` "unbiased") or sum |y| cent / sum cent^2
+    ("mse"), the sums in fp64; stats (int32 [1]) becomes the number of non-finite u.  w, base:
+    fp32 vectors of at least P elements with unit stride; nothing is kept between calls.
+    Every tensor 16-byte aligned; the outputs overlap neither each other nor w or base.
+    Nothing is synchronised.  Returns (codes, scales)."""
+    fn = "eden_compress"
+    P, NB, words = _eden_extent(fn, P, bits)
+    if scale not in EDEN_SCALES:
+        raise RuntimeError(f"{fn}: scale={scale!r} must be one of {sorted(EDEN_SCALES)}")
+    _f32_vector(fn, "w", w, P)
+    _f32_vector(fn, "base", base, P)
+    _unit_vector(fn, "codes", codes, torch.int32, words)
+    _unit_vector(fn, "scales", scales, torch.float32, NB)
+    _unit_vector(fn, "stats", stats, torch.int32, 1)
+    seed, stream_id = _drive_rotation(fn, seed, stream_id)
+    _check_same_device(fn, w, _anchor="w", base=base, codes=codes, scales=scales, stats=stats)
+    _check_disjoint({"w": w[:P], "base": base[:P], "codes": codes[:words], "scales": scales[:NB],
+                     "stats": stats[:1]}, f"{fn}: {{a}} and {{b}} overlap",
+                    allowed=lambda a, b: (a, b) == ("w", "base"))
+    _aligned16(fn, w=w, base=base, codes=codes, scales=scales, stats=stats)
+    for t in (w, base, codes, scales, stats):
+        _ptr(t)  # no CPU path
+    _check(lib().dls_eden_compress_f32(_ptr(w), _ptr(base), P, bits, seed, stream_id,
+                                       EDEN_SCALES[scale], _ptr(codes), _ptr(scales), _ptr(stats),
+                                       _stream(stream, w)),
+           "dls_eden_compress_f32")
+    return codes, scales
+
+
+def eden_fedavg(base, codes, scales, weight, total, P, bits, seed, stream_id, out, stream=None):
+    """FedAvg over K clients' rotated code rows, rotated back and added to ``base``
+    (dls_eden_fedavg_f32): codes int32 [K, >= NB * 128 * bits] (uint32 words) and scales fp32 [K,
+    >= NB] with unit stride along a row; weight fp32 [K] = the n_i, total = their fp32 sum.  Per
+    rotated coordinate of block B the chain of +-fl32(c_i * cent[m]), c_i = fl32(fl32(s[i][B] *
+    n_i) / N), over the clients in row order (the first assigns, the rest add), then one inverse
+    rotation under (seed, stream_id) and out = fl32(base + v) on the P coordinates.  base, out:
+    fp32 vectors of at least P elements, 16-byte aligned, not overlapping.  Returns out."""
+    fn = "eden_fedavg"
+    P, NB, words = _eden_extent(fn, P, bits)
+    _f32_vector(fn, "base", base, P)
+    _f32_vector(fn, "out", out, P)
+    _check_tensor(fn, "weight", weight, torch.float32, 1, "a contiguous fp32 [K] tensor, K >= 1",
+                  exact=False, contiguous=False)
+    K = weight.numel()
+    for name, t, dtype, n in (("codes", codes, torch.int32, words),
+                              ("scales", scales, torch.float32, NB)):
+        if not (torch.is_tensor(t) and t.dtype == dtype and t.dim() == 2 and t.shape[0] == K
+                and t.shape[1] >= n and t.stride(1) == 1 and (K == 1 or t.stride(0) >= n)):
+            raise RuntimeError(f"{fn}: {name} must be an {_DTYPE_NAMES[dtype]} [K={K}, >= {n}] "
+                               "matrix with unit stride along its rows")
+    total = fl32(total)
+    if not math.isfinite(total) or total <= 0.0:
+        raise RuntimeError(f"{fn}: total={total} must be a positive finite number")
+    seed, stream_id = _drive_rotation(fn, seed, stream_id)
+    _check_same_device(fn, base, _anchor="base", codes=codes, scales=scales, weight=weight, out=out)
+    if _overlaps(out[:P], base[:P]):
+        raise RuntimeError(f"{fn}: out and base overlap")
+    for name, t in (("codes", codes), ("scales", scales), ("weight", weight)):
+        if _overlaps(out[:P], t):
+            raise RuntimeError(f"{fn}: out and {name} overlap")
+    _aligned16(fn, base=base, out=out)
+    _aligned16(fn, codes=codes, scales=scales, weight=weight)
+    for t in (base, codes, scales, weight, out):
+        _ptr(t)  # no CPU path
+    _check(lib().dls_eden_fedavg_f32(_ptr(base), _ptr(codes), _row_pitch(codes), _ptr(scales),
+                                     _row_pitch(scales), _ptr(weight), total, K, P, bits, seed,
+                                     stream_id, _ptr(out), _stream(stream, base)),
+           "dls_eden_fedavg_f32")
     return out
 
 

@@ -460,6 +460,10 @@ def get_sharded_server(algorithm, **kwargs):
         raise RuntimeError("fed_drive runs on the one-process server only (factory.get_server("
                            "'fed_drive', sharded=False, ...)): a sharded server over rotated sign "
                            "payloads is not implemented")
+    if algorithm == "fed_eden":
+        raise RuntimeError("fed_eden runs on the one-process server only (factory.get_server("
+                           "'fed_eden', sharded=False, ...)): a sharded server over rotated code "
+                           "payloads is not implemented")
     if algorithm == "fed_sketch":
         raise RuntimeError("fed_sketch runs on the one-process server only (factory.get_server("
                            "'fed_sketch', sharded=False, ...)): a sharded server over Count Sketch "

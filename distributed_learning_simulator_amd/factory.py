@@ -1,5 +1,6 @@
 """Plugin factory (reference: factory.py:14-35) — same algorithm names and errors."""
 from .servers.fed_drive_server import FedDriveServer
+from .servers.fed_eden_server import FedEDENServer
 from .servers.fed_efsign_server import FedEFSignServer
 from .servers.fed_mx_server import FedMXServer
 from .servers.fed_powersgd_server import FedPowerSGDServer
@@ -14,6 +15,7 @@ from .servers.multiround_shapley_value_server import MultiRoundShapleyValueServe
 from .servers.server import Server
 from .servers.sign_sgd_server import SignSGDServer
 from .workers.fed_drive_worker import FedDriveWorker
+from .workers.fed_eden_worker import FedEDENWorker
 from .workers.fed_efsign_worker import FedEFSignWorker
 from .workers.fed_mx_worker import FedMXWorker
 from .workers.fed_powersgd_worker import FedPowerSGDWorker
@@ -50,6 +52,8 @@ def get_server(algorithm, sharded=None, **kwargs) -> Server:
         return FedEFSignServer(**kwargs)
     if algorithm == "fed_drive":
         return FedDriveServer(**kwargs)
+    if algorithm == "fed_eden":
+        return FedEDENServer(**kwargs)
     if algorithm == "fed_sketch":
         return FedSketchServer(**kwargs)
     if algorithm == "fed_powersgd":
@@ -78,6 +82,8 @@ def get_worker(algorithm, **kwargs) -> Worker:
         return FedEFSignWorker(**kwargs)
     if algorithm == "fed_drive":
         return FedDriveWorker(**kwargs)
+    if algorithm == "fed_eden":
+        return FedEDENWorker(**kwargs)
     if algorithm == "fed_sketch":
         return FedSketchWorker(**kwargs)
     if algorithm == "fed_powersgd":

@@ -26,6 +26,8 @@
         --worker_number 10 --round 5 [--efsign_error_feedback 1]
     python -m distributed_learning_simulator_amd.simulator --distributed_algorithm fed_drive \\
         --worker_number 10 --round 5 [--drive_seed 0] [--drive_scale unbiased|mse]
+    python -m distributed_learning_simulator_amd.simulator --distributed_algorithm fed_eden \\
+        --worker_number 10 --round 5 [--eden_bits 2|4] [--eden_scale unbiased|mse] [--eden_seed 0]
     python -m distributed_learning_simulator_amd.simulator --distributed_algorithm fed_sketch \\
         --worker_number 10 --round 5 [--sketch_rows 5] [--sketch_cols 262144] \\
         [--sketch_ratio 0.01] [--sketch_momentum 0.9] [--sketch_seed 0]
@@ -63,6 +65,7 @@ from .workers.fed_secagg_worker import SECAGG_DEFAULTS
 
 TOPK_DEFAULTS = {"topk_ratio": 0.01, "topk_error_feedback": 1}
 DRIVE_DEFAULTS = {"drive_seed": 0, "drive_scale": "unbiased"}
+EDEN_DEFAULTS = {"eden_bits": 4, "eden_scale": "unbiased", "eden_seed": 0}
 # sketch_cols None: the largest power of two <= P / 32, clamped to 1024..2^24
 SKETCH_DEFAULTS = {"sketch_rows": 5, "sketch_cols": None, "sketch_ratio": 0.01,
                    "sketch_momentum": 0.9, "sketch_seed": 0}
@@ -178,6 +181,13 @@ def get_config(argv=None):
     # of one decode).  The workers keep nothing between rounds
     ap.add_argument("--drive_seed", type=int, default=None)
     ap.add_argument("--drive_scale", type=str, default=None, choices=("unbiased", "mse"))
+    # fed_eden: fed_drive's rotation (--eden_seed, a fresh one every round), then --eden_bits
+    # bits per rotated coordinate, the nearest level of the Lloyd-Max quantizer of the normal
+    # distribution, and one scale per 4096 coordinates: --eden_scale unbiased (EDEN's, right in
+    # expectation) or mse.  The workers keep nothing between rounds
+    ap.add_argument("--eden_bits", type=int, default=None, choices=(2, 4))
+    ap.add_argument("--eden_scale", type=str, default=None, choices=("unbiased", "mse"))
+    ap.add_argument("--eden_seed", type=int, default=None)
     # fed_sketch (FetchSGD): every worker sends a Count Sketch of its update, --sketch_rows x
     # --sketch_cols fp32 buckets (cols a power of two; default the largest <= P / 32), under the
     # hash of --sketch_seed, and keeps nothing between rounds; the server keeps momentum
@@ -252,6 +262,15 @@ def get_config(argv=None):
             setattr(config, name, default)
     if not 0 <= config.drive_seed < 1 << 64:
         ap.error("--drive_seed must lie in 0..2^64 - 1")
+    if config.distributed_algorithm != "fed_eden" and any(
+            getattr(config, name) is not None for name in EDEN_DEFAULTS):
+        ap.error("--eden_bits, --eden_scale and --eden_seed apply to --distributed_algorithm "
+                 "fed_eden alone")
+    for name, default in EDEN_DEFAULTS.items():
+        if getattr(config, name) is None:
+            setattr(config, name, default)
+    if not 0 <= config.eden_seed < 1 << 64:
+        ap.error("--eden_seed must lie in 0..2^64 - 1")
     if config.distributed_algorithm != "fed_sketch" and any(
             getattr(config, name) is not None for name in SKETCH_DEFAULTS):
         ap.error("--sketch_rows, --sketch_cols, --sketch_ratio, --sketch_momentum and "
@@ -361,6 +380,9 @@ def server_kwargs(config):
         kwargs["secagg_dropouts"] = tuple(getattr(config, "secagg_dropouts", ()))
     if config.distributed_algorithm == "fed_drive":  # the rotation the workers use
         kwargs["seed"] = getattr(config, "drive_seed", DRIVE_DEFAULTS["drive_seed"])
+    if config.distributed_algorithm == "fed_eden":  # the workers' rotation and code width
+        kwargs["seed"] = getattr(config, "eden_seed", EDEN_DEFAULTS["eden_seed"])
+        kwargs["bits"] = getattr(config, "eden_bits", EDEN_DEFAULTS["eden_bits"])
     if config.distributed_algorithm == "fed_sketch":  # the workers' table and hash, and the round's
         kwargs.update(_sketch_table(config))
         kwargs["ratio"] = getattr(config, "sketch_ratio", SKETCH_DEFAULTS["sketch_ratio"])
@@ -384,7 +406,8 @@ def worker_kwargs(config):
     """The keyword arguments run() passes to factory.get_worker beside trainer / queue /
     round / worker_id: the sparsifier's for fed_topk, the mask format, seed, weighting and
     the round's participants (every worker) for fed_secagg, the error-feedback switch for
-    fed_efsign, the rotation's seed and the scale for fed_drive, the table's shape and the
+    fed_efsign, the rotation's seed and the scale for fed_drive, those and the code width for
+    fed_eden, the table's shape and the
     hash's seed for fed_sketch, the code width, the norm and the seed for fed_qsgd,
     the element format, the rounding, the error-feedback switch and the seed for fed_mx, the rank, the seed and the two switches for fed_powersgd, none
     for the other algorithms."""
@@ -402,6 +425,9 @@ def worker_kwargs(config):
         feedback = get("error_feedback")
         return {"format": get("format"), "rounding": get("rounding"), "seed": get("seed"),
                 "error_feedback": None if feedback is None else bool(feedback)}
+    if config.distributed_algorithm == "fed_eden":
+        return {name: getattr(config, "eden_" + name, EDEN_DEFAULTS["eden_" + name])
+                for name in ("bits", "scale", "seed")}
     if config.distributed_algorithm == "fed_drive":
         return {"seed": getattr(config, "drive_seed", DRIVE_DEFAULTS["drive_seed"]),
                 "scale": getattr(config, "drive_scale", DRIVE_DEFAULTS["drive_scale"])}

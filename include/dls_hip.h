@@ -1115,6 +1115,77 @@ int dls_drive_fedavg_f32(const float *base, const uint64_t *bits, int64_t ldb, c
                          int64_t lds, const float *weight, float total, int32_t K, int64_t P,
                          uint64_t seed, uint64_t stream_id, float *out, dls_stream_t stream);
 
+/* Multi-bit rotated compression (csrc/eden.hip; Vargaftik et al. 2022, "EDEN: communication-
+ * efficient and robust distributed mean estimation for federated learning"), DRIVE's successor
+ * at b = 2 or 4 bits per coordinate: after the rotation above a block's coordinates are close
+ * to N(0, sigma^2), so every coordinate goes as the nearest level of the fixed Lloyd-Max
+ * quantizer of N(0, 1) with 2^b levels, scaled by the block's root mean square, and one scale
+ * per block makes the decode unbiased.  No client state.  The reference simulator has no such
+ * compressor: the definitions below are this library's and tests/eden_ref.py restates them in
+ * numpy.
+ *
+ * The codebook is symmetric with M = 2^(b-1) magnitudes: centroids cent_b[0] < .. < cent_b[M-1]
+ * (DLS_EDEN_CENT2 / _CENT4) and boundaries bound_b[m] = (cent_b[m] + cent_b[m+1]) / 2, m < M - 1
+ * (DLS_EDEN_BOUND2 / _BOUND4), every centroid the mean of |N(0, 1)| over its cell; the values
+ * are tools/eden_tables.py's output, rounded to fp32.
+ *
+ * dls_eden_compress_f32, the client's side.  Operands, blocks, (seed, stream_id), sigma and the
+ * rotation are dls_drive_compress_f32's: u[j] = fl32(w[j] - base[j]), y the forward rotation of
+ * u.  Per block B of 4096 rotated coordinates:
+ *   sq      = sum (double)y[j]^2 in the order dls_drive_compress_f32 documents (a thread over r
+ *             = 0..15 ascending, the xor butterfly 32..1, the four waves in order); so are dot
+ *             and qq below
+ *   rms     = (float)sqrt(sq / 4096.0), the square root in fp64;  thr[m] = fl32(bound_b[m] * rms)
+ *   m_j     = #{m : |y[j]| > thr[m]}: a tie takes the lower cell, a NaN compares false
+ *             everywhere and gives 0;  neg_j = (y[j] < 0), as in drive
+ *   f_j     = m_j | neg_j << (b-1), the coordinate's field
+ *   dot     = sum |(double)y[j]| * (double)cent_b[m_j] (each product exact in fp64),
+ *   qq      = sum (double)cent_b[m_j]^2
+ *   scales  fp32 [NB]: DLS_EDEN_UNBIASED: (float)(sq / dot), DLS_EDEN_MSE: (float)(dot / qq);
+ *           dot == 0 gives +0.0 in both
+ *   codes   uint32 [NB * 128 * b]: a word holds fpw = 32 / b fields.  With v = j >> 10, r = (j >>
+ *           6) & 15, l = j & 63 of the block's coordinate j, its field sits at bit (r % fpw) * b
+ *           of word B * 128 * b + (v * (b / 2) + r / fpw) * 64 + l: the thread of the rotation
+ *           that owns the coordinates (v, l) packs its own 16 fields and a wave stores
+ *           contiguous words.  All Pd fields carry information
+ *   stats   int32 [1]: stats[0] is set, not added to, to #{j < P : u[j] not finite}, through
+ *           dls_drive_compress_f32's per-stream word
+ * One launch, no workspace, no floating-point atomics.  Traffic: 8 P + b P / 8 bytes.
+ *
+ * dls_eden_fedavg_f32, the server's side: FedAvg over K clients' code rows in the rotated
+ * domain, rotated back once and added to the model the clients started from.  codes uint32 [K,
+ * ldc], ldc >= NB * 128 * b; scales fp32 [K, lds], lds >= NB; weight[i] = fl32(n_i), total =
+ * fl32(sum of the n_i).  Per block B:
+ *   c[i]    = fl(fl(scales[i][B] * weight[i]) / total), the correctly rounded division of
+ *             DLS_FEDAVG_EXACT
+ *   t[i][f] = fl(c[i] * cent_b[f & (M-1)]), with the sign bit set where f has bit b-1
+ *   z[j]    = the chain over the clients i = 0..K-1 in the given order of t[i][f_ij]: the first
+ *             assigns, the later ones add with fp32 +
+ *   v       = the inverse rotation of z;  out[j] = fl(base[j] + v[j]) for j < P
+ * K >= 1 without an upper limit (clients are walked in tiles of DLS_EDEN_CLIENT_TILE).  One
+ * launch, no atomics: the same bits for any launch geometry, HIP stream or pitch.  out must
+ * not overlap base.  Traffic: (K b / 8 + 8) P bytes and 4 K NB of scales.
+ *
+ * Checks, each before any device call, in this order: no null pointer; bits 2 or 4, scale_mode
+ * one of the two, K >= 1; 64 <= P < 2^31 (DLS_EINVAL); P a multiple of 64, ldc and lds, every
+ * pointer 16-byte aligned (DLS_ELAYOUT); out against base, and for the compressor codes, scales
+ * and stats against w and base (DLS_EINVAL).  A failed check writes nothing.  Nothing is
+ * synchronised inside a call. */
+#define DLS_EDEN_CLIENT_TILE 64
+#define DLS_EDEN_UNBIASED 0
+#define DLS_EDEN_MSE 1
+#define DLS_EDEN_CENT2 {0x1.cfa592p-2f, 0x1.82aabap+0f}
+#define DLS_EDEN_BOUND2 {0x1.f6941ep-1f}
+#define DLS_EDEN_CENT4 {0x1.06f3fap-3f, 0x1.8d5c88p-2f, 0x1.5042bcp-1f, 0x1.e27a72p-1f, 0x1.41985ep+0f, 0x1.9e384ap+0f, 0x1.08d58ep+1f, 0x1.5dc57ep+1f}
+#define DLS_EDEN_BOUND4 {0x1.086b42p-2f, 0x1.0b788p-1f, 0x1.995e96p-1f, 0x1.196accp+0f, 0x1.6fe854p+0f, 0x1.d7f1b4p+0f, 0x1.334d86p+1f}
+int dls_eden_compress_f32(const float *w, const float *base, int64_t P, int32_t bits, uint64_t seed,
+                          uint64_t stream_id, int32_t scale_mode, uint32_t *codes, float *scales,
+                          int32_t *stats, dls_stream_t stream);
+int dls_eden_fedavg_f32(const float *base, const uint32_t *codes, int64_t ldc, const float *scales,
+                        int64_t lds, const float *weight, float total, int32_t K, int64_t P,
+                        int32_t bits, uint64_t seed, uint64_t stream_id, float *out,
+                        dls_stream_t stream);
+
 /* Stochastic quantization (csrc/qsgd.hip; Alistarh et al. 2017, "QSGD: communication-efficient
  * SGD via gradient quantization and encoding"; Wen et al. 2017, "TernGrad", its one-level
  * max-norm case): an unbiased quantizer without client state and without anything the clients
