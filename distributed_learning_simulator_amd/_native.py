@@ -81,6 +81,11 @@ SIGNATURES = {
     "dls_centered_clip_step_f32": ([_p, _i64, _p, _i32, _p, _i64, _p, _p, _p, _p], _i32),
     "dls_server_opt_step_f32": ([_i32, _p, _p, _p, _p, _p, _i64, _f32, _f32, _f32, _f32, _f32, _f32,
                                  _p], _i32),
+    "dls_scaffold_local_step_f32": ([_p, _p, _p, _p, _i32, _p, _p, _i64, _f32, _f32, _f32, _i32, _p],
+                                    _i32),
+    "dls_scaffold_finish_f32": ([_p, _p, _p, _p, _p, _i64, _f32, _i32, _p, _p], _i32),
+    "dls_scaffold_server_step_f32": ([_p, _i64, _p, _p, _p, _i32, _f32, _i64, _f32, _f32, _p, _p, _p,
+                                      _p, _i32, _p], _i32),
     "dls_topk_workspace": ([_i64], _i64),
     "dls_topk_compress_f32": ([_p, _p, _p, _i64, _i64, _p, _p, _p, _p, _p], _i32),
     "dls_sparse_fedavg_f32": ([_p, _p, _p, _p, _p, _i32, _f32, _i64, _p, _p], _i32),
@@ -229,6 +234,7 @@ CSRC_HASHED = [  # the Makefile's HASHED, in its order
     "qsgd.hip",
     "mx.hip",
     "eden.hip",
+    "scaffold.hip",
     "topk.hip",
     "dpnoise.hip",
     "dls_common.h",
@@ -885,6 +891,167 @@ def server_opt_step(kind, agg, x, m, v, out, P, lr, beta1, beta2, tau, stream=No
                                          lr, beta1, omb1, beta2, omb2, tau, _stream(stream, agg)),
            "dls_server_opt_step_f32")
     return out
+
+
+# ------------------------------------------- SCAFFOLD control variates / FedProx
+SCAFFOLD_MAX_SEGS = 32  # DLS_SCAFFOLD_MAX_SEGS: tensors per launch of the local step
+SCAFFOLD_MAX_K = 1024  # DLS_SCAFFOLD_MAX_K: client rows per dls_scaffold_server_step_f32 call
+
+
+def scaffold_coeff(steps, lr, population=1):
+    """fl32(1 / (steps * lr * population)), the quotient taken in fp64 and rounded once:
+    ``a`` of scaffold_finish (population 1) and ``b[k]`` of scaffold_server_step.
+    RuntimeError unless steps and population are positive integers and lr is positive and
+    the result finite."""
+    ok = all(not isinstance(v, bool) and isinstance(v, int) and v >= 1 for v in (steps, population))
+    if not ok or not (isinstance(lr, (int, float)) and math.isfinite(lr) and lr > 0):
+        raise RuntimeError(f"scaffold_coeff: steps={steps!r} and population={population!r} must be "
+                           f"positive integers and lr={lr!r} positive")
+    v = fl32(1.0 / (float(steps) * float(lr) * float(population)))
+    if not math.isfinite(v):
+        raise RuntimeError(f"scaffold_coeff: 1 / ({steps} * {lr} * {population}) is not finite in fp32")
+    return v
+
+
+def _scaffold_finite(fn, **values):
+    out = []
+    for name, v in values.items():
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(fl32(v)):
+            raise RuntimeError(f"{fn}: {name}={v!r} must be a number that is finite in fp32")
+        out.append(fl32(v))
+    return out
+
+
+def scaffold_local_step(params, grads, offsets, x, corr, lr, wd=0.0, mu=0.0, stream=None):
+    """One corrected local SGD step over a list of tensors in ceil(T / SCAFFOLD_MAX_SEGS)
+    launches (dls_scaffold_local_step_f32): per element, q = offsets[t] + its index, d = g;
+    d = fl32(d + fl32(wd * p)) if wd != 0; d = fl32(d + fl32(mu * fl32(p - x[q]))) if mu != 0;
+    d = fl32(d + corr[q]) if corr is given; p = fl32(p - fl32(lr * d)), in place, every
+    operation rounded once.  params, grads: fp32 tensors with their memory in logical order
+    (``is_contiguous()``; a storage offset is fine), grads[t] as many elements as params[t];
+    x, corr: fp32 vectors with unit stride that hold offsets[t] + numel for every t (x may be
+    None with mu == 0, corr None turns the control term off).  Returns params."""
+    fn = "scaffold_local_step"
+    params, grads, offsets = list(params), list(grads), [int(o) for o in offsets]
+    if not len(params) == len(grads) == len(offsets):
+        raise RuntimeError(f"{fn}: {len(params)} params, {len(grads)} grads and {len(offsets)} "
+                           "offsets")
+    lr, wd, mu = _scaffold_finite(fn, lr=lr, wd=wd, mu=mu)
+    if mu != 0.0 and x is None:
+        raise RuntimeError(f"{fn}: mu={mu} needs x")
+    T = len(params)
+    if T == 0:
+        return params
+    ends = [0]
+    for t, (p, g, o) in enumerate(zip(params, grads, offsets)):
+        _require_logical_f32(fn, **{f"params[{t}]": p, f"grads[{t}]": g})
+        if g.numel() != p.numel():
+            raise RuntimeError(f"{fn}: grads[{t}] holds {g.numel()} elements, params[{t}] {p.numel()}")
+        if o < 0:
+            raise RuntimeError(f"{fn}: offsets[{t}]={o}")
+        ends.append(o + p.numel())
+    P = max(ends)
+    flat = {name: t for name, t in (("x", x if mu != 0.0 else None), ("corr", corr)) if t is not None}
+    for name, t in flat.items():
+        _f32_vector(fn, name, t, P)
+    _check_same_device(fn, params[0], _anchor="params[0]", **flat,
+                       **{f"params[{t}]": p for t, p in enumerate(params)},
+                       **{f"grads[{t}]": g for t, g in enumerate(grads)})
+    _ptr(params[0])  # no CPU path
+    ptrs = ctypes.c_void_p * T
+    i64s = ctypes.c_int64 * T
+    _check(lib().dls_scaffold_local_step_f32(
+        ptrs(*[p.data_ptr() for p in params]), ptrs(*[g.data_ptr() for g in grads]),
+        i64s(*offsets), i64s(*[p.numel() for p in params]), T, _ptr(flat.get("x")),
+        _ptr(flat.get("corr")), P, lr, wd, mu, int(corr is not None),
+        _stream(stream, params[0])), "dls_scaffold_local_step_f32")
+    return params
+
+
+def scaffold_finish(y, x, c, c_i, delta, P, a, stats, stream=None):
+    """The client's round end in one launch (dls_scaffold_finish_f32): delta[:P] = fl32(y - x)
+    and, with c and c_i given, c_i[:P] = fl32(fl32(c_i - c) - fl32(a * delta)) in place (option
+    II of the paper; a = ``scaffold_coeff(steps, lr)``); stats (int32 [1]) becomes the number of
+    non-finite delta.  c = c_i = None writes delta and stats alone.  fp32 vectors of at least
+    P elements with unit stride, P a positive multiple of 4, every tensor 16-byte aligned;
+    delta, c_i and stats overlap nothing else.  Returns delta."""
+    fn = "scaffold_finish"
+    P = int(P)
+    if P < 4 or P % 4 != 0:
+        raise RuntimeError(f"{fn}: P={P} must be a positive multiple of 4")
+    if (c is None) != (c_i is None):
+        raise RuntimeError(f"{fn}: c and c_i are given together or not at all")
+    (a,) = _scaffold_finite(fn, a=a)
+    given = {name: t for name, t in (("y", y), ("x", x), ("c", c), ("c_i", c_i), ("delta", delta))
+             if t is not None}
+    for name, t in given.items():
+        _f32_vector(fn, name, t, P)
+    _unit_vector(fn, "stats", stats, torch.int32, 1)
+    _check_same_device(fn, y, _anchor="y", **given, stats=stats)
+    _check_disjoint({**{name: t[:P] for name, t in given.items()}, "stats": stats[:1]},
+                    f"{fn}: {{a}} and {{b}} overlap",
+                    allowed=lambda p, q: {p, q} <= {"y", "x", "c"})
+    _aligned16(fn, **given)
+    for t in (*given.values(), stats):
+        _ptr(t)  # no CPU path
+    _check(lib().dls_scaffold_finish_f32(_ptr(y), _ptr(x), _ptr(c), _ptr(c_i), _ptr(delta), P, a,
+                                         int(c is not None), _ptr(stats), _stream(stream, y)),
+           "dls_scaffold_finish_f32")
+    return delta
+
+
+def scaffold_server_step(U, rows, weight, b, total, P, eta_g, f, x, c, x_out=None, c_out=None,
+                         stream=None):
+    """The server's round end over the K = rows.numel() delta rows of U in one read
+    (dls_scaffold_server_step_f32), in the order of ``rows``: acc the exact FedAvg chain
+    fl32(fl32(U_k * weight[k]) / total) (dls_fedavg_f32's bits), s the chain fl32(b[k] * U_k),
+    both "the first assigns, the rest add"; x_out[:P] = fl32(x + fl32(eta_g * acc)) and
+    c_out[:P] = fl32(fl32(c - fl32(f * c)) - s).  weight, b: contiguous fp32 [K] (b[k] =
+    ``scaffold_coeff(steps_k, lr_k, N)``); f = K / N.  c = None turns the control variate off:
+    b and c_out must be None too and x_out alone is written.  x_out / c_out default to x / c
+    (in place) and may be those or disjoint from everything.  1 <= K <= SCAFFOLD_MAX_K; the
+    rest as the rows family (P and the pitch multiples of 4, 16-byte alignment).  Returns
+    (x_out, c_out)."""
+    fn = "scaffold_server_step"
+    if (not torch.is_tensor(U) or U.dtype != torch.float32 or U.dim() != 2
+            or (U.shape[1] > 1 and U.stride(1) != 1)):
+        raise RuntimeError(f"{fn}: U must be an fp32 [rows, ld] matrix with unit element stride")
+    _check_tensor(fn, "rows", rows, torch.int32, 0, "a contiguous int32 [K] tensor", exact=False,
+                  contiguous=False)
+    K = rows.numel()
+    if not 1 <= K <= SCAFFOLD_MAX_K:
+        raise RuntimeError(f"{fn}: K={K} rows (1..SCAFFOLD_MAX_K={SCAFFOLD_MAX_K})")
+    control = c is not None
+    if not control and (b is not None or c_out is not None):
+        raise RuntimeError(f"{fn}: b and c_out need c (the control variate is off without it)")
+    if control and b is None:
+        raise RuntimeError(f"{fn}: c needs b")
+    eta_g, f, total = _scaffold_finite(fn, eta_g=eta_g, f=f, total=total)
+    if total <= 0.0:
+        raise RuntimeError(f"{fn}: total={total} must be positive")
+    P, ldu = _rows_extent(fn, U, P)
+    x_out = x if x_out is None else x_out
+    c_out = c if c_out is None else c_out
+    _k_tensor(fn, "weight", weight, torch.float32, (K,))
+    if control:
+        _k_tensor(fn, "b", b, torch.float32, (K,))
+    vectors = {"x": x, "x_out": x_out, **({"c": c, "c_out": c_out} if control else {})}
+    for name, t in vectors.items():
+        _f32_vector(fn, name, t, P)
+    _rows_placement(fn, U, tuple(vectors), rows=rows, weight=weight, b=b, **vectors)
+    same = {("x", "x_out"), ("c", "c_out")}
+    _check_disjoint({"U": U, **{name: t[:P] for name, t in vectors.items()}},
+                    f"{fn}: {{a}} and {{b}} overlap (x_out may be x itself and c_out c itself, "
+                    "nothing else may overlap)",
+                    allowed=lambda p, q: (p, q) in same and vectors[p].data_ptr() == vectors[q].data_ptr())
+    for t in (U, rows, weight, *vectors.values()):
+        _ptr(t)  # no CPU path
+    if P != 0:
+        _check(lib().dls_scaffold_server_step_f32(
+            _ptr(U), ldu, _ptr(rows), _ptr(weight), _ptr(b), K, total, P, eta_g, f, _ptr(x),
+            _ptr(c), _ptr(x_out), _ptr(c_out), int(control), _stream(stream, U)),
+            "dls_scaffold_server_step_f32")
+    return x_out, c_out
 
 
 # ------------------------------------------------------- top-k sparsification

@@ -6,6 +6,7 @@ from .servers.fed_mx_server import FedMXServer
 from .servers.fed_powersgd_server import FedPowerSGDServer
 from .servers.fed_qsgd_server import FedQSGDServer
 from .servers.fed_quant_server import FedQuantServer
+from .servers.fed_scaffold_server import FedScaffoldServer
 from .servers.fed_secagg_server import FedSecAggServer
 from .servers.fed_sketch_server import FedSketchServer
 from .servers.fed_server import FedServer
@@ -21,6 +22,7 @@ from .workers.fed_mx_worker import FedMXWorker
 from .workers.fed_powersgd_worker import FedPowerSGDWorker
 from .workers.fed_qsgd_worker import FedQSGDWorker
 from .workers.fed_quant_worker import FedQuantWorker
+from .workers.fed_scaffold_worker import FedScaffoldWorker
 from .workers.fed_secagg_worker import FedSecAggWorker
 from .workers.fed_sketch_worker import FedSketchWorker
 from .workers.fed_topk_worker import FedTopKWorker
@@ -62,6 +64,8 @@ def get_server(algorithm, sharded=None, **kwargs) -> Server:
         return FedQSGDServer(**kwargs)
     if algorithm == "fed_mx":
         return FedMXServer(**kwargs)
+    if algorithm == "fed_scaffold":
+        return FedScaffoldServer(**kwargs)
     if algorithm == "multiround_shapley_value":
         return MultiRoundShapleyValueServer(**kwargs)
     if algorithm == "GTG_shapley_value":
@@ -92,6 +96,8 @@ def get_worker(algorithm, **kwargs) -> Worker:
         return FedQSGDWorker(**kwargs)
     if algorithm == "fed_mx":
         return FedMXWorker(**kwargs)
+    if algorithm == "fed_scaffold":
+        return FedScaffoldWorker(**kwargs)
     if algorithm in ("fed", "multiround_shapley_value", "GTG_shapley_value"):
         return FedWorker(**kwargs)
     raise RuntimeError("unknown algorithm:" + algorithm)

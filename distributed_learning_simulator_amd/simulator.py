@@ -39,6 +39,9 @@
     python -m distributed_learning_simulator_amd.simulator --distributed_algorithm fed_mx \\
         --worker_number 10 --round 5 [--mx_format e4m3|e5m2|e2m1] \\
         [--mx_rounding nearest|stochastic] [--mx_error_feedback 0|1] [--mx_seed 0]
+    python -m distributed_learning_simulator_amd.simulator --distributed_algorithm fed_scaffold \\
+        --worker_number 10 --round 5 [--scaffold_global_lr 1.0] [--scaffold_mu 0] \\
+        [--scaffold_control 1|0]
 
 Same flags and flow as the reference: IID split of the training set over the
 workers (:48-50), a tester on the test split (:51), ``factory.get_server``
@@ -75,6 +78,7 @@ QSGD_DEFAULTS = {"qsgd_bits": 4, "qsgd_norm": "l2", "qsgd_seed": 0}
 # mx_error_feedback None: on for nearest rounding, off for stochastic
 MX_DEFAULTS = {"mx_format": "e4m3", "mx_rounding": "nearest", "mx_error_feedback": None,
                "mx_seed": 0}
+SCAFFOLD_DEFAULTS = {"scaffold_global_lr": 1.0, "scaffold_mu": 0.0, "scaffold_control": 1}
 # the fed_secagg flags and what they hold when not given (threshold None: a majority)
 SECAGG_FLAGS = {**{name: int(v) for name, v in SECAGG_DEFAULTS.items()},
                 "secagg_dropouts": (), "secagg_threshold": None}
@@ -225,6 +229,14 @@ def get_config(argv=None):
     ap.add_argument("--mx_rounding", type=str, default=None, choices=("nearest", "stochastic"))
     ap.add_argument("--mx_error_feedback", type=int, default=None, choices=(0, 1))
     ap.add_argument("--mx_seed", type=int, default=None)
+    # fed_scaffold: local SGD corrected against client drift.  Every step adds the difference of
+    # the server's and the client's control variate to the gradient (SCAFFOLD; --scaffold_control
+    # 0 turns it off) and --scaffold_mu times the distance to the round's global model (FedProx's
+    # proximal term; --scaffold_control 0 --scaffold_mu 0.01 is FedProx); the server moves the
+    # model by --scaffold_global_lr times the averaged update.  It needs --momentum 0
+    ap.add_argument("--scaffold_global_lr", type=float, default=None)
+    ap.add_argument("--scaffold_mu", type=float, default=None)
+    ap.add_argument("--scaffold_control", type=int, default=None, choices=(0, 1))
     # fed_secagg: every worker sends its update quantised to --secagg_bits bits with
     # --secagg_frac_bits fractional ones (defaults 20 and 16: +-8 at 1.5e-5) and masked in
     # Z_2^32 with the pair and self masks of the Philox stream under --secagg_seed;
@@ -316,6 +328,17 @@ def get_config(argv=None):
             setattr(config, name, default)
     if not 0 <= config.mx_seed < 1 << 64:
         ap.error("--mx_seed must lie in 0..2^64 - 1")
+    if config.distributed_algorithm != "fed_scaffold" and any(
+            getattr(config, name) is not None for name in SCAFFOLD_DEFAULTS):
+        ap.error("--scaffold_global_lr, --scaffold_mu and --scaffold_control apply to "
+                 "--distributed_algorithm fed_scaffold alone")
+    for name, default in SCAFFOLD_DEFAULTS.items():
+        if getattr(config, name) is None:
+            setattr(config, name, default)
+    if not config.scaffold_global_lr > 0.0:
+        ap.error("--scaffold_global_lr must be positive")
+    if not config.scaffold_mu >= 0.0:
+        ap.error("--scaffold_mu must not be negative")
     if config.topk_ratio is None:
         config.topk_ratio = TOPK_DEFAULTS["topk_ratio"]
     if config.topk_error_feedback is None:
@@ -393,6 +416,11 @@ def server_kwargs(config):
         kwargs["bits"] = getattr(config, "qsgd_bits", QSGD_DEFAULTS["qsgd_bits"])
     if config.distributed_algorithm == "fed_mx":  # the element format of the workers' codes
         kwargs["format"] = getattr(config, "mx_format", MX_DEFAULTS["mx_format"])
+    if config.distributed_algorithm == "fed_scaffold":  # the server's step; control as the workers'
+        kwargs["global_lr"] = getattr(config, "scaffold_global_lr",
+                                      SCAFFOLD_DEFAULTS["scaffold_global_lr"])
+        kwargs["control"] = bool(getattr(config, "scaffold_control",
+                                         SCAFFOLD_DEFAULTS["scaffold_control"]))
     return kwargs
 
 
@@ -410,7 +438,11 @@ def worker_kwargs(config):
     fed_eden, the table's shape and the
     hash's seed for fed_sketch, the code width, the norm and the seed for fed_qsgd,
     the element format, the rounding, the error-feedback switch and the seed for fed_mx, the rank, the seed and the two switches for fed_powersgd, none
-    for the other algorithms."""
+    for the other algorithms (fed_scaffold: the proximal coefficient and the control switch)."""
+    if config.distributed_algorithm == "fed_scaffold":
+        return {"mu": getattr(config, "scaffold_mu", SCAFFOLD_DEFAULTS["scaffold_mu"]),
+                "control": bool(getattr(config, "scaffold_control",
+                                        SCAFFOLD_DEFAULTS["scaffold_control"]))}
     if config.distributed_algorithm == "fed_powersgd":
         get = lambda name: getattr(config, "powersgd_" + name, POWERSGD_DEFAULTS["powersgd_" + name])
         return {"rank": get("rank"), "seed": get("seed"), "warm_start": bool(get("warm_start")),

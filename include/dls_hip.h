@@ -404,6 +404,69 @@ int dls_server_opt_step_f32(int32_t kind, const float *agg, const float *x, floa
                             float *out, int64_t P, float lr, float beta1, float omb1,
                             float beta2, float omb2, float tau, dls_stream_t stream);
 
+/* SCAFFOLD control variates and the FedProx proximal term (csrc/scaffold.hip; Karimireddy,
+ * Kale, Mohri, Reddi, Stich & Suresh 2020, "SCAFFOLD: stochastic controlled averaging for
+ * federated learning", with the paper's option II for the client control variate; Li et al.
+ * 2020, "Federated optimization in heterogeneous networks").  The reference simulator has
+ * neither: the definitions below are this library's and tests/scaffold_ref.py restates them
+ * in numpy float32.  Every operation is rounded once to fp32 and never fused, so given the
+ * input bits every output is defined bit for bit wherever it is not NaN.  Nothing is
+ * synchronised inside a call and every check runs before any device call.
+ *
+ * dls_scaffold_local_step_f32, the client's optimizer step (plain SGD) over T tensors.  p, g,
+ * off, n are HOST arrays of T entries: device pointers of the parameter and its gradient (n[t]
+ * fp32 each, memory in logical order, 4-byte aligned, not overlapping), the tensor's first
+ * index off[t] in the flat vectors x (the round's global model) and corr (c - c_i), fp32 [P].
+ * Per element, q = off[t] + its index:
+ *   d = g;  d = fl(d + fl(wd * p)) if wd != 0;  d = fl(d + fl(mu * fl(p - x[q]))) if mu != 0;
+ *   d = fl(d + corr[q]) if control;  p = fl(p - fl(lr * d)).
+ * x is not read (and may be NULL) when mu == 0, corr likewise when control == 0; then off is
+ * not looked at either.  Launches: ceil(T' / DLS_SCAFFOLD_MAX_SEGS) for the T' tensors with
+ * n > 0, the segment table passed in the kernel arguments; a wave steps DLS_SCAFFOLD_TILE
+ * elements of one tensor, with 16-byte accesses where p[t], g[t], x + off[t] and corr +
+ * off[t] are 16-byte aligned and one element per access otherwise: the bits do not depend
+ * on the alignment.  Elements past n[t] are neither read nor written.  DLS_EINVAL: a null
+ * pointer, T < 0, control not 0 or 1, a non-finite lr, wd or mu, a segment outside [0, P);
+ * DLS_ELAYOUT: a pointer that is not 4-byte aligned.
+ *
+ * dls_scaffold_finish_f32, the client's round end: y the local model, x the round's global
+ * model, c the server control variate, ci the client's, all fp32 [P], P a positive multiple
+ * of 4, 16-byte aligned.  Per coordinate
+ *   delta = fl(y - x);  ci' = fl(fl(ci - c) - fl(a * delta))   (option II; ci in place)
+ * with a the caller's fl32(1 / (steps * lr)); stats[0] is set, not added to, to the number of
+ * non-finite delta (the call completes, the caller decides).  control == 0 writes delta and
+ * stats alone and c, ci may be NULL.  delta, ci and stats overlap nothing else.  One launch;
+ * the count meets in one 64-bit word per HIP stream (as dls_drive_compress_f32).
+ *
+ * dls_scaffold_server_step_f32, the server's round end over the K delta rows U[rows[k]][0, P)
+ * in the order of `rows` (operands as the rows family: P and ldu multiples of 4, ldu >= P, U
+ * and the vectors 16-byte aligned; 1 <= K <= DLS_SCAFFOLD_MAX_K).  weight[k] = fl32(n_k),
+ * total = fl32(sum n_k), b[k] = the caller's fl32(1 / (steps_k * lr_k * N)), f = fl32(K / N),
+ * N the population.  Per coordinate
+ *   acc: t_k = fl(fl(U_k * weight[k]) / total) (the correctly rounded division of
+ *        DLS_FEDAVG_EXACT), acc = t_0, acc = fl(acc + t_k): dls_fedavg_f32's bits
+ *   s:   s = fl(b[0] * U_0), s = fl(s + fl(b[k] * U_k))
+ *   x_out = fl(x + fl(eta_g * acc));  c_out = fl(fl(c - fl(f * c)) - s)
+ * x_out may be x itself and c_out c itself (the same pointer); nothing else may overlap.
+ * control == 0 computes x_out alone: b, c and c_out are not touched and may be NULL.  One
+ * launch, no atomics, (K + 2) * 4P bytes read and 8P written; the same bits for any pitch,
+ * stream or CU count.  P == 0 launches nothing. */
+#define DLS_SCAFFOLD_MAX_SEGS 32
+#define DLS_SCAFFOLD_TILE 256
+#define DLS_SCAFFOLD_MAX_K 1024
+int dls_scaffold_local_step_f32(float *const *p, const float *const *g, const int64_t *off,
+                                const int64_t *n, int32_t T, const float *x, const float *corr,
+                                int64_t P, float lr, float wd, float mu, int32_t control,
+                                dls_stream_t stream);
+int dls_scaffold_finish_f32(const float *y, const float *x, const float *c, float *ci,
+                            float *delta, int64_t P, float a, int32_t control, int32_t *stats,
+                            dls_stream_t stream);
+int dls_scaffold_server_step_f32(const float *U, int64_t ldu, const int32_t *rows,
+                                 const float *weight, const float *b, int32_t K, float total,
+                                 int64_t P, float eta_g, float f, const float *x, const float *c,
+                                 float *x_out, float *c_out, int32_t control,
+                                 dls_stream_t stream);
+
 /* Subset aggregation as a dense fp32 MFMA contraction: out[S, P] = C[S, K] · U[rows, P]
  * (C row-major [S, K], c_si = n_i / N_S; rows[K] selects the K client rows of U).
  * fp32 in / fp32 accumulate (v_mfma_f32_32x32x2_f32): per element one fma chain in
