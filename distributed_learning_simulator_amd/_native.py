@@ -86,6 +86,8 @@ SIGNATURES = {
     "dls_scaffold_finish_f32": ([_p, _p, _p, _p, _p, _i64, _f32, _i32, _p, _p], _i32),
     "dls_scaffold_server_step_f32": ([_p, _i64, _p, _p, _p, _i32, _f32, _i64, _f32, _f32, _p, _p, _p,
                                       _p, _i32, _p], _i32),
+    "dls_hetero_fedavg_f32": ([_p, _p, _i64, _p, _p, _i32, _p, _i64, _p, _p, _p], _i32),
+    "dls_hetero_extract_f32": ([_p, _p, _i64, _p, _p, _i64, _p], _i32),
     "dls_topk_workspace": ([_i64], _i64),
     "dls_topk_compress_f32": ([_p, _p, _p, _i64, _i64, _p, _p, _p, _p, _p], _i32),
     "dls_sparse_fedavg_f32": ([_p, _p, _p, _p, _p, _i32, _f32, _i64, _p, _p], _i32),
@@ -235,6 +237,7 @@ CSRC_HASHED = [  # the Makefile's HASHED, in its order
     "mx.hip",
     "eden.hip",
     "scaffold.hip",
+    "hetero.hip",
     "topk.hip",
     "dpnoise.hip",
     "dls_common.h",
@@ -1052,6 +1055,104 @@ def scaffold_server_step(U, rows, weight, b, total, P, eta_g, f, x, c, x_out=Non
             _ptr(c), _ptr(x_out), _ptr(c_out), int(control), _stream(stream, U)),
             "dls_scaffold_server_step_f32")
     return x_out, c_out
+
+
+# ------------------------------------------- width-heterogeneous FedAvg (HeteroFL / FedRolex)
+HETERO_MAX_LEVELS = 8  # DLS_HETERO_MAX_LEVELS: width levels of a plan
+HETERO_MAX_K = 1024  # DLS_HETERO_MAX_K: clients per dls_hetero_fedavg_f32 call
+
+
+def _hetero_plan(fn, plan):
+    """plan: a ``hetero.HeteroPlan``; returns its host words after the checks on its size."""
+    words = getattr(plan, "words", None)
+    if (not torch.is_tensor(words) or words.dtype != torch.int32 or words.is_cuda
+            or not words.is_contiguous()):
+        raise RuntimeError(f"{fn}: plan must be a hetero.HeteroPlan (int32 words on the host)")
+    if not 1 <= len(plan.widths) <= HETERO_MAX_LEVELS:
+        raise RuntimeError(f"{fn}: L={len(plan.widths)} levels (1..HETERO_MAX_LEVELS="
+                           f"{HETERO_MAX_LEVELS})")
+    return words
+
+
+def hetero_fedavg(plan, levels, starts, weights, ragged, prev, out=None, stream=None):
+    """The server's round over K clients of different widths in one launch
+    (dls_hetero_fedavg_f32).  Client k, in id order, is of level levels[k] of ``plan`` (a
+    ``hetero.HeteroPlan``), its compact row is ragged[starts[k] : starts[k] + plan.level_P[level]]
+    and its weight fl32(weights[k]), finite and > 0.  Per global coordinate, over the clients
+    whose level holds it in ascending k: acc = the chain of fl32(w_k * u_k), den the chain of
+    w_k, out = fl32(acc / den); a coordinate nobody holds keeps prev's bits; the padding is
+    zero.  ragged, prev, out: fp32 vectors with unit stride, 16-byte aligned, starts multiples
+    of 4; out defaults to prev (in place) and may be prev or disjoint from everything.
+    1 <= K <= HETERO_MAX_K.  Returns out."""
+    fn = "hetero_fedavg"
+    words = _hetero_plan(fn, plan)
+    levels, starts = [int(v) for v in levels], [int(v) for v in starts]
+    K = len(levels)
+    if not 1 <= K <= HETERO_MAX_K:
+        raise RuntimeError(f"{fn}: K={K} clients (1..HETERO_MAX_K={HETERO_MAX_K})")
+    weights = list(weights)
+    if not len(starts) == len(weights) == K:
+        raise RuntimeError(f"{fn}: {K} levels, {len(starts)} starts and {len(weights)} weights")
+    for k, w in enumerate(weights):
+        if isinstance(w, bool) or not isinstance(w, (int, float)) or not math.isfinite(fl32(w)) \
+                or not fl32(w) > 0.0:
+            raise RuntimeError(f"{fn}: weights[{k}]={w!r} must be finite and > 0 in fp32")
+    _unit_vector(fn, "ragged", ragged, torch.float32, 0)
+    level_P = plan.level_P
+    for k, (lvl, start) in enumerate(zip(levels, starts)):
+        if not 0 <= lvl < len(level_P):
+            raise RuntimeError(f"{fn}: levels[{k}]={lvl} is not a level of the plan (0..{len(level_P) - 1})")
+        if start < 0 or start % 4 != 0 or start + level_P[lvl] > ragged.numel():
+            raise RuntimeError(f"{fn}: the row of client {k}, [{start}, {start} + {level_P[lvl]}) of "
+                               f"level {lvl}, must start at a multiple of 4 inside the "
+                               f"{ragged.numel()} elements of ragged")
+    out = prev if out is None else out
+    _f32_vector(fn, "prev", prev, plan.P)
+    _f32_vector(fn, "out", out, plan.P)
+    _check_same_device(fn, ragged, _anchor="ragged", prev=prev, out=out)
+    _check_disjoint({"ragged": ragged, "prev": prev[:plan.P], "out": out[:plan.P]},
+                    f"{fn}: {{a}} and {{b}} overlap (out may be prev itself, nothing else)",
+                    allowed=lambda a, b: (a, b) == ("prev", "out") and prev.data_ptr() == out.data_ptr())
+    _aligned16(fn, ragged=ragged, prev=prev, out=out)
+    for t in (ragged, prev, out):
+        _ptr(t)  # no CPU path
+    table = torch.empty((K, 4), dtype=torch.int32)
+    table[:, 0] = torch.tensor(levels, dtype=torch.int32)
+    table[:, 1] = torch.tensor([fl32(w) for w in weights], dtype=torch.float32).view(torch.int32)
+    table[:, 2:] = torch.tensor(starts, dtype=torch.int64).view(-1, 1).view(torch.int32)
+    table_dev = table.to(ragged.device)
+    if stream is not None:
+        table_dev.record_stream(stream)
+    _check(lib().dls_hetero_fedavg_f32(
+        ctypes.c_void_p(words.data_ptr()), _ptr(plan.device_words(ragged.device)), words.numel(),
+        ctypes.c_void_p(table.data_ptr()), _ptr(table_dev), K, _ptr(ragged), ragged.numel(),
+        _ptr(prev), _ptr(out), _stream(stream, ragged)), "dls_hetero_fedavg_f32")
+    return out
+
+
+def hetero_extract(plan, flat, rows=None, stream=None):
+    """The downlink in one launch (dls_hetero_extract_f32): the compact row of every level of
+    ``plan`` from the global row ``flat`` (fp32, at least plan.P elements, 16-byte aligned),
+    bit-for-bit copies with zero padding.  rows: fp32 [sum(plan.level_P)] (None: a new tensor),
+    the levels' rows one after the other.  Returns the list of the levels' rows (views)."""
+    fn = "hetero_extract"
+    words = _hetero_plan(fn, plan)
+    _f32_vector(fn, "flat", flat, plan.P)
+    total = sum(plan.level_P)
+    if rows is None:
+        rows = torch.empty(total, dtype=torch.float32, device=flat.device)
+    _unit_vector(fn, "rows", rows, torch.float32, total, count=("sum(level_P)", total))
+    _check_same_device(fn, flat, _anchor="flat", rows=rows)
+    _check_disjoint({"flat": flat[:plan.P], "rows": rows[:total]}, f"{fn}: {{a}} and {{b}} overlap")
+    _aligned16(fn, flat=flat, rows=rows)
+    _ptr(flat), _ptr(rows)  # no CPU path
+    _check(lib().dls_hetero_extract_f32(
+        ctypes.c_void_p(words.data_ptr()), _ptr(plan.device_words(flat.device)), words.numel(),
+        _ptr(flat), _ptr(rows), total, _stream(stream, flat)), "dls_hetero_extract_f32")
+    ends = [0]
+    for n in plan.level_P:
+        ends.append(ends[-1] + n)
+    return [rows[a:b] for a, b in zip(ends, ends[1:])]
 
 
 # ------------------------------------------------------- top-k sparsification

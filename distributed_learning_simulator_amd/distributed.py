@@ -480,6 +480,10 @@ def get_sharded_server(algorithm, **kwargs):
         raise RuntimeError("fed_mx runs on the one-process server only (factory.get_server("
                            "'fed_mx', sharded=False, ...)): a sharded server over microscaling "
                            "payloads is not implemented")
+    if algorithm == "fed_hetero":
+        raise RuntimeError("fed_hetero runs on the one-process server only (factory.get_server("
+                           "'fed_hetero', sharded=False, ...)): a sharded server over rows of "
+                           "different widths is not implemented")
     if algorithm not in table:
         raise RuntimeError("unknown algorithm:" + algorithm)
     return table[algorithm](**kwargs)

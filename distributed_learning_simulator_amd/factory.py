@@ -2,6 +2,7 @@
 from .servers.fed_drive_server import FedDriveServer
 from .servers.fed_eden_server import FedEDENServer
 from .servers.fed_efsign_server import FedEFSignServer
+from .servers.fed_hetero_server import FedHeteroServer
 from .servers.fed_mx_server import FedMXServer
 from .servers.fed_powersgd_server import FedPowerSGDServer
 from .servers.fed_qsgd_server import FedQSGDServer
@@ -18,6 +19,7 @@ from .servers.sign_sgd_server import SignSGDServer
 from .workers.fed_drive_worker import FedDriveWorker
 from .workers.fed_eden_worker import FedEDENWorker
 from .workers.fed_efsign_worker import FedEFSignWorker
+from .workers.fed_hetero_worker import FedHeteroWorker
 from .workers.fed_mx_worker import FedMXWorker
 from .workers.fed_powersgd_worker import FedPowerSGDWorker
 from .workers.fed_qsgd_worker import FedQSGDWorker
@@ -66,6 +68,8 @@ def get_server(algorithm, sharded=None, **kwargs) -> Server:
         return FedMXServer(**kwargs)
     if algorithm == "fed_scaffold":
         return FedScaffoldServer(**kwargs)
+    if algorithm == "fed_hetero":
+        return FedHeteroServer(**kwargs)
     if algorithm == "multiround_shapley_value":
         return MultiRoundShapleyValueServer(**kwargs)
     if algorithm == "GTG_shapley_value":
@@ -98,6 +102,8 @@ def get_worker(algorithm, **kwargs) -> Worker:
         return FedMXWorker(**kwargs)
     if algorithm == "fed_scaffold":
         return FedScaffoldWorker(**kwargs)
+    if algorithm == "fed_hetero":
+        return FedHeteroWorker(**kwargs)
     if algorithm in ("fed", "multiround_shapley_value", "GTG_shapley_value"):
         return FedWorker(**kwargs)
     raise RuntimeError("unknown algorithm:" + algorithm)

@@ -10,13 +10,37 @@ import torch.nn.functional as F
 
 
 class LeNet5(nn.Module):
-    def __init__(self, num_classes=10):
+    HIDDEN = {"c1": 6, "c2": 16, "h1": 120, "h2": 84}  # the channel groups at width 1
+
+    def __init__(self, num_classes=10, width=1.0):
+        """``width``: the ratio r of a width-heterogeneous client (hetero.py): every hidden
+        layer has ceil(r * C) channels; 1 is the model of ``model_shapes``."""
         super().__init__()
-        self.conv1 = nn.Conv2d(1, 6, 5)
-        self.conv2 = nn.Conv2d(6, 16, 5)
-        self.fc1 = nn.Linear(400, 120)
-        self.fc2 = nn.Linear(120, 84)
-        self.fc3 = nn.Linear(84, num_classes)
+        from .hetero import check_width, level_channels
+        c1, c2, h1, h2 = (level_channels(check_width(width), c) for c in self.HIDDEN.values())
+        self.conv1 = nn.Conv2d(1, c1, 5)
+        self.conv2 = nn.Conv2d(c1, c2, 5)
+        self.fc1 = nn.Linear(25 * c2, h1)
+        self.fc2 = nn.Linear(h1, h2)
+        self.fc3 = nn.Linear(h2, num_classes)
+
+    def hetero_views(self):
+        """The [O, I, R] view and channel groups of every parameter of the width-1 model, in
+        ``named_parameters`` order (hetero.SliceView).  fc1 reads the flattened [c2, 5, 5]
+        activation, so its input is [c2, 25]; the image channel and the classes never scale."""
+        from .hetero import SliceView, vector_view
+        c1, c2, h1, h2 = self.HIDDEN.values()
+        o = self.fc3.out_features
+        return [SliceView("conv1.weight", (c1, 1, 5, 5), (c1, 1, 25), "c1", None),
+                vector_view("conv1.bias", c1, "c1"),
+                SliceView("conv2.weight", (c2, c1, 5, 5), (c2, c1, 25), "c2", "c1"),
+                vector_view("conv2.bias", c2, "c2"),
+                SliceView("fc1.weight", (h1, 25 * c2), (h1, c2, 25), "h1", "c2"),
+                vector_view("fc1.bias", h1, "h1"),
+                SliceView("fc2.weight", (h2, h1), (h2, h1, 1), "h2", "h1"),
+                vector_view("fc2.bias", h2, "h2"),
+                SliceView("fc3.weight", (o, h2), (o, h2, 1), None, "h2"),
+                vector_view("fc3.bias", o, None)]
 
     def forward(self, x):  # x: [B, 1, 32, 32]
         x = F.max_pool2d(F.relu(self.conv1(x)), 2)
@@ -142,12 +166,18 @@ class _Block(nn.Module):
 class ResNet18(nn.Module):
     """CIFAR-10 ResNet-18 (3x3 stem, no max-pool)."""
 
-    def __init__(self, num_classes=10):
+    STAGES = (64, 128, 256, 512)  # the channel groups "s64" .. "s512" at width 1
+
+    def __init__(self, num_classes=10, width=1.0):
+        """``width``: the ratio r of a width-heterogeneous client (hetero.py): every stage
+        has ceil(r * C) channels; 1 is the model of ``model_shapes``."""
         super().__init__()
-        self.conv1 = nn.Conv2d(3, 64, 3, 1, 1, bias=False)
-        self.bn1 = nn.BatchNorm2d(64)
-        layers, cin = [], 64
-        for li, cout in enumerate([64, 128, 256, 512]):
+        from .hetero import check_width, level_channels
+        stages = [level_channels(check_width(width), c) for c in self.STAGES]
+        self.conv1 = nn.Conv2d(3, stages[0], 3, 1, 1, bias=False)
+        self.bn1 = nn.BatchNorm2d(stages[0])
+        layers, cin = [], stages[0]
+        for li, cout in enumerate(stages):
             blocks = []
             for b in range(2):
                 stride = 2 if (li > 0 and b == 0) else 1
@@ -155,7 +185,35 @@ class ResNet18(nn.Module):
                 cin = cout
             layers.append(nn.Sequential(*blocks))
         self.layer1, self.layer2, self.layer3, self.layer4 = layers
-        self.linear = nn.Linear(512, num_classes)
+        self.linear = nn.Linear(stages[3], num_classes)
+
+    def hetero_views(self):
+        """The [O, I, R] view and channel groups of every parameter of the width-1 model, in
+        ``named_parameters`` order (hetero.SliceView).  One group per stage: the residual
+        partners, the batch norms on them and the blocks' inner channels share its shift; the
+        image channels and the classes never scale."""
+        from .hetero import SliceView, vector_view
+
+        def conv(name, cout, cin, k, gin):
+            return SliceView(name, (cout, cin, k, k), (cout, cin, k * k), f"s{cout}", gin)
+
+        def bn(name, c):
+            return [vector_view(f"{name}.weight", c, f"s{c}"), vector_view(f"{name}.bias", c, f"s{c}")]
+
+        views = [conv("conv1.weight", 64, 3, 3, None)] + bn("bn1", 64)
+        cin = 64
+        for li, cout in enumerate(self.STAGES, start=1):
+            for b in range(2):
+                pre = f"layer{li}.{b}"
+                views += [conv(f"{pre}.conv1.weight", cout, cin, 3, f"s{cin}")] + bn(f"{pre}.bn1", cout)
+                views += [conv(f"{pre}.conv2.weight", cout, cout, 3, f"s{cout}")] + bn(f"{pre}.bn2", cout)
+                if cin != cout:
+                    views += [conv(f"{pre}.shortcut.0.weight", cout, cin, 1, f"s{cin}")]
+                    views += bn(f"{pre}.shortcut.1", cout)
+                cin = cout
+        o = self.linear.out_features
+        return views + [SliceView("linear.weight", (o, 512), (o, 512, 1), None, "s512"),
+                        vector_view("linear.bias", o, None)]
 
     def forward(self, x):
         out = F.relu(self.bn1(self.conv1(x)))

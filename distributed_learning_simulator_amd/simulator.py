@@ -42,6 +42,8 @@
     python -m distributed_learning_simulator_amd.simulator --distributed_algorithm fed_scaffold \\
         --worker_number 10 --round 5 [--scaffold_global_lr 1.0] [--scaffold_mu 0] \\
         [--scaffold_control 1|0]
+    python -m distributed_learning_simulator_amd.simulator --distributed_algorithm fed_hetero \\
+        --worker_number 10 --round 5 [--hetero_widths 1,0.5,0.25] [--hetero_rolling 0|1]
 
 Same flags and flow as the reference: IID split of the training set over the
 workers (:48-50), a tester on the test split (:51), ``factory.get_server``
@@ -79,6 +81,7 @@ QSGD_DEFAULTS = {"qsgd_bits": 4, "qsgd_norm": "l2", "qsgd_seed": 0}
 MX_DEFAULTS = {"mx_format": "e4m3", "mx_rounding": "nearest", "mx_error_feedback": None,
                "mx_seed": 0}
 SCAFFOLD_DEFAULTS = {"scaffold_global_lr": 1.0, "scaffold_mu": 0.0, "scaffold_control": 1}
+HETERO_DEFAULTS = {"hetero_widths": (1.0,), "hetero_rolling": 0}
 # the fed_secagg flags and what they hold when not given (threshold None: a majority)
 SECAGG_FLAGS = {**{name: int(v) for name, v in SECAGG_DEFAULTS.items()},
                 "secagg_dropouts": (), "secagg_threshold": None}
@@ -237,6 +240,12 @@ def get_config(argv=None):
     ap.add_argument("--scaffold_global_lr", type=float, default=None)
     ap.add_argument("--scaffold_mu", type=float, default=None)
     ap.add_argument("--scaffold_control", type=int, default=None, choices=(0, 1))
+    # fed_hetero: worker i trains the model at width ratio --hetero_widths[i mod len] (HeteroFL: the
+    # first ceil(r * C) channels of every hidden layer) and the server averages every coordinate
+    # over the workers that hold it; --hetero_rolling 1 moves every window on by one channel per
+    # round (FedRolex), so that every coordinate gets trained
+    ap.add_argument("--hetero_widths", type=_width_ratios, default=None)
+    ap.add_argument("--hetero_rolling", type=int, default=None, choices=(0, 1))
     # fed_secagg: every worker sends its update quantised to --secagg_bits bits with
     # --secagg_frac_bits fractional ones (defaults 20 and 16: +-8 at 1.5e-5) and masked in
     # Z_2^32 with the pair and self masks of the Philox stream under --secagg_seed;
@@ -339,6 +348,13 @@ def get_config(argv=None):
         ap.error("--scaffold_global_lr must be positive")
     if not config.scaffold_mu >= 0.0:
         ap.error("--scaffold_mu must not be negative")
+    if config.distributed_algorithm != "fed_hetero" and any(
+            getattr(config, name) is not None for name in HETERO_DEFAULTS):
+        ap.error("--hetero_widths and --hetero_rolling apply to --distributed_algorithm "
+                 "fed_hetero alone")
+    for name, default in HETERO_DEFAULTS.items():
+        if getattr(config, name) is None:
+            setattr(config, name, default)
     if config.topk_ratio is None:
         config.topk_ratio = TOPK_DEFAULTS["topk_ratio"]
     if config.topk_error_feedback is None:
@@ -366,6 +382,26 @@ def _worker_ids(text):
         return tuple(int(t) for t in text.split(",") if t.strip())
     except ValueError:
         raise argparse.ArgumentTypeError(f"comma-separated worker ids expected, not {text!r}")
+
+
+def _width_ratios(text):
+    """"1,0.5,0.25" -> (1.0, 0.5, 0.25), every ratio in (0, 1]."""
+    try:
+        widths = tuple(float(t) for t in text.split(",") if t.strip())
+    except ValueError:
+        widths = ()
+    if not widths or not all(0.0 < w <= 1.0 for w in widths):
+        raise argparse.ArgumentTypeError(f"comma-separated width ratios in (0, 1] expected, not {text!r}")
+    return widths
+
+
+def hetero_width(config, worker_id):
+    """The width ratio run() builds worker ``worker_id``'s model at: --hetero_widths dealt
+    round-robin by id under fed_hetero, 1 (today's model) under every other algorithm."""
+    if config.distributed_algorithm != "fed_hetero":
+        return 1.0
+    widths = getattr(config, "hetero_widths", HETERO_DEFAULTS["hetero_widths"])
+    return float(widths[worker_id % len(widths)])
 
 
 def server_kwargs(config):
@@ -421,6 +457,9 @@ def server_kwargs(config):
                                       SCAFFOLD_DEFAULTS["scaffold_global_lr"])
         kwargs["control"] = bool(getattr(config, "scaffold_control",
                                          SCAFFOLD_DEFAULTS["scaffold_control"]))
+    if config.distributed_algorithm == "fed_hetero":  # the widths run() deals to the workers
+        kwargs["widths"] = tuple(getattr(config, "hetero_widths", HETERO_DEFAULTS["hetero_widths"]))
+        kwargs["rolling"] = bool(getattr(config, "hetero_rolling", HETERO_DEFAULTS["hetero_rolling"]))
     return kwargs
 
 
@@ -518,14 +557,17 @@ def run(config, devices=None, sharded=None):
         try:
             torch.cuda.set_device(device)
             idx = shards[worker_id]
-            trainer = Trainer(model_cls(), (X[idx], y[idx]), (Xt, yt), epoch=config.epoch,
+            width = hetero_width(config, worker_id)
+            model = model_cls() if width == 1.0 else model_cls(width=width)
+            extra = {"width": width} if config.distributed_algorithm == "fed_hetero" else {}
+            trainer = Trainer(model, (X[idx], y[idx]), (Xt, yt), epoch=config.epoch,
                               batch_size=config.batch_size, learning_rate=config.learning_rate,
                               momentum=config.momentum, weight_decay=config.weight_decay,
                               optimizer_name=config.optimizer_name, device=device,
                               seed=config.seed + worker_id)
             worker = get_worker(config.distributed_algorithm, trainer=trainer,
                                 worker_data_queue=server.worker_data_queue, round=config.round,
-                                worker_id=worker_id, **worker_kwargs(config))
+                                worker_id=worker_id, **worker_kwargs(config), **extra)
             worker.train(device=device)
         except BaseException as e:  # surfaced after join
             errors.append(e)

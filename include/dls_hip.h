@@ -467,6 +467,70 @@ int dls_scaffold_server_step_f32(const float *U, int64_t ldu, const int32_t *row
                                  float *x_out, float *c_out, int32_t control,
                                  dls_stream_t stream);
 
+/* Width-heterogeneous FedAvg (csrc/hetero.hip; HeteroFL, Diao, Ding & Tarokh 2021; FedRolex,
+ * Alam, Liu, Yan & Zhang 2022): clients train narrower copies of the model and the server
+ * averages every coordinate over the clients that hold it.  The reference simulator has
+ * neither: the definitions below are this library's and tests/hetero_ref.py restates them in
+ * numpy float32.
+ *
+ * The slice model.  The global row is T tensors in the flat layout (each starts at a multiple
+ * of 64 elements, the padding follows it); tensor t is an array [O, I, R] in row-major order.  A
+ * width level l holds O_l <= O and I_l <= I indices of the first two dimensions: its local
+ * index jo stands for the global index (shO + jo) mod O, ji for (shI + ji) mod I (shift 0: a
+ * prefix, HeteroFL; shift = round mod C: FedRolex).  The level's own tensor is the contiguous
+ * [O_l, I_l, R] at its own flat-layout offset in the level's compact row of P_l elements.
+ *
+ * The plan, int32 words, host-made; an entry point takes the host copy, checks EVERY word of
+ * it before anything is launched (the kernels index with them), and hands the kernel the
+ * device copy `plan_dev` of the same words, which the caller keeps in step:
+ *   [0] DLS_HETERO_MAGIC  [1] T  [2] L  [3] tiles  [4] P  [5..7] 0  [8 + l] P_l (0 for l >= L)
+ *   [16 + t]                    tile prefix: the DLS_HETERO_TILE-element tiles of tensors 0..t,
+ *                               ceil(pad64(O I R) / DLS_HETERO_TILE) each
+ *   [16 + T + t * 76 ...]       tensor t: 12 words  offset, O, I, R, m(I R), s(I R), m(R), s(R),
+ *                               vector path (0 / 1), O I R, I R, pad64(O I R)
+ *                               then per level l < 8 (zeros past L) 8 words  offset in the level's
+ *                               row, O_l, I_l, shO, shI, I_l R, O_l I_l R, 0
+ * (m, s)(d) divide by d without an integer divide: floor(n / d) = mulhi32(n, m) >> s for n <
+ * 2^31 with l = ceil(log2 d), m = floor(2^(31 + l) / d) + 1, s = l - 1; d = 1 is m = s = 0.
+ * The vector path is taken by a tensor with every shift 0 and I R and every I_l R multiples of
+ * 4.  1 <= L <= DLS_HETERO_MAX_LEVELS, 1 <= T <= DLS_HETERO_MAX_TENSORS, a tensor has at
+ * most 2^30 elements and P, P_l < 2^31.
+ *
+ * dls_hetero_fedavg_f32, the server's round in one launch.  clients: K records of 4 words in id
+ * order, {level, the bits of w_k = fl32(n_k), row start low, high}, host copy and device copy
+ * as for the plan; client k's compact row is ragged[start_k, start_k + P_level) (start_k a
+ * multiple of 4, inside ragged_len).  Per global coordinate j of a tensor, M_j the clients
+ * whose level holds j, in ascending k:
+ *   M_j empty:  out[j] has the bits of prev[j] (NaN payloads and -0 kept)
+ *   otherwise:  acc = fl(w_k u_k[j]) of the first member, acc = fl(acc + fl(w_k u_k[j])) of the
+ *               rest; den = the same chain over w_k; out[j] = fl(acc / den), correctly rounded
+ * Every operation is rounded once and never fused, so the bits are defined wherever the result
+ * is not NaN; a non-finite value of one client reaches only the coordinates that client holds.
+ * The padding after a tensor is written as zero.  out may be prev itself and overlaps nothing
+ * else.  No atomics; the same bits for any stream or CU count.  sum_k 4 P_k + 8 P bytes of HBM
+ * traffic.  DLS_EINVAL: a null pointer, a word of the plan that does not follow, K outside
+ * 1..DLS_HETERO_MAX_K, a level outside the plan, a weight that is not finite and > 0, a row
+ * outside ragged; DLS_ELAYOUT: a device pointer that is not 16-byte aligned.
+ *
+ * dls_hetero_extract_f32, the downlink in one launch: rows[sum_{m < l} P_m + ...] becomes level
+ * l's compact row of `global`, every element a bit-for-bit copy, every padding zero; the global
+ * row is read once.  rows_len >= sum_l P_l; rows overlaps nothing. */
+#define DLS_HETERO_MAGIC 0x48545231
+#define DLS_HETERO_MAX_LEVELS 8
+#define DLS_HETERO_MAX_K 1024
+#define DLS_HETERO_MAX_TENSORS 4096
+#define DLS_HETERO_TILE 1024
+#define DLS_HETERO_HEADER_WORDS 16
+#define DLS_HETERO_TENSOR_WORDS 12
+#define DLS_HETERO_LEVEL_WORDS 8
+int dls_hetero_fedavg_f32(const int32_t *plan, const int32_t *plan_dev, int64_t plan_words,
+                          const int32_t *clients, const int32_t *clients_dev, int32_t K,
+                          const float *ragged, int64_t ragged_len, const float *prev, float *out,
+                          dls_stream_t stream);
+int dls_hetero_extract_f32(const int32_t *plan, const int32_t *plan_dev, int64_t plan_words,
+                           const float *global, float *rows, int64_t rows_len,
+                           dls_stream_t stream);
+
 /* Subset aggregation as a dense fp32 MFMA contraction: out[S, P] = C[S, K] · U[rows, P]
  * (C row-major [S, K], c_si = n_i / N_S; rows[K] selects the K client rows of U).
  * fp32 in / fp32 accumulate (v_mfma_f32_32x32x2_f32): per element one fma chain in
